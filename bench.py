@@ -5,10 +5,12 @@ ranks with one RCCL all-gather of the per-cell probabilities = configs[3]).
 
 One step = one pass of the hot path over the tile, inputs (uint16 image, int32 mask, packed weights) resident in HBM:
 normalise -> label table -> per-cell crop / soft mask -> 5 x (patch-embed, 12 blocks, head, softmax) -> vote -> labels
-on the host.  Prints ONE JSON line (rank 0).  ``roofline`` is measured live with HIP events around every GEMM launch of
-one extra (untimed) profiled pass; ``cpu_baseline`` times the CPU oracle on a bounded sample of the same workload;
-``dropin`` times the boundary itself (``Annotator.preprocess -> predict -> export_annotations`` from host ``.npy`` files,
-H2D copies and the CSV included) on the same tile.
+on the host.  Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ``--steps`` steps and prints the line;
+``--dump-outputs DIR`` also writes what the last timed step returned (per-cell labels and confidences) as ``DIR/<name>.npy``.
+``--full`` adds what the headline figure does not need: ``roofline``, measured live with HIP events around every GEMM launch
+of one extra (untimed) profiled pass per classifier; ``cpu_baseline``, the CPU oracle timed on a bounded sample of the same
+workload; ``dropin``, the boundary itself (``Annotator.preprocess -> predict -> export_annotations`` from host ``.npy``
+files, H2D copies and the CSV included) timed on the same tile; ``parity_audit``, quoted from the committed profile.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (``torch.distributed.run`` as a child
 process, before this process touches a GPU); under the driver's own ``torch.distributed.run`` launch it is just a rank.
@@ -47,7 +49,20 @@ def parse():
     ap.add_argument("--config1", action="store_true", help="BASELINE configs[0] stand-in (example_1 mask, Basic panel, bs 8): drop-in on the GPU "
                                                             "beside the CPU oracle timed IN FULL")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous + one all-gather only (no GPU work): CPU test of the N-rank launch path")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the roofline pass, the drop-in "
+                                                         "(Annotator) timing, the CPU-oracle baseline and the parity-audit quote")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the per-cell labels and confidences "
+                                                                           "of the last timed step as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.config1:
+        ap.error("--dump-outputs applies to the tile workload, not --config1")
+    if not args.full:      # a plain run does only what its headline figure needs
+        args.no_cpu_baseline = args.no_roofline = args.no_dropin = True
+    return args
 
 
 def visible_gpu_count() -> int:
@@ -349,6 +364,8 @@ def main():
         tdist.all_reduce(t, op=tdist.ReduceOp.SUM)
         total_cells = int(t.item())
     value = total_cells * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"labels": lab, "confidence": conf})
 
     out = {
         "metric": "cells/sec annotated (whole node)", "value": round(value, 2), "unit": "cells/s", "n_gpus": world, "steps": args.steps,
@@ -402,7 +419,8 @@ def main():
     if imputer is not None:      # the imputer's own load-time probe: its imputed plane against the fp16x3 imputer's on 64 probe cells (bar 1e-3)
         out["imputer_probe_plane_delta"] = imputer.probe_plane_delta
         out["imputer_fast_path_in_use"] = imputer.fast_ok
-    out["parity_audit"] = parity_audit_record(out["kernel_source_sha256"])
+    if args.full:
+        out["parity_audit"] = parity_audit_record(out["kernel_source_sha256"])
     if sharded:
         ag_ms = sum(a.elapsed_time(b) for a, b in ag_events)
         out["collective"] = collective_record(world, ag_ms, args.steps, ag_state.get("local", torch.zeros(0)))
@@ -607,6 +625,26 @@ def main():
         # destroyed on some ranks while another still holds it is the kind of exit RCCL may not take quietly)
         tdist.barrier()
         tdist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: the per-cell arrays the last timed step handed its caller (the vote's label, a global class index, and its
+    confidence), as float32 ``.npy`` files.  Beyond DUMP_LIMIT_BYTES in all, a fixed seeded sample of the cells is written, with the
+    sampled cell indices as ``cell_index.npy``."""
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_cell = sum(a.itemsize for a in arrays.values())
+    if n * per_cell > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (per_cell + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["cell_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def fused_attn_on():

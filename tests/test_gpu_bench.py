@@ -18,7 +18,7 @@ def test_two_rank_bench_line_on_a_shared_gpu():
         env.pop(k, None)
     env.update(RIBCA_DIST_BACKEND="gloo", RIBCA_SHARE_GPU="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cells", "3000", "--size", "768", "--steps", "1",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-dropin"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-dropin"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

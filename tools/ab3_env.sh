@@ -10,7 +10,7 @@ F=$OUT/ab_$VAR.txt
 : > "$F"
 for i in $(seq "$REP"); do
   for v in "$@"; do
-    line=$(env "$VAR=$v" python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-dropin 2>/dev/null | tail -1)
+    line=$(env "$VAR=$v" python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-dropin 2>/dev/null | tail -1)
     echo "$VAR=$v: $(echo "$line" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); k=d.get("per_kernel_ms") or {}; print(d["value"], "cells/s", d["ms_per_step"], "ms", {x: k[x] for x in ("gemm_qkv","gemm_fc1","gemm_fc2","gemm_proj","cell_qkv_attention","layernorm") if x in k})')" | tee -a "$F"
   done
 done

@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 ALT=${1:?alternative library}
 for rep in $(seq 1 ${2:-3}); do
   for lib in $ALT libribca_hip.so; do
-    RIBCA_LIB=$lib timeout -k 10 250 python3 bench.py --steps 3 --no-cpu-baseline --no-dropin 2>/dev/null \
+    RIBCA_LIB=$lib timeout -k 10 250 python3 bench.py --full --steps 3 --no-cpu-baseline --no-dropin 2>/dev/null \
       | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', d['value'], d['ms_per_step'], json.dumps(d['per_kernel_ms']))" || exit 1
   done
 done
