@@ -103,18 +103,6 @@ int ribca_test_gemm_duo_gelu(const uint16_t* A, int32_t lda, const uint16_t* W, 
 int ribca_test_cell_attention(const uint16_t* z_ps, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D,
                               const float* bias2, const float* csum, const float* rowstat, uint16_t* out, int32_t ldo, void* stream);
 int32_t ribca_gemm_padded_n(int32_t N);
-/* Measurement hooks of the DIAGNOSTIC library (libribca_hip_diag.so, built with -DRIBCA_DIAG; tools/ only).  In the product library
- * every variant runs the production kernel.  0 = production GEMM; 3 = without the half-step stagger; 4/5/7/9/20-24 = timing
- * ablations (no loads / loads only / no loads + stagger / no epilogue / fewer MFMA passes) whose RESULTS ARE WRONG by construction;
- * 12 = production kernel + time stamps; 30 = persistent workgroups; 40-49 = the two-workgroups-per-CU kernel and its ablations. */
-int ribca_set_gemm_variant(int32_t v);
-/* Diagnostics for variants 12 / 48: device buffer of 20 x uint64 per workgroup receiving 100 MHz time stamps (entry, first stage
- * landed, K loop done, epilogue stores accepted), the XCC / HW id the workgroup ran on, and in [6..17] the time each of the 12
- * waves had its epilogue stores accepted.  capacity_blocks = workgroups the buffer has room for (workgroups beyond it do not
- * stamp).  NULL disables. */
-int ribca_set_gemm_stamps(void* dev_buffer, int64_t capacity_blocks);
-/* 1 if this library carries the diagnostic kernel forms (-DRIBCA_DIAG), else 0 */
-int ribca_is_diag_build(void);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

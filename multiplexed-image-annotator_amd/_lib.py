@@ -10,8 +10,7 @@ import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# RIBCA_DIAG=1 selects the diagnostic library (same ABI + the A/B and timing-ablation kernel forms; `build --diag`): tools/ only
-LIB_PATH = os.path.join(HERE, "libribca_hip_diag.so" if os.environ.get("RIBCA_DIAG") == "1" else "libribca_hip.so")
+LIB_PATH = os.path.join(HERE, "libribca_hip.so")
 # RIBCA_LIB=<file name next to this module, or a path>: another build of the same library (same-box A/B of two builds, tools/ab_env.sh)
 if os.environ.get("RIBCA_LIB"):
     LIB_PATH = os.environ["RIBCA_LIB"] if os.path.isabs(os.environ["RIBCA_LIB"]) else os.path.join(HERE, os.environ["RIBCA_LIB"])
@@ -106,9 +105,6 @@ TEST_SIGNATURES = {
     "ribca_test_cell_attention": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                             c_void_p]),
     "ribca_gemm_padded_n": (c_int32, [c_int32]),
-    "ribca_set_gemm_variant": (c_int32, [c_int32]),
-    "ribca_set_gemm_stamps": (c_int32, [c_void_p, c_int64]),
-    "ribca_is_diag_build": (c_int32, []),
 }
 
 
@@ -151,8 +147,6 @@ def _load_test_lib():
         handle = ctypes.CDLL(TEST_LIB_PATH)
         _bind(handle, TEST_SIGNATURES)
         _test_lib = handle
-        if os.environ.get("RIBCA_GEMM_VARIANT"):
-            handle.ribca_set_gemm_variant(int(os.environ["RIBCA_GEMM_VARIANT"]))
     return _test_lib
 
 
@@ -170,8 +164,6 @@ def lib() -> _Library:
         handle = ctypes.CDLL(LIB_PATH)
         _bind(handle, SIGNATURES)
         _lib = _Library(handle)
-        if os.environ.get("RIBCA_GEMM_VARIANT"):
-            _load_test_lib()
     return _lib
 
 

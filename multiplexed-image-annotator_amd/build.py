@@ -13,11 +13,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libribca_hip.so")
-LIB_DIAG = os.path.join(HERE, "libribca_hip_diag.so")
 # kernel-level hooks of tests/ and tools/ (include/ribca_hip_test.h): a library of their own, linked against the product library -- the same
 # launchers and kernels, none of them exported by libribca_hip.so itself
 LIB_TEST = os.path.join(HERE, "libribca_hip_test.so")
-LIB_TEST_DIAG = os.path.join(HERE, "libribca_hip_diag_test.so")
 TEST_SOURCES = ["ribca_test_api.hip"]
 EXPORTS = os.path.join(CSRC, "exports.map")
 SOURCES = ["gemm_split16.hip", "gemm_duo.hip", "gemm_mx.hip", "attention.hip", "cell_attention.hip", "vit_misc.hip", "preprocess.hip", "preprocess_scaled.hip", "vote.hip", "colorize.hip", "knn.hip", "normalize.hip", "ribca_api.hip"]
@@ -60,14 +58,10 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
-    """diag=True builds libribca_hip_diag.so with -DRIBCA_DIAG: the product kernels plus the A/B / timing-ablation / stamp forms that
-    tools/ drive (select it at run time with RIBCA_DIAG=1).  The product library carries none of them."""
+def build(force: bool = False, verbose: bool = True) -> str:
     srcs = [s for s in SOURCES + TEST_SOURCES if os.path.exists(os.path.join(CSRC, s))]
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
-    objdir = os.path.join(HERE, "build_diag" if diag else "build")
-    lib_path = LIB_DIAG if diag else LIB
-    flags = FLAGS + (["-DRIBCA_DIAG"] if diag else [])
+    objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
 
@@ -75,7 +69,7 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         path = os.path.join(CSRC, src)
         if force or _stale(obj, [path] + hdrs):
-            cmd = [hipcc] + flags + ["-c", path, "-o", obj]
+            cmd = [hipcc] + FLAGS + ["-c", path, "-o", obj]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, r.stdout, r.stderr))
@@ -88,24 +82,23 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
         res = list(ex.map(compile_one, srcs))
     objs = [o for (o, _), src in zip(res, srcs) if src not in TEST_SOURCES]
     test_objs = [o for (o, _), src in zip(res, srcs) if src in TEST_SOURCES]
-    if force or _stale(lib_path, objs + [EXPORTS]):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(lib_path), "-Wl,--version-script=" + EXPORTS, "-o", lib_path] + objs
+    if force or _stale(LIB, objs + [EXPORTS]):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(LIB), "-Wl,--version-script=" + EXPORTS, "-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n%s\n%s" % (r.stdout, r.stderr))
-    test_path = LIB_TEST_DIAG if diag else LIB_TEST
-    if force or _stale(test_path, test_objs + [lib_path, EXPORTS]):
-        libname = os.path.basename(lib_path)[3:-3]
+    if force or _stale(LIB_TEST, test_objs + [LIB, EXPORTS]):
+        libname = os.path.basename(LIB)[3:-3]
         # --no-undefined: the hooks reach the product library through its C entry points (ribca_internal_table) only; a stray direct reference to a
         # hidden launcher fails HERE, not at dlopen on the GPU box
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-Wl,--version-script=" + EXPORTS, "-o", test_path] + test_objs + ["-L" + HERE, "-l" + libname, "-Wl,-rpath,$ORIGIN"]
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-Wl,--version-script=" + EXPORTS, "-o", LIB_TEST] + test_objs + ["-L" + HERE, "-l" + libname, "-Wl,-rpath,$ORIGIN"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n%s\n%s" % (r.stdout, r.stderr))
     if verbose:
-        print("built", lib_path)
-    return lib_path
+        print("built", LIB)
+    return LIB
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv, diag="--diag" in sys.argv)
+    build(force="--force" in sys.argv)

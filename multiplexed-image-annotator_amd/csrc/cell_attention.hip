@@ -19,7 +19,6 @@
 // * S^T = K Q^T per 16-key tile, softmax over keys in registers + two xor-shuffles, P in place as the next operand, O^T = V^T P^T:
 //   the arithmetic and its order per (query, key, dim) are those of gemm + attention.hip, so results agree to rounding with the
 //   unfused path (tests/test_gpu_kernels.py::test_cell_attention_fused compares with fp64 and with the unfused kernels).
-#include <cstdlib>
 
 #include "gemm_epi.h"
 #include "ribca_common.h"
@@ -64,25 +63,12 @@ template <int D, int HD>
 __global__ __launch_bounds__(512) void cell_qkv_attention_kernel(const uint16_t* __restrict__ z, int ldz, const uint16_t* __restrict__ W, int ldw,
                                                                  const float* __restrict__ bias2, const float* __restrict__ csum,
                                                                  const float2* __restrict__ rowstat, uint16_t* __restrict__ out, int ldo, int T,
-                                                                 float scale, int dbg_arg) {
-  // timing ablations exist in the diagnostic library only (RIBCA_CELL_DBG, tools/bench_cell_attention.py); the product kernel has none
-#ifdef RIBCA_DIAG
-  const int dbg = dbg_arg;
-#else
-  constexpr int dbg = 0;
-  (void)dbg_arg;
-#endif
+                                                                 float scale) {
   using G = CellGeom<D, HD>;
   constexpr int NK = G::NK, GROUPS = G::GROUPS, HPG = G::HPG, kRing = G::RING, kGroupDims = G::GD, NTP = G::NTP, kWStage = G::WSTAGE;
   constexpr int NTILES = 3 * NTP;              // accumulator tiles per wave and group: q | k | v
   constexpr int TOTAL = GROUPS * NK;           // K steps of the whole cell
-#ifdef CELLDBG_MXBOUND      // timing-only bound (results wrong on purpose; tools/build_ab_lib.py ... -DCELLDBG_MXBOUND): what the weight stream in an
-  // MX image (fp16 hi + fp6 lo: ~2/3 of the bytes) and one correction on the block-scaled instruction could buy the QKV phase at most --
-  // 2/3 of the DMA pieces per stage, no lo fragment reads, 2 of the 3 MFMAs per tile and step
-  constexpr int GPL = G::WROWS / 8 * 2 / 3;
-#else
   constexpr int GPL = G::WROWS / 8;            // 18 / 24 DMA instructions (1 KB each) per stage
-#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -126,16 +112,10 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_kernel(const uint16_t*
     issue(0);
     issue(1);
     for (int step = 0; step < TOTAL; ++step) {
-#ifdef CELLDBG_HALFBAR      // timing-only (results racy on purpose): what half the step barriers (64-deep ring stages) would buy
-      if ((step & 1) == 0 || step + 1 == TOTAL) {
-#endif
       if (step + 1 < TOTAL) wait_vmcnt<GPL>();
       else wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();                            // stage `step` landed; the slot of step - 1 has been read by everyone
       asm volatile("" ::: "memory");
-#ifdef CELLDBG_HALFBAR
-      }
-#endif
       if (step + 2 < TOTAL) issue(step + 2);
       if ((step + 1) % NK == 0) __builtin_amdgcn_s_barrier();  // the group's "k, v published" barrier
     }
@@ -176,33 +156,20 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_kernel(const uint16_t*
       // in the ISA) -- and the slot is only protected by the DMA's latency exceeding an LDS read's.  That is the non-repeatability the
       // round-3 buffer-descriptor loader showed (a few rows per thousand cells at D = 144 / 288): it issues its first piece a few
       // cycles behind the barrier instead of ~70 and so closed the window.
-#ifdef CELLDBG_HALFBAR
-      if ((step & 1) == 0 || step + 1 == TOTAL) {
-#endif
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-#ifdef CELLDBG_HALFBAR
-      }
-#endif
       const char* st = smem + (step % kRing) * kWStage;
-      if (dbg & 2) continue;                                   // timing ablation: barriers and the weight stream only
 #pragma unroll
       for (int jb = 0; jb < NTILES / 3; ++jb) {
         f16x8 whi[3], wlo[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           whi[j] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(st + w_rd[3 * jb + j]));
-#ifndef CELLDBG_MXBOUND
           wlo[j] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(st + (w_rd[3 * jb + j] ^ 16)));
-#else
-          wlo[j] = whi[j];
-#endif
         }
-#ifndef CELLDBG_MXBOUND
 #pragma unroll
         for (int j = 0; j < 3; ++j) acc[3 * jb + j] = mfma_f16(wlo[j], ahi[s], acc[3 * jb + j]);
-#endif
 #pragma unroll
         for (int j = 0; j < 3; ++j) acc[3 * jb + j] = mfma_f16(whi[j], alo[s], acc[3 * jb + j]);
 #pragma unroll
@@ -264,7 +231,6 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_kernel(const uint16_t*
     __builtin_amdgcn_s_barrier();                              // k, v of every token are in LDS
     asm volatile("" ::: "memory");
 
-    if (dbg & 1) continue;                                     // timing ablation (RIBCA_CELL_DBG=1): no attention phase, results wrong
     // ---- attention of the group's heads for this wave's 16 queries, TWO heads at a time: the S^T MFMAs of one head cover the softmax
     // VALU of the other, and the two P V products interleave (a wave is in-order: without a second independent chain every
     // exp / split waits behind the MFMAs that feed it)
@@ -373,12 +339,7 @@ void launch_cell_qkv_attention(const uint16_t* z, int ldz, const uint16_t* W, in
     static unsigned long long attr_done[3] = {0ull, 0ull, 0ull};      // per width (one kernel instantiation each) and device
     const int slot = D == 288 ? 1 : D == 384 ? 2 : 0;
     if (!ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done[slot])) return;
-#ifdef RIBCA_DIAG
-    static const int dbg = getenv("RIBCA_CELL_DBG") ? atoi(getenv("RIBCA_CELL_DBG")) : 0;      // timing ablations of tools/bench_cell_attention.py
-#else
-    const int dbg = 0;
-#endif
-    hipLaunchKernelGGL(kern, dim3(cells), dim3(512), lds, s, z, ldz, W, ldw, bias2, csum, rowstat, out, ldo, (int)kTokens, scale, dbg);
+    hipLaunchKernelGGL(kern, dim3(cells), dim3(512), lds, s, z, ldz, W, ldw, bias2, csum, rowstat, out, ldo, (int)kTokens, scale);
   };
   if (D == 288) go(cell_qkv_attention_kernel<288, 24>, CellGeom<288, 24>::LDS);
   else if (D == 384) go(cell_qkv_attention_kernel<384, 32>, CellGeom<384, 32>::LDS);

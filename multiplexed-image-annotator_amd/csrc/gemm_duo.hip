@@ -24,9 +24,6 @@
 //   bit-identical to that kernel's.
 // * Epilogue straight from the accumulator registers (run_epilogue): its latency chain and store shape now overlap the other
 //   workgroup's K loop.
-#include <cstdlib>
-#include <map>
-#include <tuple>
 #include <type_traits>
 #include <utility>
 
@@ -79,16 +76,6 @@ void launch_pack_wf(const uint16_t* W, int ldw, int Np, int Kp, uint16_t* WF, hi
   hipLaunchKernelGGL(pack_wf_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, W, ldw, Np, nk, WF);
 }
 
-// Diagnostic stamps (ABL = 4, variant 44): same record as gemm_split16.hip's variant 12 -- per workgroup t0 entry, t1 first stage
-// landed, t2 K loop done, t3 stores accepted (wave 0), XCC id, HW id, then each wave's "stores accepted" -- into a buffer nothing reads.
-static __device__ unsigned long long* g_duo_stamps = nullptr;
-static __device__ unsigned int g_duo_stamp_cap = 0;      // workgroups the buffer has room for: larger grids do not stamp
-int duo_set_stamp_buffer(void* dev_ptr, unsigned int capacity_blocks) {
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_duo_stamp_cap), &capacity_blocks, sizeof(capacity_blocks)) != hipSuccess) return 1;
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_duo_stamps), &dev_ptr, sizeof(dev_ptr));
-}
-
-// ABL bit mask (timing ablations, results wrong on purpose): 1 = no epilogue, 2 = no A loads, 4 = no W loads; 8 = stamps (results correct)
 // BM = rows of the tile: 256 with a 2-stage A ring (64 KB; operands of step k + 1 in flight during step k), or 192 with a 3-stage ring
 //      (72 KB) and three W register sets: operands of steps k + 1 and k + 2 in flight.  One K step of one workgroup is 0.55-0.75 us
 //      of MFMA issue, an L2 round trip under load 1-1.5 us: with one step of prefetch a workgroup that has the CU's matrix pipe to
@@ -102,9 +89,9 @@ int duo_set_stamp_buffer(void* dev_ptr, unsigned int capacity_blocks) {
 // from a single in-order wave beside the neighbour workgroup's MFMA stream -- measured 14.5 cycles per VALU instruction, 13 us per
 // tile against 5.4 us with the CU to itself, and the neighbour's K loop a third slower.  8 waves (128 registers each) put two
 // waves per SIMD on every phase.
-template <int BM, int NW, int WM, int TN, int NWS, class Epi, int ABL>
+template <int BM, int NW, int WM, int TN, int NWS, class Epi>
 __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint16_t* __restrict__ A, int lda, const uint16_t* __restrict__ WF, int M,
-                                                                       int Kp, int mtiles, int ntiles, Epi epi, int mode, int delay) {
+                                                                       int Kp, int mtiles, int ntiles, Epi epi) {
   static_assert(BM == 256 || BM == 192 || BM == 128, "tile rows");
   constexpr int NST = BM == 256 ? 2 : 3;      // ring stages
   static_assert(NWS == NST || (NST == 3 && NWS == 2), "W register sets");
@@ -117,47 +104,19 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
   constexpr int STAGE = BM * ROWB;            // A only
   constexpr int GPW = BM / 8 / NW;            // 8-row DMA groups per wave and stage
   static_assert(GPW * 8 * NW == BM, "DMA groups");
-  constexpr int NA = (ABL & 2) ? 0 : GPW, NWL = (ABL & 4) ? 0 : 2 * TN;   // vector-memory operations per K step and wave: A, W
+  constexpr int NA = GPW, NWL = 2 * TN;   // vector-memory operations per K step and wave: A, W
   // issue order inside a step: W (for step k + NWS - 1), then A (for step k + NST - 1); what may stay in flight at the top of step k
   constexpr int FLY = NST == 2 ? 0 : (NWS == 3 ? NA + NWL : NA);
   constexpr int PERIOD = NST == NWS ? NST : NST * NWS;
-  // z touch (EpiResid: the drain's z loads are HBM / Infinity-Cache misses, 13 of a tile's 17 us of epilogue here): every thread reads
-  // one dword of each 128-byte line of "its" row of the residual tile right behind the LAST operand batch; vmcnt retires in order,
-  // so the remaining waits leave these NT youngest operations in flight and nothing waits for them before the epilogue does.
-  constexpr int NT = (Epi::kTouch && !(ABL & 1)) ? BN / 32 : 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nblk = mtiles * ntiles;
   int bid = blockIdx.x;
   {
-    // blocks b, b + 8, ... run on one XCD (one L2): XCD x walks the contiguous tile range [first, first + cnt) with n fastest, so
-    // the n-tiles of an m-tile run together and its A rows are fetched once.  When the weight is larger than the L2 can keep
-    // beside the A / output streams (panel > 0: n-tiles per panel, chosen by the launcher), the whole m-tile rows of the range are
-    // walked panel by panel -- every m-tile's n-tiles of panel 0, then of panel 1, ... -- so a panel of W stays resident while the
-    // A rows stream past it (A is then fetched once per panel); the partial rows at the two ends of the range keep the plain order.
+    // blocks b, b + 8, ... run on one XCD (one L2): XCD x walks a contiguous tile range with n fastest, so the n-tiles of an
+    // m-tile run together and its A rows are fetched once.
     const int xcd = bid & 7, loc = bid >> 3;
     const int q = nblk >> 3, r = nblk & 7;
-    const int first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int cnt = xcd < r ? q + 1 : q;
-    bid = first + loc;
-    const int panel = mode >> 8;
-    if (panel > 0 && panel < ntiles) {
-      const int r0 = (first + ntiles - 1) / ntiles, r1 = (first + cnt) / ntiles;     // whole m-tile rows [r0, r1)
-      const int head = r0 * ntiles - first;
-      if (r1 > r0 && loc >= head) {
-        int l = loc - head;
-        const int rows = r1 - r0;
-        if (l < rows * ntiles) {
-          int p0 = 0, w = panel;
-          while (l >= rows * w) {          // at most ntiles / panel iterations, uniform over the workgroup
-            l -= rows * w;
-            p0 += w;
-            w = ntiles - p0 < panel ? ntiles - p0 : panel;
-          }
-          const int rr = l / w;
-          bid = (r0 + rr) * ntiles + p0 + (l - rr * w);
-        }
-      }
-    }
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
   }
   const int mt = bid / ntiles, nt = bid - mt * ntiles;
   const int m0 = mt * BM, n0 = nt * BN;
@@ -170,33 +129,8 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
   // EpiResidZK: the residual tile's BN / 32 K steps follow the product's own through the same ring
   constexpr bool ZK = is_zk<Epi>::value;
   constexpr int ZS = ZK ? BN / 32 : 0;
-  static_assert(!ZK || (NST == 3 && ABL == 0), "the residual-through-the-ring form exists for the production tile only");
+  static_assert(!ZK || NST == 3, "the residual-through-the-ring form exists for the 3-stage tile only");
   const int nkz = nk + ZS;
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, tc1 = 0, tc2 = 0;      // tc: shader-clock stamps around the K loop (in-kernel clock)
-  if (ABL & 8) ts0 = __builtin_amdgcn_s_memrealtime();
-  // the scheduling A/B switches below (RIBCA_DUO_MODE) exist in the diagnostic library only; none of them paid
-#ifdef RIBCA_DIAG
-  const int lab = mode & 0xff;
-#else
-  constexpr int lab = 0;
-#endif
-  // mode bit 0: static wave priority by the CU's workgroup slot (TG_ID of HW_ID, bits 19:16); bit 1: the first round's odd-slot
-  // workgroups start `delay` x 10 ns late; bit 2: epilogue at raised priority (A/B switches: none paid)
-  if (lab & 3) {
-    unsigned int hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    const bool odd_slot = ((hwid >> 16) & 1u) != 0;
-    if (lab & 1) {
-      if (odd_slot) __builtin_amdgcn_s_setprio(0);
-      else __builtin_amdgcn_s_setprio(2);
-    }
-    if ((lab & 2) && odd_slot && (int)blockIdx.x < 1024) {
-      const unsigned long long until = __builtin_amdgcn_s_memrealtime() + (unsigned long long)delay;
-      while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(16);
-    }
-  }
-
-  if (lab & 8) __builtin_amdgcn_s_setprio(3);
   // ---- A ring: wave w loads the 8-row groups w, w + NW, ... of every stage (1 KB per instruction) through a buffer descriptor
   // over the tile's rows: ONE per-lane offset register, everything that varies (group, K step) in the scalar offset, and rows beyond
   // M read as zeros by the descriptor's range check (their outputs are dropped by the epilogue guards).
@@ -219,7 +153,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     z_gstride = 8 * NW * epi.ldz * 2;
   }
   auto issue_a = [&](int kk, int slot) {
-    if (ABL & 2) return;
     char* st = smem + slot * STAGE + wave * 1024;
     if (ZK && kk >= nk) {
       const int ko = n0 * 4 + (kk - nk) * (4 * BK);
@@ -245,7 +178,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
   const size_t wjstride = (size_t)nk * 2048;
   f16x8 whi[NWS][TN], wlo[NWS][TN];
   auto issue_w = [&](int kk, f16x8 (&hi)[TN], f16x8 (&lo)[TN]) {
-    if (ABL & 4) return;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const char* p = wbase + (size_t)j * wjstride + (size_t)kk * 2048;
@@ -277,29 +209,11 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     for (int i = 0; i < RB; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (ABL & 4) {
-#pragma unroll
-    for (int s = 0; s < NWS; ++s)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) whi[s][j] = wlo[s][j] = f16x8{};
-  }
 
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const unsigned a_hi = lds_base + (unsigned)lds_off(wm * (16 * MT) + r16, 2 * g);     // + 2048 per m-tile, + STAGE per slot
   const unsigned a_lo = a_hi ^ 16u;
 
-  unsigned int touched[NT > 0 ? NT : 1];
-  auto touch = [&]() {
-    if constexpr (NT > 0) {
-      const int trow = tid < BM ? tid : BM - 1;
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        const float* p = epi.touch_on() ? epi.touch_ptr(m0 + trow, n0 + 32 * i) : epi.touch_ptr(0, 0);
-        asm volatile("global_load_dword %0, %1, off" : "=v"(touched[i]) : "v"(p) : "memory");
-      }
-    }
-  };
-  const int last_issue = nk - NST;            // the step whose issue is the final operand batch (< 0: all issued in the prologue)
   // K step kk on ring slot SA = kk % NST with W set SW = kk % NWS
   auto step = [&](auto sa_c, auto sw_c, int kk) {
     constexpr int SA = decltype(sa_c)::value, SW = decltype(sw_c)::value;
@@ -307,9 +221,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     if constexpr (ZK) {                         // behind the last W batch only the next stage's A (or z) rows stay in flight
       if (kk + 1 < nk) wait_vmcnt<FLY>();
       else wait_vmcnt<NA>();
-    } else if (NT > 0 && kk > last_issue) {     // the touches sit behind every operand batch
-      if (FLY > 0 && kk + 1 < nk) wait_vmcnt<FLY + NT>();
-      else wait_vmcnt<NT>();
     } else {
       if (FLY > 0 && kk + 1 < nk) wait_vmcnt<FLY>();
       else wait_vmcnt<0>();
@@ -318,13 +229,11 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(whi[SW][j]), "+v"(wlo[SW][j]));
     __builtin_amdgcn_s_barrier();             // stage kk landed for every wave; the slot of stage kk - 1 read by all
     asm volatile("" ::: "memory");
-    if ((ABL & 8) && kk == 0) { ts1 = __builtin_amdgcn_s_memrealtime(); tc1 = __builtin_amdgcn_s_memtime(); }
     if (kk + NWS - 1 < nk) {
       constexpr int SN = (SW + NWS - 1) % NWS;
       issue_w(kk + NWS - 1, whi[SN], wlo[SN]);
     }
     if (kk + NST - 1 < nkz) issue_a(kk + NST - 1, (SA + NST - 1) % NST);
-    if (NT > 0 && kk == last_issue) touch();
     __builtin_amdgcn_sched_barrier(0);
     f16x8 ah[2], al[2];
     const unsigned a_hi_s = a_hi + (unsigned)(SA * STAGE), a_lo_s = a_lo + (unsigned)(SA * STAGE);   // (the 16-bit offset field cannot hold slot 2)
@@ -356,10 +265,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     if (S < NWS - 1 && S < nk) issue_w(S, whi[S], wlo[S]);
     if (S < nkz) issue_a(S, S);
   });
-  if (NT > 0 && last_issue < 0) touch();
-#ifdef RIBCA_KLOOP_PRIO      // A/B (tools/build_ab_lib.py ... -DRIBCA_KLOOP_PRIO): the K loop's waves ahead of the co-resident workgroup's epilogue waves at issue
-  __builtin_amdgcn_s_setprio(2);
-#endif
   int kk = 0;
   for (; kk + PERIOD <= nk; kk += PERIOD)
     static_for<PERIOD>([&](auto p_c) {
@@ -370,9 +275,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     constexpr int P = decltype(p_c)::value;
     if (kk + P < nk) step(std::integral_constant<int, P % NST>{}, std::integral_constant<int, P % NWS>{}, kk + P);
   });
-#ifdef RIBCA_KLOOP_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 
   if constexpr (ZK) {
     // ---- the residual tile: K step t holds columns n0 + 32 t .. + 31 of the stored rows; against the identity, the column tile whose
@@ -432,29 +334,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     });
   }
 
-  if (ABL & 8) { ts2 = __builtin_amdgcn_s_memrealtime(); tc2 = __builtin_amdgcn_s_memtime(); }
-  if (ABL & 1) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int i = 0; i < RB; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[b][i][j]));
-    if ((ABL & 8) && g_duo_stamps != nullptr && blockIdx.x < g_duo_stamp_cap && lane == 0) {
-      unsigned long long* o = g_duo_stamps + (size_t)blockIdx.x * 20;
-      o[6 + wave] = ts2;
-      if (wave == 0) {
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts2; o[18] = tc1; o[19] = tc2;
-        unsigned int xcc, hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        o[4] = xcc; o[5] = hwid;
-      }
-    }
-    return;
-  }
-  if (lab & 4) __builtin_amdgcn_s_setprio(3);
-  if (lab & 8) __builtin_amdgcn_s_setprio(0);     // bit 3: K loop at priority 3 (set below the prologue), epilogue back at 0
   const int mbase = m0 + wm * (16 * MT) + r16, nbase = n0 + wn * (16 * TN) + 4 * g;
   // a tile wholly inside the product (all but the last row of m-tiles, every n-tile when N is a multiple of BN) takes the unguarded
   // form of the epilogue: workgroup-uniform branch
@@ -478,171 +357,65 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_ps_duo_kernel(const uint
     static_assert(WM == 1 && TN == 2 && NB == 1, "the MX3-emitting GELU epilogue: 4 waves as 1 x 4 over a 128-wide tile");
     if (m0 + BM <= M) gelu_mx_epilogue<MT, true>(epi, m0 + r16, n0 + wn * 32, g, acc);
     else gelu_mx_epilogue<MT, false>(epi, m0 + r16, n0 + wn * 32, g, acc);
-  } else if (m0 + BM <= M && n0 + BN <= epi.N && !(mode & 0x10)) {      // mode bit 4 (RIBCA_DUO_GUARDED=1): A/B switch, always the guarded form
+  } else if (m0 + BM <= M && n0 + BN <= epi.N) {
 #pragma unroll
     for (int b = 0; b < NB; ++b) run_epilogue<TN, Epi, RB, true>(epi, mbase + 16 * RB * b, nbase, acc[b]);
   } else {
 #pragma unroll
     for (int b = 0; b < NB; ++b) run_epilogue<TN, Epi, RB>(epi, mbase + 16 * RB * b, nbase, acc[b]);
   }
-  if constexpr (NT > 0) {
-#pragma unroll
-    for (int i = 0; i < NT; ++i) asm volatile("" ::"v"(touched[i]));
-  }
-  if ((ABL & 8) && g_duo_stamps != nullptr && blockIdx.x < g_duo_stamp_cap && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long ts3 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o = g_duo_stamps + (size_t)blockIdx.x * 20;
-    o[6 + wave] = ts3;
-    if (wave == 0) {
-      o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3; o[18] = tc1; o[19] = tc2;
-      unsigned int xcc, hwid;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      o[4] = xcc; o[5] = hwid;
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// Fragment-order copies made on demand for weights that were not created through ribca_vit_create (tests, tools): keyed by the
-// packed weight's device address.  Model weights carry their own copy (GemmArgs::WF).
-#ifndef RIBCA_DIAG
-static const uint16_t* wf_for(const GemmArgs& g, hipStream_t) { return g.WF; }     // product build: the caller owns the fragment-order copy
-#else
-// (diagnostic library only: single-threaded tools; the copy is remade on the caller's stream on every call)
-static const uint16_t* wf_for(const GemmArgs& g, hipStream_t s) {
-  if (g.WF != nullptr) return g.WF;
-  static std::map<std::tuple<const void*, int, int>, uint16_t*> cache;
-  const int Np = gemm_padded_n(g.N);
-  const auto key = std::make_tuple((const void*)g.W, Np, g.Kp);
-  auto it = cache.find(key);
-  if (it != cache.end()) {
-    // the same address can be reused for different contents (test tensors): repack every time in this fallback path
-    launch_pack_wf(g.W, g.ldw, Np, g.Kp, it->second, s);
-    return it->second;
-  }
-  uint16_t* wf = nullptr;
-  if (hipMalloc(&wf, (size_t)Np * 2 * g.Kp * sizeof(uint16_t)) != hipSuccess) return nullptr;
-  launch_pack_wf(g.W, g.ldw, Np, g.Kp, wf, s);
-  cache[key] = wf;
-  return wf;
-}
-#endif
-
-// false = not launched (no fragment-order weight): the caller runs the one-workgroup-per-CU kernel instead
+// false = not launched (no fragment-order weight, GemmArgs::WF): the caller runs the one-workgroup-per-CU kernel instead
 template <int BM, int NW, int WM, int NWS, int BN, class Epi>
-static bool launch_duo_impl(const GemmArgs& g, const Epi& epi, hipStream_t s, int abl) {
-  static const int mode = getenv("RIBCA_DUO_MODE") ? atoi(getenv("RIBCA_DUO_MODE")) : 0;
-  static const int delay_per_step = getenv("RIBCA_DUO_DELAY") ? atoi(getenv("RIBCA_DUO_DELAY")) : 40;   // 10 ns ticks per K step
-  static const int lds_pad = getenv("RIBCA_DUO_SOLO") ? 1 : 0;      // diagnostics: one workgroup per CU (LDS padded past half)
+static bool launch_duo_impl(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   constexpr int TN = BN / (16 * (NW / WM));
   constexpr int NST = BM == 256 ? 2 : 3;
+  if (g.WF == nullptr) return false;
   const int mtiles = (g.M + BM - 1) / BM;
   const int ntiles = gemm_padded_n(g.N) / BN;
-  size_t lds = lds_pad ? (size_t)100 * 1024 : (size_t)NST * BM * ROWB;
+  size_t lds = (size_t)NST * BM * ROWB;
   if constexpr (is_zk<Epi>::value && TN == 3 && WM == 1) {      // an MX3 copy of the new rows: staging image + exchange space (gemm_epi.h mx3_emit_wave48)
     if (epi.zmx.hi != nullptr && lds < (size_t)kMx3StageBytes + 2048) lds = (size_t)kMx3StageBytes + 2048;
   }
-  const uint16_t* wf = wf_for(g, s);
-  if (wf == nullptr) return false;
-  const dim3 grid(mtiles * ntiles), block(64 * NW);
-  const int delay = delay_per_step * (g.Kp / BK);
-  // W panel order (see the kernel's tile map), OFF by default: RIBCA_DUO_PANEL_KB = the most W (KB) a panel may hold, applied only where
-  // the whole weight is larger.  Measured at D = 576 (W = 4.0 / 5.3 MB against the XCD's 4 MB L2; profiles/r3/duo_w_panel_experiment.txt):
-  // 2816 KB halves the counter traffic of those launches (fc1 3.7 -> 2.5 GB, qkv 2.7 -> 1.7 GB; whole pass 21.7 -> 19.4 TB) and costs
-  // 0.4-0.9 % of throughput, more with smaller panels -- the misses it removes are served by the Infinity Cache at no cost in time,
-  // while every panel re-reads the A rows.
-  static const int panel_kb = getenv("RIBCA_DUO_PANEL_KB") ? atoi(getenv("RIBCA_DUO_PANEL_KB")) : 0;
-  int panel = 0;
-  {
-    const size_t tile_bytes = (size_t)BN * g.Kp * 4, w_bytes = tile_bytes * ntiles;
-    if (panel_kb > 0 && w_bytes > (size_t)panel_kb * 1024) {
-      const int fit = (int)((size_t)panel_kb * 1024 / tile_bytes);
-      if (fit >= 1) {
-        const int np = (ntiles + fit - 1) / fit;
-        panel = (ntiles + np - 1) / np;
-      }
-    }
-  }
-  static const int guarded = (getenv("RIBCA_DUO_GUARDED") && atoi(getenv("RIBCA_DUO_GUARDED")) != 0) ? 0x10 : 0;
-  const int mode_p = (mode & 0xef) | guarded | (panel << 8);
-  auto go = [&](auto abl_c) {
-    constexpr int ABL = decltype(abl_c)::value;
-    static unsigned long long attr_done = 0ull;
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_ps_duo_kernel<BM, NW, WM, TN, NWS, Epi, ABL>), (int)(100 * 1024), attr_done)) return;
-    hipLaunchKernelGGL((gemm_ps_duo_kernel<BM, NW, WM, TN, NWS, Epi, ABL>), grid, block, lds, s, g.A, g.lda, wf, g.M, g.Kp, mtiles, ntiles, epi, mode_p, delay);
-  };
-  // the diagnostic forms (no epilogue / stamps) exist for the epilogues tools/bench_gemm.py and tools/stamp_duo.py drive
-#ifdef RIBCA_DIAG
-  constexpr bool diag = std::is_same<Epi, EpiGelu>::value || std::is_same<Epi, EpiResid>::value;
-#else
-  constexpr bool diag = false;
-#endif
-  if constexpr (diag) {
-    switch (abl) {
-      case 1: go(std::integral_constant<int, 1>{}); return true;
-      case 8: go(std::integral_constant<int, 8>{}); return true;
-      case 9: go(std::integral_constant<int, 9>{}); return true;
-      default: break;
-    }
-  }
-  go(std::integral_constant<int, 0>{});
+  static unsigned long long attr_done = 0ull;
+  if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_ps_duo_kernel<BM, NW, WM, TN, NWS, Epi>), (int)(100 * 1024), attr_done)) return true;
+  hipLaunchKernelGGL((gemm_ps_duo_kernel<BM, NW, WM, TN, NWS, Epi>), dim3(mtiles * ntiles), dim3(64 * NW), lds, s, g.A, g.lda, g.WF, g.M, g.Kp, mtiles,
+                     ntiles, epi);
   return true;
 }
 
 template <int BN, class Epi>
-bool launch_duo(const GemmArgs& g, const Epi& epi, hipStream_t s, int abl) {
-  // RIBCA_DUO_FORM (A/B): 0 = 192-row tiles, 3-stage ring, 4 waves as 1 x 4 (2 x 2 for 96-wide tiles), 3 W sets (production);
-  // 1 = the same tile with 8 waves as 2 x 4 (4 x 2), 2 W sets; 2 = 256 rows, 2-stage ring, 4 waves
-  static const int form = getenv("RIBCA_DUO_FORM") ? atoi(getenv("RIBCA_DUO_FORM")) : 0;
-  (void)form;
+bool launch_duo(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   if constexpr (BN == 192) {
     // 128 x 192 tiles, 4 waves as 1 x 4: a wave owns all 128 rows x 48 columns (96 accumulator registers) and every W fragment is
     // requested by ONE wave.  (192 rows x 192 columns needs 144 + 48 + 16 registers beside the addresses: hipcc spills fragment
     // registers inside the K loop, and a spilled register that an inline-asm load is still filling holds garbage.)
-    return launch_duo_impl<128, 4, 1, 3, BN, Epi>(g, epi, s, abl);
+    return launch_duo_impl<128, 4, 1, 3, BN, Epi>(g, epi, s);
   } else if constexpr (BN % 64 == 0) {
-#ifdef RIBCA_DIAG
-    if constexpr (!is_zk<Epi>::value) {      // the A/B tile forms do not exist for the residual-through-the-ring epilogue
-      if (form == 2) return launch_duo_impl<256, 4, 1, 2, BN, Epi>(g, epi, s, abl);
-      if (form == 1) return launch_duo_impl<192, 8, 2, 2, BN, Epi>(g, epi, s, abl);
-    }
-#endif
-    return launch_duo_impl<192, 4, 1, 3, BN, Epi>(g, epi, s, abl);
-  } else {   // BN = 96
-#ifdef RIBCA_DIAG
-    if constexpr (!is_zk<Epi>::value) {
-      if (form == 2) return launch_duo_impl<256, 4, 2, 2, BN, Epi>(g, epi, s, abl);
-      if (form == 1) return launch_duo_impl<192, 8, 4, 2, BN, Epi>(g, epi, s, abl);
-    }
-#endif
-    return launch_duo_impl<192, 4, 2, 3, BN, Epi>(g, epi, s, abl);
+    // 192-row tiles, 3-stage ring, 4 waves as 1 x 4, 3 W register sets
+    return launch_duo_impl<192, 4, 1, 3, BN, Epi>(g, epi, s);
+  } else {   // BN = 96: 4 waves as 2 x 2
+    return launch_duo_impl<192, 4, 2, 3, BN, Epi>(g, epi, s);
   }
 }
 
 // mlp.fc1 (LayerNorm folded) writing its GELU output in the MX3 format of gemm_mx.hip: 192 x 128 tiles, 4 waves as 1 x 4 (one 32-column
-// block per wave and row).  N % 128 == 0 and a fragment-order weight are required.
+// block per wave and row).  N % 128 == 0 and a fragment-order weight are required.  The planes are stored plainly: non-temporal stores,
+// which the MX kernel's fc1 gains 2-5 % from, measured nothing here (fc1 at D = 288, profiles/r4/ab_mx_nt_stores.txt).
 bool launch_gemm_gelu_mx(const GemmArgs& g, const float2* rowstat, const float* csum, const MxAct& out, hipStream_t s) {
   if (g.N % 128 != 0 || g.WF == nullptr || out.Kp != g.N) return false;
-  // RIBCA_MX_NT bit 2 (default off): the MX3 planes of h stored non-temporal from THIS kernel (fc1 at D = 288).  The MX kernel's fc1
-  // (D = 384 / 576, bit 1, gemm_mx.hip) gains 2-5 % from it; here it measured nothing (profiles/r4/ab_mx_nt_stores.txt)
-  static const int mx_nt = getenv("RIBCA_MX_NT") ? atoi(getenv("RIBCA_MX_NT")) : 2;
-  const EpiGeluMx epi{out, g.bias, g.M, g.N, rowstat, csum, 1, (mx_nt >> 2) & 1};
-  return launch_duo_impl<192, 4, 1, 3, 128, EpiGeluMx>(g, epi, s, 0);
+  const EpiGeluMx epi{out, g.bias, g.M, g.N, rowstat, csum, 1, 0};
+  return launch_duo_impl<192, 4, 1, 3, 128, EpiGeluMx>(g, epi, s);
 }
 
-#define RIBCA_DUO_INST(BN, EPI) template bool launch_duo<BN, EPI>(const GemmArgs&, const EPI&, hipStream_t, int);
-RIBCA_DUO_INST(128, EpiGelu) RIBCA_DUO_INST(96, EpiGelu) RIBCA_DUO_INST(64, EpiGelu)
-RIBCA_DUO_INST(128, EpiGeluLn) RIBCA_DUO_INST(96, EpiGeluLn) RIBCA_DUO_INST(64, EpiGeluLn)
-RIBCA_DUO_INST(128, EpiQKVLn) RIBCA_DUO_INST(96, EpiQKVLn) RIBCA_DUO_INST(64, EpiQKVLn)
-RIBCA_DUO_INST(128, EpiResidZK) RIBCA_DUO_INST(96, EpiResidZK) RIBCA_DUO_INST(64, EpiResidZK)
-RIBCA_DUO_INST(192, EpiQKVLn) RIBCA_DUO_INST(192, EpiGeluLn) RIBCA_DUO_INST(192, EpiResidZK)
-#ifdef RIBCA_DIAG
-RIBCA_DUO_INST(128, EpiResid) RIBCA_DUO_INST(96, EpiResid) RIBCA_DUO_INST(64, EpiResid)
-RIBCA_DUO_INST(128, EpiQKV) RIBCA_DUO_INST(96, EpiQKV) RIBCA_DUO_INST(64, EpiQKV)
-RIBCA_DUO_INST(128, EpiRowMap) RIBCA_DUO_INST(96, EpiRowMap) RIBCA_DUO_INST(64, EpiRowMap)
-#endif
-#undef RIBCA_DUO_INST
+#define DUO_INST(BN, EPI) template bool launch_duo<BN, EPI>(const GemmArgs&, const EPI&, hipStream_t);
+DUO_INST(128, EpiGelu) DUO_INST(96, EpiGelu) DUO_INST(64, EpiGelu)
+DUO_INST(128, EpiGeluLn) DUO_INST(96, EpiGeluLn) DUO_INST(64, EpiGeluLn)
+DUO_INST(128, EpiQKVLn) DUO_INST(96, EpiQKVLn) DUO_INST(64, EpiQKVLn)
+DUO_INST(128, EpiResidZK) DUO_INST(96, EpiResidZK) DUO_INST(64, EpiResidZK)
+DUO_INST(192, EpiQKVLn) DUO_INST(192, EpiGeluLn) DUO_INST(192, EpiResidZK)
+#undef DUO_INST
 
 }  // namespace ribca

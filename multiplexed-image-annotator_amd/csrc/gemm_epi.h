@@ -33,7 +33,7 @@ __device__ __forceinline__ void settle_row(NoRow&) {}
 __device__ __forceinline__ void settle_row(LnRow& r) { asm volatile("" : "+v"(r.rstd), "+v"(r.nm)); }
 
 struct EpiResid {
-  float* z; int ldz; const float* bias; int M, N; int nt = 0;
+  float* z; int ldz; const float* bias; int M, N;
   struct Ctx { float4 zv; };
   typedef NoRow RowS;
   __device__ __forceinline__ RowS fetch_row(int) const { return RowS{}; }
@@ -43,7 +43,6 @@ struct EpiResid {
   // loader waves therefore TOUCH it (one dword per 128-byte line, result discarded) right behind the last ring stage they issue,
   // two K steps before the drain reads it.
   static constexpr bool kTouch = true, kFold = false;
-  __device__ __forceinline__ bool touch_on() const { return (nt & 2) == 0; }      // nt bit 1: RIBCA_GEMM_TOUCH=0 (A/B)
   __device__ __forceinline__ const float* touch_ptr(int m, int n) const {      // always a valid address: the touch is issued by every
     return z + (size_t)(m < M ? m : M - 1) * ldz + (n < N ? n : N - 1);         // wave, whatever its rows (the caller counts vmcnt)
   }
@@ -58,9 +57,7 @@ struct EpiResid {
     if (m >= M || n >= N) return;
     f32x4 o;
     o[0] = c.zv.x + (v[0] + b.x); o[1] = c.zv.y + (v[1] + b.y); o[2] = c.zv.z + (v[2] + b.z); o[3] = c.zv.w + (v[3] + b.w);
-    f32x4* dst = reinterpret_cast<f32x4*>(z + (size_t)m * ldz + n);
-    if (nt & 1) __builtin_nontemporal_store(o, dst);
-    else *dst = o;
+    *reinterpret_cast<f32x4*>(z + (size_t)m * ldz + n) = o;
   }
 };
 
@@ -76,12 +73,11 @@ struct EpiResid {
 // Only the LDS-drain form of the kernel supports it (fetch / apply are never called).
 struct EpiResidPS {
   static constexpr bool kTouch = true, kFold = false;
-  uint16_t* z; int ldz; const float* bias; int M, N; int nt = 0;
+  uint16_t* z; int ldz; const float* bias; int M, N;
   float2* part = nullptr;      // [column tiles][M] (mean, M2), or nullptr: no statistics wanted
   const float2* prev = nullptr; int prev_stride = 1;     // (rstd, mean) of the stored rows, or nullptr: no re-centring
   struct Ctx {};
   typedef NoRow RowS;
-  __device__ __forceinline__ bool touch_on() const { return (nt & 2) == 0; }
   __device__ __forceinline__ const float* touch_ptr(int m, int n) const {      // one dword of the 128-byte line holding columns n .. n + 31
     return reinterpret_cast<const float*>(z + (size_t)(m < M ? m : M - 1) * ldz + 2 * (n < N ? n : N - 8));
   }
@@ -115,7 +111,6 @@ struct EpiResidZK {
   // element instead of 4, and fp16 hi * hi + block-scaled corrections instead of three fp16 passes); hi == nullptr: not wanted.  Only with
   // 48-column wave blocks (TN = 3) and N % 192 == 0: a 32-column scale block then lies in one wave or is shared by a wave and its neighbour.
   MxAct zmx = MxAct{nullptr, nullptr, nullptr, 0, 0};
-  int nt = 0;      // A/B switch (RIBCA_MX_NT bit 3): the new rows -- both copies -- stored non-temporal
   struct Ctx {};
   typedef NoRow RowS;
 };
@@ -137,7 +132,7 @@ __device__ __forceinline__ float4 ln_fold4(const f32x4& v, const float4& b, cons
 template <bool FOLD>
 struct EpiGeluT {
   static constexpr bool kTouch = false, kFold = FOLD;
-  uint16_t* out; int ldo; const float* bias; int M, N; int nt = 0;
+  uint16_t* out; int ldo; const float* bias; int M, N;
   const float2* rowstat = nullptr; const float* csum = nullptr;     // FOLD only
   int rs_stride = 1;                                                 // rowstat[m * rs_stride] belongs to GEMM row m
   struct Ctx {};
@@ -161,7 +156,7 @@ struct EpiGeluT {
   }
   // the same epilogue for a tile whose fold (and bias) has already been applied to the accumulators (gemm_split16.hip does it before
   // parking the tile: the drain then needs neither row statistics nor column sums)
-  __device__ __forceinline__ EpiGeluT<false> plain() const { return EpiGeluT<false>{out, ldo, nullptr, M, N, nt}; }
+  __device__ __forceinline__ EpiGeluT<false> plain() const { return EpiGeluT<false>{out, ldo, nullptr, M, N}; }
   __device__ __forceinline__ void fetch(int, int, Ctx&) const {}
   template <int PX = 16, bool IN = false>
   __device__ __forceinline__ void apply(int m, int n, const f32x4& v, const float4& b, const float4& c, const RowS& r, const Ctx&) const {
@@ -169,7 +164,7 @@ struct EpiGeluT {
     const float4 x = ln_fold4<FOLD>(v, b, c, r);
     const f32x2v u0 = gelu_erf2(f32x2v{x.x, x.y}), u1 = gelu_erf2(f32x2v{x.z, x.w});
     float t[4] = {u0.x, u0.y, u1.x, u1.y};
-    ps_store4_pair<PX>(out + (size_t)m * ldo, n, t, nt != 0);      // N % 8 == 0: the partner lane (n ^ 4, same m) passed the same guard
+    ps_store4_pair<PX>(out + (size_t)m * ldo, n, t);      // N % 8 == 0: the partner lane (n ^ 4, same m) passed the same guard
   }
 };
 typedef EpiGeluT<false> EpiGelu;
@@ -192,7 +187,6 @@ struct EpiQKVT {
   }
   uint16_t* q; uint16_t* k; uint16_t* vt; const float* bias; int D, hd, hdp /* stored dims per Q/K row = AttnGeom::hdq */, hdv; float scale; int M, N;
   int T, TP, H, KP;   // tokens per cell, padded token rows of Q/K, heads, padded keys per V^T row
-  int nt = 0;
   unsigned magicT = 0;   // ceil(2^32 / T): m / T as one v_mul_hi + a fix-up (the epilogue does one such division per output row)
   const float2* rowstat = nullptr; const float* csum = nullptr;     // FOLD only
   // vrow != 0: V is stored like K -- row-major packed-split rows [cell][head][TP][2 * hdq] in `vt` -- and the attention kernel
@@ -234,7 +228,7 @@ struct EpiQKVT {
     return (bias != nullptr && (IN || n < N)) ? *reinterpret_cast<const float4*>(bias + n) : float4{0.f, 0.f, 0.f, 0.f};
   }
   __device__ __forceinline__ EpiQKVT<false> plain() const {
-    return EpiQKVT<false>{q, k, vt, nullptr, D, hd, hdp, hdv, scale, M, N, T, TP, H, KP, nt, magicT, nullptr, nullptr, vrow, n_off, cls_rows, 1};
+    return EpiQKVT<false>{q, k, vt, nullptr, D, hd, hdp, hdv, scale, M, N, T, TP, H, KP, magicT, nullptr, nullptr, vrow, n_off, cls_rows, 1};
   }
   __device__ __forceinline__ void fetch(int, int, Ctx&) const {}
   template <int PX = 16, bool IN = false>
@@ -250,7 +244,7 @@ struct EpiQKVT {
         for (int i = 0; i < 4; ++i) x[i] *= scale;
       }
       uint16_t* rowp = (c.which == 0 ? q : c.which == 1 ? k : vt) + (ch * TP + r.t) * (size_t)(2 * hdp);
-      if ((hd & 7) == 0) ps_store4_pair<PX>(rowp, c.d, x, nt != 0);   // the partner lane's 4 columns are in the same head
+      if ((hd & 7) == 0) ps_store4_pair<PX>(rowp, c.d, x);   // the partner lane's 4 columns are in the same head
       else ps_store4(rowp, c.d, x);
     } else {
       uint2 hi, lo;
@@ -389,7 +383,7 @@ struct EpiGeluMx {
   static constexpr bool kTouch = false, kFold = true, kMxOut = true;
   MxAct out; const float* bias; int M, N;
   const float2* rowstat; const float* csum; int rs_stride = 1;
-  int nt = 0;      // 1: the emitted planes are stored non-temporal (A/B switch RIBCA_MX_NT: h is read once, by the next launch)
+  int nt = 0;      // 1: the emitted planes are stored non-temporal (h is read once, by the next launch; the MX kernel's fc1 only)
   struct Ctx {};
   typedef LnRow RowS;
 };
@@ -468,7 +462,7 @@ __device__ __forceinline__ void gelu_mx_epilogue(const EpiGeluMx& epi, int mbase
     if (ok) {
       u32x4* hp = reinterpret_cast<u32x4*>(epi.out.hi + (size_t)m * Kp + hpos);
       u32x2s* lp = reinterpret_cast<u32x2s*>(epi.out.l8 + (size_t)m * Kp + c8);
-      if (epi.nt) {      // h is read once, by the next launch: stores that do not displace the weight from the L2 (RIBCA_MX_NT)
+      if (epi.nt) {      // h is read once, by the next launch: stores that do not displace the weight from the L2
         __builtin_nontemporal_store(u32x4{rx[0], ry[0], rx[1], ry[1]}, hp);
         __builtin_nontemporal_store(u32x2s{rl[0], rl[1]}, lp);
       } else {
@@ -729,9 +723,7 @@ __device__ __forceinline__ void resid_zk_epilogue(const EpiResidZK& epi, int mba
       const u32x4 o = {rx[0], ry[0], rx[1], ry[1]};      // even g: 8 x hi, odd g: 8 x lo
       const int k = nbase + 16 * j;
       if (ok) {
-        u32x4* zp = reinterpret_cast<u32x4*>(zr + ps_off(k & ~7) + ((k & 4) ? 8 : 0));
-        if (epi.nt) __builtin_nontemporal_store(o, zp);
-        else *zp = o;
+        *reinterpret_cast<u32x4*>(zr + ps_off(k & ~7) + ((k & 4) ? 8 : 0)) = o;
       }
     }
     sum[i] = tot.x + tot.y;
@@ -791,23 +783,12 @@ __device__ __forceinline__ void gelu_mx48_epilogue(const EpiGeluMx& epi, int m0,
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const float4 f = ln_fold4<true>(acc[0][i][j], b4[j], c4[j], rs[i]);
-#ifdef MXDBG_NOGELU      // (timing ablation, tools/build_mx_variant.py)
-      const f32x2v u0 = f32x2v{f.x, f.y}, u1 = f32x2v{f.z, f.w};
-#else
       const f32x2v u0 = gelu_erf2(f32x2v{f.x, f.y}), u1 = gelu_erf2(f32x2v{f.z, f.w});
-#endif
       acc[0][i][j] = f32x4{clamp_f16_range(u0.x), clamp_f16_range(u0.y), clamp_f16_range(u1.x), clamp_f16_range(u1.y)};
       // (one tile at a time: interleaving the 24 erf evaluations costs more registers than the wave has beside its accumulators)
       if ((j & 1) == 1 || j == 2) __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef MXDBG_NOEMIT
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) asm volatile("" ::"v"(acc[0][i][j]));
-#else
   mx3_emit_wave48<MT, IN>(epi.out, epi.M, m0, ncol0, g, r16, wave, stg_lds, xch_lds, acc[0], epi.nt != 0);
-#endif
 }
 
 
@@ -819,9 +800,8 @@ template <int CNT> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
 }
 
-// gemm_duo.hip: two 256-thread workgroups per CU, W in fragment order straight to registers (abl: timing ablations, 0 = none)
+// gemm_duo.hip: two 256-thread workgroups per CU, W in fragment order straight to registers
 template <int BN, class Epi>
-bool launch_duo(const GemmArgs& g, const Epi& epi, hipStream_t s, int abl);
-int duo_set_stamp_buffer(void* dev_ptr, unsigned int capacity_blocks);
+bool launch_duo(const GemmArgs& g, const Epi& epi, hipStream_t s);
 
 }  // namespace ribca

@@ -38,17 +38,10 @@
 // Two barriers per 128 k (the fp16x3 kernels: four).  The residual tile rides the ring behind the product's own steps exactly as in
 // gemm_duo.hip (EpiResidZK: identity fragments, exact), and the epilogue is that kernel's.
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 #include "gemm_epi.h"
-
-#ifdef MX_BIG      // (see the kernel section: 256-row tiles, accumulators in AGPRs)
-#define MX_ACC_CONSTRAINT "+a"
-#else
-#define MX_ACC_CONSTRAINT "+v"
-#endif
 
 namespace ribca {
 
@@ -132,7 +125,7 @@ __device__ __forceinline__ void pin_acc(f32x4 (&acc)[1][MT][TN]) {
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j) asm volatile("" : MX_ACC_CONSTRAINT(acc[0][i][j]));
+    for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(acc[0][i][j]));
 }
 
 }  // namespace
@@ -258,28 +251,19 @@ void launch_mx_pack_act(const uint16_t* ps, int ldps, int M, int Kp, const MxAct
 }
 
 // ----------------------------------------------------------------------------------------------------------- kernel
-#ifndef MXDBG_PF
-#define MXDBG_PF 3
-#endif
 namespace {
-// MX_BIG (experiment of round 5, tools/build_ab_lib.py ... -DMX_BIG; NOT the product): 256-row tiles, ONE 4-wave workgroup per CU, a wave owns 256 rows x
-// 48 columns (16 x 3 accumulator tiles in AGPRs) -- every W fragment then serves twice the rows: 0.027 operand bytes per multiply-add instead of
-// 0.038.  No MX3 emission in this form (the staging image is that of a 128-row tile).
-#ifdef MX_BIG
-constexpr int MX_BM = 256, MX_MT = 16;
-#else
-constexpr int MX_BM = 128, MX_MT = 8;
-#endif
-constexpr int MX_BN = 192, MX_TN = 3;
+constexpr int MX_BM = 128, MX_MT = 8, MX_BN = 192, MX_TN = 3;
+// A hi fragments are read this many row tiles ahead of their MFMAs (see the f16 phase)
+constexpr int MX_PF = 3;
 // LDS map: hi as two halves of BM rows x 128 bytes (sub-steps 0-1 | 2-3), the fp6 rows, two scale slots, two lo slots
 constexpr int L_HALF = MX_BM * 128;
 constexpr int L_HI = 0, L_H6A = 2 * L_HALF, L_H6B = L_H6A + MX_BM * 64, L_SC = L_H6B + MX_BM * 32, L_SC_SLOT = MX_BM * 4 + 128, L_L8 = L_SC + 2 * L_SC_SLOT,
               L_XCH = L_L8 + 2 * L_HALF;
-static_assert(MX_BM != 128 || (L_H6A == 32768 && L_H6B == 40960 && L_SC == 45056 && L_SC_SLOT == 640), "the 128-row map is the one the tests pinned");
+static_assert(L_H6A == 32768 && L_H6B == 40960 && L_SC == 45056 && L_SC_SLOT == 640, "the LDS map is the one the tests pinned");
 // (L_XCH: 2 KB outside every ring slot for the MX3-emitting epilogues, gemm_epi.h mx3_emit_wave48; their staging image overlays the ring)
 constexpr int L_TOTAL = L_XCH + 2048;
 static_assert(L_TOTAL <= 160 * 1024, "LDS of a CU");
-static_assert(MX_BM != 128 || kMx3StageBytes <= L_XCH, "the staging image of the MX3 emission must not reach the exchange space");
+static_assert(kMx3StageBytes <= L_XCH, "the staging image of the MX3 emission must not reach the exchange space");
 
 static_assert(L_L8 % 16 == 0, "LDS-DMA destination alignment");
 __device__ __forceinline__ int mx_f4(int row) { return (4 - ((row >> 2) & 3)) & 3; }      // chunk swizzle of the 64-byte hi rows
@@ -289,20 +273,14 @@ __device__ __forceinline__ int mx_f4(int row) { return (4 - ((row >> 2) & 3)) & 
 __device__ __forceinline__ int mx_f8(int row) { return (row >> 1) & 7; }
 }  // namespace
 
-// ABL (diagnostic library only): 1 = no epilogue (results dropped)
 // HALF (round 6; the launcher sets it where N is not a multiple of the 192-column tile: mlp.fc2 at D = 288, whose second column tile holds 96
 // columns): the waves of a tile that lie wholly beyond N -- their accumulators are never stored -- skip their W requests, their fragment
 // reads and their MFMAs, and keep what the workgroup needs from them: their share of the A requests, the hi -> fp6 conversion of their two row
 // tiles, the residual units' requests and every barrier.  A separate instantiation: with HALF = false `dead` is a compile-time false and the
 // code of every other launch is the round-5 kernel's, instruction for instruction.
-template <class Epi, int ABL, bool HALF = false>
-#ifdef MX_BIG
-__global__ __launch_bounds__(256, 1) void gemm_mx_duo_kernel(
-#else
-__global__ __launch_bounds__(256, 2) void gemm_mx_duo_kernel(
-#endif
-MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, int M, int nb,
-                                                              int mtiles, int ntiles, Epi epi, int panel) {
+template <class Epi, bool HALF = false>
+__global__ __launch_bounds__(256, 2) void gemm_mx_duo_kernel(MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, int M, int nb,
+                                                              int mtiles, int ntiles, Epi epi) {
   // epilogues: EpiResidZK (proj / fc2: the residual tile through the ring, optionally a second copy of the new rows in MX3), EpiQKVLn,
   // EpiGeluMx (fc1: GELU output in MX3)
   constexpr bool ZK = is_zk<Epi>::value;
@@ -311,34 +289,10 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
   const int nblk = mtiles * ntiles;
   int bid = blockIdx.x;
   {
-    // blocks b, b + 8, ... run on one XCD (one L2): XCD x walks a contiguous tile range with n fastest (as gemm_duo.hip).  panel > 0
-    // (n-tiles per panel, chosen by the launcher where the weight image is larger than an XCD's L2 can keep beside the A and output
-    // streams): the whole m-tile rows of the range are walked panel by panel -- every m-tile's n-tiles of panel 0, then of panel 1, ... --
-    // so a panel of W stays resident while the A rows stream past it (A is then fetched once per panel); the partial rows at the two
-    // ends of the range keep the plain order.
+    // blocks b, b + 8, ... run on one XCD (one L2): XCD x walks a contiguous tile range with n fastest (as gemm_duo.hip)
     const int xcd = bid & 7, loc = bid >> 3;
     const int q = nblk >> 3, r = nblk & 7;
-    const int first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int cnt = xcd < r ? q + 1 : q;
-    bid = first + loc;
-    if (panel > 0 && panel < ntiles) {
-      const int r0 = (first + ntiles - 1) / ntiles, r1 = (first + cnt) / ntiles;     // whole m-tile rows [r0, r1)
-      const int head = r0 * ntiles - first;
-      if (r1 > r0 && loc >= head) {
-        int l = loc - head;
-        const int rows = r1 - r0;
-        if (l < rows * ntiles) {
-          int p0 = 0, w = panel;
-          while (l >= rows * w) {          // at most ntiles / panel iterations, uniform over the workgroup
-            l -= rows * w;
-            p0 += w;
-            w = ntiles - p0 < panel ? ntiles - p0 : panel;
-          }
-          const int rr = l / w;
-          bid = (r0 + rr) * ntiles + p0 + (l - rr * w);
-        }
-      }
-    }
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
   }
   const int mt = bid / ntiles, nt = bid - mt * ntiles;
   const int m0 = mt * BM, n0 = nt * BN;
@@ -368,9 +322,6 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
     sc_voff = (wave * (BM / 4) + lane) * 4;
   }
   auto issue_hi = [&](int b) {      // the hi columns of step b as two halves of 64 columns (sub-steps 0-1, 2-3): 8 operations per wave
-#ifdef MXDBG_NOA
-    return;
-#endif
     // whole 128-byte lines per row and piece: a sub-step's 64 bytes alone would request every line twice, half at a time
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -380,17 +331,9 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
                                                  hi_voff, i * 32 * Kp * 2 + b * 256 + h * 128, 0, 0);
   };
   auto issue_l8 = [&](int b) {      // lo unit + scale unit of step b: 5 operations per wave
-#ifdef MXDBG_NOA
-    return;
-#endif
     char* st = smem + L_L8 + (b & 1) * L_HALF + wave * 1024;
-#ifdef MXDBG_LO4      // timing variant: half the lo bytes (what an fp4 image of A lo would move)
-#pragma unroll
-    for (int i = 0; i < BM / 64; ++i)
-#else
 #pragma unroll
     for (int i = 0; i < BM / 32; ++i)
-#endif
       __builtin_amdgcn_raw_ptr_buffer_load_lds(l8_rsrc, (__attribute__((address_space(3))) void*)(st + i * 4096), 16, l8_voff, i * 32 * Kp + b * 128, 0, 0);
     // 64 rows per wave from row 32 w: the upper half repeats what the next wave writes (the same bytes) and the last wave's spills into the slot's pad
     __builtin_amdgcn_raw_ptr_buffer_load_lds(sc_rsrc, (__attribute__((address_space(3))) void*)(smem + L_SC + (b & 1) * L_SC_SLOT + wave * BM), 4, sc_voff,
@@ -425,18 +368,12 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
   u32v2 wsc;      // bytes: sl0 sh0' sl1 sh1' | sl2 sh2' - -   (sl: this step's lo image, sh': the NEXT step's hi image)
   u32v2 wsh;      // the hi scale bytes of the current step (taken out of wsc before the next block's words are requested into it)
   auto issue_whi = [&](int t, f16x8 (&dst)[TN]) {      // sub-step t = 4 b + s of the K loop: 3 operations
-#ifdef MXDBG_NOW
-    return;
-#endif
     const unsigned long long p = uniform_ptr(whb + (size_t)t * 3072);
     gld16h<0>(dst[0], wvoff16, p);
     gld16h<1024>(dst[1], wvoff16, p);
     gld16h<2048>(dst[2], wvoff16, p);
   };
   auto issue_wx = [&](int b) {                          // 7 operations
-#ifdef MXDBG_NOW
-    return;
-#endif
     const unsigned long long p = uniform_ptr(wxb + (size_t)b * kMxWxBytes + kWxBase);
     gld8<kWxL6b - kWxBase>(wl6b[0], wvoff8, p); gld8<kWxL6b - kWxBase + 512>(wl6b[1], wvoff8, p); gld8<kWxL6b - kWxBase + 1024>(wl6b[2], wvoff8, p);
     gld16<kWxL6a - kWxBase>(wl6a[0], wvoff16, p); gld16<kWxL6a - kWxBase + 1024>(wl6a[1], wvoff16, p); gld16<kWxL6a - kWxBase + 2048>(wl6a[2], wvoff16, p);
@@ -461,9 +398,7 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
 
   // ---- prologue
   if (!MX_DEAD) {
-#ifndef MXDBG_NOW
     gld8<0>(wsh, wvoff8, uniform_ptr(wxh));
-#endif
     issue_whi(0, whi[0]);
     issue_whi(1, whi[1]);
     issue_whi(2, whi[2]);
@@ -481,13 +416,6 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
   issue_hi(0);
   if (!MX_DEAD) issue_wx(0);
 
-#ifdef MXDBG_STAMP      // timing variant (tools/build_mx_variant.py): shader-clock cycles per phase, summed over the K loop, per wave
-  unsigned long long st_prev = __builtin_amdgcn_s_memtime(), st_b1 = 0, st_f16 = 0, st_cv = 0, st_b2 = 0, st_mx = 0;
-  const unsigned long long st_start = st_prev, rt_start = __builtin_amdgcn_s_memrealtime();      // (100 MHz: the in-kernel clock = d memtime / d memrealtime)
-#define MX_STAMP(acc_) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc_ += t_ - st_prev; st_prev = t_; }
-#else
-#define MX_STAMP(acc_)
-#endif
   // one 128-deep step
   // (the last step is its own instance: "more" is a compile-time constant, so no phase is cut into basic blocks by the requests for the next step)
   auto step = [&](auto more_c, int b) {
@@ -498,7 +426,6 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
     else wait_vmcnt<NWX>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    MX_STAMP(st_b1)
     if (!MX_DEAD) {
     // the fp6 image of this step's W hi, from the four resident fragment sets (they are refilled for the next step right behind their last use,
     // so now is the moment); scale byte = the packer's sh of the tile, which travelled with the PREVIOUS block's words (wsh)
@@ -523,7 +450,7 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
       // A hi fragments PF row tiles ahead of their MFMAs: a row tile is 3 MFMAs = 48 cycles here (the fp16x3 kernels: 9), less than one LDS
       // round trip -- with the next tile's read as the only one in flight every iteration waited for it (timing ablation without any
       // global load: 2.2 x the matrix time)
-      constexpr int PF = MXDBG_PF;
+      constexpr int PF = MX_PF;
       f16x8 ah[PF + 1];
       const unsigned rd_s = (S & 1) ? (rd_hi ^ 64u) : rd_hi;
       constexpr int HOFF = (S >> 1) * L_HALF;
@@ -540,10 +467,8 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
         } else {
           asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ah[cur]) : "n"(MT - 1 - i) : "memory");
         }
-#ifndef MXDBG_NOF16
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[0][i][j] = mfma_f16(whi[S][j], ah[cur], acc[0][i][j]);
-#endif
         __builtin_amdgcn_sched_barrier(0);
       });
       pin_acc(acc);
@@ -555,8 +480,6 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
     // the next step's lo and scale units (their slot was last read in the MX phase of step b - 1, which every wave left before B1)
     if constexpr (more) issue_l8(b + 1);
     __builtin_amdgcn_sched_barrier(0);
-    MX_STAMP(st_f16)
-#ifndef MXDBG_NOCONV
     // ---- conversion: this wave turns the hi rows of row tiles 2 w, 2 w + 1 into fp6 for everybody
     {
       constexpr int CVT = MT / 4;      // row tiles this wave converts
@@ -582,18 +505,15 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
         lds_wr64<U * 512>(cv_b, u32v2{c[4], c[5]});
       });
     }
-#endif
     // B2: fp6 rows visible to every wave, hi slots free.  W's fp6 images of THIS step (requested behind the previous MX phase) must have
     // landed before the MX phase reads them: only the requests made during this step's f16 phase are younger -- 4 x 3 W hi fragments and
     // the 5 pieces of the next lo / scale unit; none in the last step.  (A first version of the four-set W hi schedule had dropped the
     // wait that used to cover them: tests/test_gpu_e2e.py::test_classifier_bitwise_repeatable caught it.)
-    MX_STAMP(st_cv)
     if constexpr (more) wait_vmcnt<4 * TN + 5>();
     else wait_vmcnt<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    MX_STAMP(st_b2)
     if constexpr (more) {
       issue_hi(b + 1);
     } else if constexpr (ZK) {
@@ -605,7 +525,6 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
     __builtin_amdgcn_sched_barrier(0);
     if (!MX_DEAD) {
     // ---- MX phase
-#ifndef MXDBG_NOMX
 #pragma unroll
     for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(wl6a[j]), "+v"(wl6b[j]));
     asm volatile("" : "+v"(wsc));
@@ -621,32 +540,23 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
       u32v4 la[2], lb[2], ha[2];
       u32v2 hb[2];
       unsigned sb[2];
-#ifdef MXDBG_LO4
-#define MX_LB_READ(dst, off, addr) dst = la[0]
-#define MX_LGKM_PER_TILE 4
-#define MX_LO_FMT 2
-#else
-#define MX_LB_READ(dst, off, addr) lds_rd128<off>(dst, addr)
-#define MX_LGKM_PER_TILE 5
-#define MX_LO_FMT 0
-#endif
-      lds_rd128<0>(la[0], m_l8a); MX_LB_READ(lb[0], 0, m_l8b); lds_rd128<0>(ha[0], rd_h6a); lds_rd64<0>(hb[0], rd_h6b); lds_rd8<0>(sb[0], m_sc);
+      lds_rd128<0>(la[0], m_l8a); lds_rd128<0>(lb[0], m_l8b); lds_rd128<0>(ha[0], rd_h6a); lds_rd64<0>(hb[0], rd_h6b); lds_rd8<0>(sb[0], m_sc);
       sfor<MT>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         constexpr int cur = i & 1, nxt = cur ^ 1;
         if constexpr (i + 1 < MT) {
-          lds_rd128<(i + 1) * 2048>(la[nxt], m_l8a); MX_LB_READ(lb[nxt], (i + 1) * 2048, m_l8b);
+          lds_rd128<(i + 1) * 2048>(la[nxt], m_l8a); lds_rd128<(i + 1) * 2048>(lb[nxt], m_l8b);
           lds_rd128<(i + 1) * 1024>(ha[nxt], rd_h6a); lds_rd64<(i + 1) * 512>(hb[nxt], rd_h6b); lds_rd8<(i + 1) * 64>(sb[nxt], m_sc);
-          asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(la[cur]), "+v"(lb[cur]), "+v"(ha[cur]), "+v"(hb[cur]), "+v"(sb[cur]) : "n"(MX_LGKM_PER_TILE) : "memory");
+          asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(la[cur]), "+v"(lb[cur]), "+v"(ha[cur]), "+v"(hb[cur]), "+v"(sb[cur])::"memory");
         } else {
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(la[cur]), "+v"(lb[cur]), "+v"(ha[cur]), "+v"(hb[cur]), "+v"(sb[cur])::"memory");
         }
         const i32x8 al8 = op8(la[cur], lb[cur]), ah6 = op6(ha[cur], hb[cur]);
         const int asc = (int)(sb[cur] | ((sb[cur] + kMxShDelta) << 8));      // byte 0: lo scale, byte 1: fp6-hi scale
         // W hi' (fp6, its sh byte) x A lo (fp8, byte 0);  W lo' (fp6, its sl byte) x A hi' (fp6, byte 1)
-        acc[0][i][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wh6[0], al8, acc[0][i][0], 2, MX_LO_FMT, 1, (int)wsh[0], 0, asc);
-        acc[0][i][1] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wh6[1], al8, acc[0][i][1], 2, MX_LO_FMT, 3, (int)wsh[0], 0, asc);
-        acc[0][i][2] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wh6[2], al8, acc[0][i][2], 2, MX_LO_FMT, 1, (int)wsh[1], 0, asc);
+        acc[0][i][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wh6[0], al8, acc[0][i][0], 2, 0, 1, (int)wsh[0], 0, asc);
+        acc[0][i][1] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wh6[1], al8, acc[0][i][1], 2, 0, 3, (int)wsh[0], 0, asc);
+        acc[0][i][2] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wh6[2], al8, acc[0][i][2], 2, 0, 1, (int)wsh[1], 0, asc);
         acc[0][i][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wl6[0], ah6, acc[0][i][0], 2, 2, 0, (int)wsc[0], 1, asc);
         acc[0][i][1] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wl6[1], ah6, acc[0][i][1], 2, 2, 2, (int)wsc[0], 1, asc);
         acc[0][i][2] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wl6[2], ah6, acc[0][i][2], 2, 2, 0, (int)wsc[1], 1, asc);
@@ -654,23 +564,15 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
       });
     }
     pin_acc(acc);
-#endif
     wsh = wsc;      // the next step's hi scale bytes, before the next block's words are requested into wsc
     asm volatile("" : "+v"(wsh));
     if constexpr (more) issue_wx(b + 1);
     __builtin_amdgcn_sched_barrier(0);
     }
-    MX_STAMP(st_mx)
   };
 
-#ifdef RIBCA_KLOOP_PRIO      // A/B: see gemm_duo.hip
-  __builtin_amdgcn_s_setprio(2);
-#endif
   for (int b = 0; b + 1 < nb; ++b) step(std::true_type{}, b);
   step(std::false_type{}, nb - 1);
-#ifdef RIBCA_KLOOP_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 
   // the lane's position again, from the hardware: r16 / g of the prologue then end with the address registers formed from them instead of
   // occupying registers (or scratch) across the K loop for the epilogue's sake
@@ -694,7 +596,6 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
       const int m = m0 + 16 * i + r16e;
       zpm[i] = (epi.prev != nullptr && m < M) ? epi.prev[(size_t)m * epi.prev_stride].y : 0.f;
     }
-#ifndef MXDBG_NOZ
     // ---- the residual tile: unit t holds columns n0 + 32 t .. + 31 of the stored rows (gemm_duo.hip, EpiResidZK)
     {
       const int last = nb - 1;
@@ -751,57 +652,21 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
         }
       });
     }
-#endif
-#ifdef MXDBG_NOEPI
-    if (true) {
-#else
-    if (ABL & 1) {
-#endif
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[0][i][j]));
-      return;
-    }
     if (n0 + wn * (16 * TN) >= epi.N) return;      // (never with an MX3 copy: its launcher takes whole tiles only)
     const int blk = nt * 4 + wn;
-#ifdef MXDBG_STAMP
-    if (epi.part != nullptr && lane_e == 0) {      // behind the statistics: [N / 48][M] pairs, then 4 pairs per wave of every workgroup
-      float2* o = epi.part + (size_t)(epi.N / 48) * epi.M + ((size_t)blockIdx.x * 4 + wave) * 4;
-      o[0] = float2{(float)st_b1, (float)st_f16};
-      o[1] = float2{(float)st_cv, (float)st_b2};
-      o[2] = float2{(float)st_mx, (float)nb};
-      const unsigned long long st_now = __builtin_amdgcn_s_memtime(), rt_now = __builtin_amdgcn_s_memrealtime();
-      // everything behind the K loop; the shader clock this wave saw from its first instruction to here, in MHz (MI355X_MICROARCH.md, DVFS give-back item 6)
-      o[3] = float2{(float)(st_now - st_prev), rt_now > rt_start ? 100.0f * (float)(st_now - st_start) / (float)(rt_now - rt_start) : 0.f};
-    }
-#endif
     const bool emit = epi.zmx.hi != nullptr;
     if (m0 + BM <= M) {
       resid_zk_epilogue<TN, MT, MT, true>(epi, mbase, nbase, blk, ge, acc, zb4, zpm);
-      if constexpr (MT == 8) { if (emit) mx3_emit_wave48<MT, true>(epi.zmx, M, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc[0], epi.nt != 0); }
+      if (emit) mx3_emit_wave48<MT, true>(epi.zmx, M, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc[0]);
     } else {
       resid_zk_epilogue<TN, MT, MT, false>(epi, mbase, nbase, blk, ge, acc, zb4, zpm);
-      if constexpr (MT == 8) { if (emit) mx3_emit_wave48<MT, false>(epi.zmx, M, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc[0], epi.nt != 0); }
+      if (emit) mx3_emit_wave48<MT, false>(epi.zmx, M, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc[0]);
     }
   } else {
     // N is a multiple of the tile width for these (gemm_mx_supported + the launchers): only the rows need guards
-#ifdef MXDBG_NOEPI
-    if (true) {
-#else
-    if (ABL & 1) {
-#endif
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[0][i][j]));
-      return;
-    }
     if constexpr (is_mx_out<Epi>::value) {
-      if constexpr (MT == 8) {
-        if (m0 + BM <= M) gelu_mx48_epilogue<MT, true>(epi, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc);
-        else gelu_mx48_epilogue<MT, false>(epi, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc);
-      }
+      if (m0 + BM <= M) gelu_mx48_epilogue<MT, true>(epi, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc);
+      else gelu_mx48_epilogue<MT, false>(epi, m0, n0 + wn * (16 * TN), ge, r16e, wave, lds_base, xch, acc);
     } else {
       if (m0 + BM <= M) run_epilogue<TN, Epi, MT, true>(epi, mbase, nbase, acc[0]);
       else run_epilogue<TN, Epi, MT>(epi, mbase, nbase, acc[0]);
@@ -812,49 +677,28 @@ MxAct A, const uint16_t* __restrict__ WH, const unsigned char* __restrict__ WX, 
 // ----------------------------------------------------------------------------------------------------------- host side
 bool gemm_mx_supported(int N, int Kp) { return N % 48 == 0 && N % 8 == 0 && Kp % 128 == 0 && Kp >= 128; }
 
-template <class Epi, int ABL, bool HALF = false>
+template <class Epi, bool HALF = false>
 static void launch_mx_impl(const MxAct& A, const MxWeight& W, int M, int N, const Epi& epi, hipStream_t s) {
   const int mtiles = (M + MX_BM - 1) / MX_BM, ntiles = (N + MX_BN - 1) / MX_BN;
   const int nb = A.Kp / 128;
-  void (*kernel)(MxAct, const uint16_t*, const unsigned char*, int, int, int, int, Epi, int) = gemm_mx_duo_kernel<Epi, ABL, HALF>;
+  void (*kernel)(MxAct, const uint16_t*, const unsigned char*, int, int, int, int, Epi) = gemm_mx_duo_kernel<Epi, HALF>;
   static unsigned long long attr_done = 0ull;
   if (!ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), L_TOTAL, attr_done)) return;
-  // W-panel walk (see the kernel's tile map): RIBCA_MX_PANEL_KB = the most weight image (KB) a panel may hold, applied only where the
-  // whole image is larger (qkv / fc1 at D = 576: 3.1 / 4.2 MB against the XCD's 4 MB L2); 0 = off
-  static const int panel_kb = getenv("RIBCA_MX_PANEL_KB") ? atoi(getenv("RIBCA_MX_PANEL_KB")) : 0;
-  int panel = 0;
-  {
-    const size_t tile_bytes = (size_t)4 * nb * (kMxWhBytes + kMxWxBytes), w_bytes = tile_bytes * ntiles;
-    if (panel_kb > 0 && w_bytes > (size_t)panel_kb * 1024) {
-      const int fit = (int)((size_t)panel_kb * 1024 / tile_bytes);
-      if (fit >= 1) {
-        const int np = (ntiles + fit - 1) / fit;
-        panel = (ntiles + np - 1) / np;
-      }
-    }
-  }
-  kernel<<<dim3(mtiles * ntiles), dim3(256), L_TOTAL, s>>>(A, W.wh, W.wx, M, nb, mtiles, ntiles, epi, panel);
+  kernel<<<dim3(mtiles * ntiles), dim3(256), L_TOTAL, s>>>(A, W.wh, W.wx, M, nb, mtiles, ntiles, epi);
 }
 
 // z (packed-split) = (z - prev mean) + A W^T + bias with A in MX3, W in the mx_pack_w image; statistics per 48-column wave block
 ResidStatGeom launch_gemm_mx_resid(const MxAct& A, const MxWeight& W, int M, int N, const float* bias, uint16_t* z, int ldz, float2* part, const float2* prev,
-                                   int prev_stride, hipStream_t s, int abl, const MxAct* zmx) {
+                                   int prev_stride, hipStream_t s, const MxAct* zmx) {
   EpiResidZK epi{z, ldz, bias, M, N, part, prev, prev_stride};
-  static const int mx_nt = getenv("RIBCA_MX_NT") ? atoi(getenv("RIBCA_MX_NT")) : 2;
-  epi.nt = (mx_nt >> 3) & 1;
   if (zmx != nullptr) {
     // (whole 192-column tiles: every wave of a workgroup then reaches the barrier of the emission)
     if (N % MX_BN != 0) { launch_error("launch_gemm_mx_resid: an MX3 copy of the residual rows needs N %% 192 == 0 (N = %d)", N); return ResidStatGeom{N / 48, 48}; }
     epi.zmx = *zmx;
   }
-#ifdef RIBCA_DIAG
-  if (abl == 1) { launch_mx_impl<EpiResidZK, 1>(A, W, M, N, epi, s); return ResidStatGeom{N / 48, 48}; }
-#endif
-  (void)abl;
-  // RIBCA_MX_HALF=0: the whole-tile kernel for the ragged last column tile as well (A/B; the results are the same bits either way)
-  static const bool half_on = !(getenv("RIBCA_MX_HALF") && atoi(getenv("RIBCA_MX_HALF")) == 0);
-  if (N % MX_BN != 0 && half_on) launch_mx_impl<EpiResidZK, 0, true>(A, W, M, N, epi, s);
-  else launch_mx_impl<EpiResidZK, 0>(A, W, M, N, epi, s);
+  // a ragged last column tile: the instantiation whose waves beyond N skip their work (the same bits as the whole-tile kernel)
+  if (N % MX_BN != 0) launch_mx_impl<EpiResidZK, true>(A, W, M, N, epi, s);
+  else launch_mx_impl<EpiResidZK>(A, W, M, N, epi, s);
   return ResidStatGeom{N / 48, 48};
 }
 
@@ -862,22 +706,18 @@ ResidStatGeom launch_gemm_mx_resid(const MxAct& A, const MxWeight& W, int M, int
 void launch_gemm_mx_qkv_ln(const MxAct& A, const MxWeight& W, int M, int N, const float* bias, const float2* rowstat, const float* csum, uint16_t* q,
                            uint16_t* k, uint16_t* vt, const AttnGeom& a, float scale, hipStream_t s) {
   if (N % MX_BN != 0) { launch_error("launch_gemm_mx_qkv_ln needs N %% 192 == 0 (N = %d)", N); return; }
-  // RIBCA_MX_NT: bit 0 = the q / k / v rows stored non-temporal (A/B: no effect measured), bit 1 = the MX3 planes of h (default on, below)
-  static const int mx_nt = getenv("RIBCA_MX_NT") ? atoi(getenv("RIBCA_MX_NT")) : 2;
-  const EpiQKVLn epi{q, k, vt, bias, a.D, a.hd, a.hdq, a.hdv, scale, M, N, a.T, a.TP, a.H, a.KP, mx_nt & 1,
+  const EpiQKVLn epi{q, k, vt, bias, a.D, a.hd, a.hdq, a.hdv, scale, M, N, a.T, a.TP, a.H, a.KP,
                      (unsigned)((0x100000000ull + (unsigned long long)a.T - 1) / (unsigned long long)a.T), rowstat, csum, attention_v_rowmajor(a) ? 1 : 0,
                      0, 0, 1};
-  launch_mx_impl<EpiQKVLn, 0>(A, W, M, N, epi, s);
+  launch_mx_impl<EpiQKVLn>(A, W, M, N, epi, s);
 }
 void launch_gemm_mx_gelu(const MxAct& A, const MxWeight& W, int M, int N, const float* bias, const float2* rowstat, const float* csum, const MxAct& out,
                          hipStream_t s) {
   if (N % MX_BN != 0 || out.Kp != N) { launch_error("launch_gemm_mx_gelu needs N %% 192 == 0 and out.Kp == N (N = %d, out.Kp = %d)", N, out.Kp); return; }
   // The emitted planes of h (715 MB per launch at D = 576) are read once, by the next launch: stored non-temporal they do not displace
   // the weight image from the XCD's L2 -- fetch 1689 -> 1125 MB per launch, fc1 -2 %, fc2 -1 % (profiles/r4/ab_mx_nt_stores.txt).
-  // RIBCA_MX_NT bit 1 = 0 for A/B.
-  static const int mx_nt = getenv("RIBCA_MX_NT") ? atoi(getenv("RIBCA_MX_NT")) : 2;
-  const EpiGeluMx epi{out, bias, M, N, rowstat, csum, 1, (mx_nt >> 1) & 1};
-  launch_mx_impl<EpiGeluMx, 0>(A, W, M, N, epi, s);
+  const EpiGeluMx epi{out, bias, M, N, rowstat, csum, 1, 1};
+  launch_mx_impl<EpiGeluMx>(A, W, M, N, epi, s);
 }
 
 }  // namespace ribca

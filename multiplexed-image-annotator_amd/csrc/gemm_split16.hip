@@ -30,9 +30,8 @@
 //   chunks -- whole 256-512 byte row segments per instruction (what a CU can drain depends on the address shape of a store,
 //   tools/store_bench.hip).  It is not overlapped with the next tile's K loop; DESIGN.md section 6 lists the persistent /
 //   streaming / relay forms that were built for that and why they did not pay (output traffic, not the latency chain).
-//   gemm_duo.hip is the two-workgroups-per-CU form of this kernel (weights out of LDS, in fragment order): bit-identical, reached
-//   through variants 40-49 / RIBCA_GEMM_DUO=1, not faster end to end.
-#include <cstdlib>
+//   gemm_duo.hip is the two-workgroups-per-CU form of this kernel (weights out of LDS, in fragment order): bit-identical; the
+//   launchers below send it the shapes where it measured faster.
 #include <type_traits>
 
 #include "gemm_epi.h"
@@ -40,14 +39,6 @@
 #include "ribca_kernels.h"
 
 namespace ribca {
-
-// Diagnostic stamps (measurement builds only: variant 12): wave 0 of every workgroup writes s_memrealtime (100 MHz) at kernel
-// entry, after the first stage has landed, after the K loop and after its epilogue, plus the XCC/CU it ran on, into a
-// buffer nothing else reads.
-__device__ unsigned long long* g_stamps = nullptr;
-__device__ unsigned int g_stamp_cap = 0;      // workgroups the buffer has room for: larger grids do not stamp
-constexpr int kStampStride = 20;   // per workgroup: t0..t3, xcc, hw id, then the epilogue end of each of the 12 waves
-__device__ __forceinline__ unsigned long long stamp_now() { return __builtin_amdgcn_s_memrealtime(); }
 
 // ---------------------------------------------------------------------------------------------- epilogue through LDS
 // tools/store_bench.hip: what one CU can push to memory depends on the ADDRESS SHAPE of each store instruction, not on its
@@ -102,7 +93,7 @@ __device__ __forceinline__ void lds_drain(const Epi& epi, const char* smem, int 
   // ALL of this thread's chunks leave LDS before the first store is issued.  The kernel contains LDS-DMA, so hipcc guards every
   // use of a ds_read result with s_waitcnt vmcnt(0) (an LDS-DMA could be pending for all it knows) -- interleaved with the stores
   // (read, compute, store, read, ...) that wait also drained the PREVIOUS iteration's global store, i.e. one HBM write round
-  // trip per iteration, 8-11 times per tile: most of the 6-9 us the epilogue took (tools/epilogue_scaling.py).  With the reads
+  // trip per iteration, 8-11 times per tile: most of the 6-9 us the epilogue took.  With the reads
   // hoisted the single wait sits before any store and the stores stream out back to back.
   const char* src = smem + row0 * SROW + c * 16;
   f32x4 vals[NIT];
@@ -285,16 +276,11 @@ __device__ __forceinline__ void fold_accumulators(f32x4 (&acc)[4][TN], const cha
 // direct-to-LDS loads.  An LDS-DMA instruction costs its wave ~100 issue cycles, and 6 of them per wave right after each
 // barrier (every wave at once, both SIMD partners) left the matrix pipe idle for a third of each K step; on dedicated waves
 // that cost overlaps the consumers' MFMAs (3 waves per SIMD: 2 consumers + 1 loader).  Consumers never touch vmcnt in the
-// loop, so their epilogue loads/stores cannot drain the ring.
-// timing ablations (measurement builds only; results are wrong on purpose): 1 = no loads, 2 = no MFMA/LDS reads, 3 = no epilogue,
-// 4 = stamps, 5 = no loads and no epilogue, 6 / 7 = two / one MFMA per operand pair, 8 / 9 = the same without the epilogue
-constexpr bool abl_no_loads(int a) { return a == 1 || a == 5; }
-constexpr bool abl_no_epi(int a) { return a == 3 || a == 5 || a == 8 || a == 9; }
-constexpr int abl_passes(int a) { return (a == 6 || a == 8) ? 2 : (a == 7 || a == 9) ? 1 : 3; }
-template <int BN, class Epi, int ABL = 0,
-          bool STAG = false, bool LEPI = false /* epilogue through LDS: row-contiguous stores by all 12 waves */>
+// loop, so their epilogue loads/stores cannot drain the ring.  The finished tile leaves through LDS (row-contiguous stores by all 12
+// waves), except the V tiles of the qkv product's V^T form, which keep the register path (lepi_tile_uses_registers).
+template <int BN, class Epi>
 __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __restrict__ A, int lda, const uint16_t* __restrict__ W, int ldw,
-                                                            int M, int Kp, int mtiles, int ntiles, Epi epi, int deph) {
+                                                            int M, int Kp, int mtiles, int ntiles, Epi epi) {
   constexpr int BM = 256, NST = 3, NLW = 4;
   constexpr int TN = BN / 32;
   constexpr int ROWS = BM + BN;
@@ -316,15 +302,6 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nk = Kp / BK;
-
-  // De-phasing: the first workgroup on every CU starts 0..31/32 of a tile time late (spread within each XCD), so that the
-  // CUs' epilogue bursts interleave instead of all hitting the memory system together (chip-wide write limit ~5 TB/s = ~20
-  // GB/s per CU when all 256 store at once, against ~67 GB/s that one CU can sustain with row-contiguous stores).  Later
-  // workgroups inherit the phase of the CU they land on.  Consumers wait; loaders prefetch and meet them at the barrier.
-  if (deph > 0 && blockIdx.x < 256 && wave < 8) {
-    const unsigned long long until = __builtin_amdgcn_s_memrealtime() + (unsigned long long)(((blockIdx.x >> 3) & 31) * deph) / 32;
-    while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(8);
-  }
 
   if (wave >= 8) {
     // ------------------------------------------------------------------ loader
@@ -358,17 +335,14 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
     // BN / 32 lines, issued right BEHIND the last ring stage: vmcnt retires in order, so the two remaining stage waits simply
     // leave these NT youngest operations in flight.  The results are never used; the destination registers are kept allocated
     // until the drain's own waits have passed (empty asm at the end of this branch).
-    constexpr int NT = (Epi::kTouch && LEPI && STAG && (ABL == 0 || ABL == 4)) ? BN / 32 : 0;
+    constexpr int NT = Epi::kTouch ? BN / 32 : 0;
     unsigned int touched[NT > 0 ? NT : 1];
     auto touch = [&]() {
       if constexpr (NT > 0) {
         const int trow = lw * 64 + lane;
 #pragma unroll
-        for (int i = 0; i < NT; ++i) {
-          // (switched off for A/B, the same instruction reads the start of z: an L2 hit that keeps the vmcnt arithmetic unchanged)
-          const float* p = epi.touch_on() ? epi.touch_ptr(m0 + trow, n0 + 32 * i) : epi.touch_ptr(0, 0);
-          asm volatile("global_load_dword %0, %1, off" : "=v"(touched[i]) : "v"(p) : "memory");
-        }
+        for (int i = 0; i < NT; ++i)
+          asm volatile("global_load_dword %0, %1, off" : "=v"(touched[i]) : "v"(epi.touch_ptr(m0 + trow, n0 + 32 * i)) : "memory");
       }
     };
     // folded LayerNorm: this lane's row statistics and (loader waves 0 / 1) a chunk of the column sums / folded bias, requested
@@ -403,10 +377,8 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(fold_cb) : "v"(cp) : "memory");
       }
     }
-    if (!abl_no_loads(ABL)) {
-      issue(0, 0);
-      if (nk > 1) issue(1, 1);
-    }
+    issue(0, 0);
+    if (nk > 1) issue(1, 1);
     if (nk <= 2) touch();
     int cur = 0;
     for (int kk = 0; kk < nk; ++kk) {
@@ -445,25 +417,19 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
       }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (!abl_no_loads(ABL) && kk + 2 < nk) {
+      if (kk + 2 < nk) {
         int nxt = cur + 2;
         nxt = nxt >= NST ? nxt - NST : nxt;
         issue(kk + 2, nxt);
         if (kk + 3 == nk) touch();              // that was the last stage
       }
-      if (STAG) __builtin_amdgcn_s_barrier();   // phase 2kk+1
+      __builtin_amdgcn_s_barrier();             // phase 2kk+1
       cur = cur + 1 == NST ? 0 : cur + 1;
     }
-    if (STAG) __builtin_amdgcn_s_barrier();     // phase 2nk
-    if constexpr (LEPI && STAG && !abl_no_epi(ABL)) {
-      if (!lepi_tile_uses_registers(lepi_plain(epi), n0, BN)) {
-        __syncthreads();                          // consumers have parked the tile
-        lds_drain_any<BN>(epi, smem, m0, n0, nt, tid);
-      }
-    }
-    if (ABL == 4 && g_stamps != nullptr && blockIdx.x < g_stamp_cap && lane == 0) {      // per-wave end of the epilogue (stores accepted)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      g_stamps[(size_t)blockIdx.x * kStampStride + 6 + wave] = stamp_now();
+    __builtin_amdgcn_s_barrier();               // phase 2nk
+    if (!lepi_tile_uses_registers(lepi_plain(epi), n0, BN)) {
+      __syncthreads();                            // consumers have parked the tile
+      lds_drain_any<BN>(epi, smem, m0, n0, nt, tid);
     }
     if constexpr (NT > 0) {
 #pragma unroll
@@ -473,8 +439,6 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
   }
 
   // -------------------------------------------------------------------- consumer
-  unsigned long long t0 = 0, t1 = 0, t2 = 0, tc1 = 0, tc2 = 0;
-  if (ABL == 4) t0 = stamp_now();
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, g = lane >> 4;
   int a_rd[4], w_rd[TN];
@@ -502,67 +466,40 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
     }
   };
   auto mfmas = [&]() {
-    if constexpr (abl_passes(ABL) >= 3) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(wlo[j], ahi[i], acc[i][j]);
-    }
-    if constexpr (abl_passes(ABL) >= 2) {
+      for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(wlo[j], ahi[i], acc[i][j]);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(whi[j], alo[i], acc[i][j]);
-    }
+      for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(whi[j], alo[i], acc[i][j]);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(whi[j], ahi[i], acc[i][j]);
   };
 
+  // Two barriers per K step split it into a fragment-read phase and an MFMA phase; waves 4-7 (the SIMD partners of
+  // waves 0-3) run half a step late, so on every SIMD one wave's LDS burst overlaps the other wave's 48 MFMAs.
+  //   phase 2s   : waves 0-3 read(s)   | waves 4-7 mfma(s-1)
+  //   phase 2s+1 : waves 0-3 mfma(s)   | waves 4-7 read(s)
   int cur = 0;
-  if (!STAG) {
-    for (int kk = 0; kk < nk; ++kk) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (ABL != 2) {
-        read_frags(smem + cur * STAGE);
-        mfmas();
-      }
-      cur = cur + 1 == NST ? 0 : cur + 1;
-    }
-  } else {
-    // Two barriers per K step split it into a fragment-read phase and an MFMA phase; waves 4-7 (the SIMD partners of
-    // waves 0-3) run half a step late, so on every SIMD one wave's LDS burst overlaps the other wave's 48 MFMAs.
-    //   phase 2s   : waves 0-3 read(s)   | waves 4-7 mfma(s-1)
-    //   phase 2s+1 : waves 0-3 mfma(s)   | waves 4-7 read(s)
-    const bool late = wave >= 4;
-    if (late) __builtin_amdgcn_s_barrier();          // phase 0: nothing to multiply yet
-    for (int kk = 0; kk < nk; ++kk) {
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (ABL == 4 && kk == 0) { t1 = stamp_now(); tc1 = __builtin_amdgcn_s_memtime(); }
-      if (ABL != 2) read_frags(smem + cur * STAGE);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (ABL != 2) mfmas();
-      cur = cur + 1 == NST ? 0 : cur + 1;
-    }
-    if (!late) __builtin_amdgcn_s_barrier();         // phase 2nk: partners finish their last MFMAs
+  const bool late = wave >= 4;
+  if (late) __builtin_amdgcn_s_barrier();          // phase 0: nothing to multiply yet
+  for (int kk = 0; kk < nk; ++kk) {
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    read_frags(smem + cur * STAGE);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    mfmas();
+    cur = cur + 1 == NST ? 0 : cur + 1;
   }
-  if (ABL == 4) { t2 = stamp_now(); tc2 = __builtin_amdgcn_s_memtime(); }
-  if (abl_no_epi(ABL)) {   // timing ablation: no epilogue (accumulators kept alive so the MFMAs are not dead code)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
+  if (!late) __builtin_amdgcn_s_barrier();         // phase 2nk: partners finish their last MFMAs
   if constexpr (Epi::kFold) {
-    static_assert(LEPI && STAG, "the folded epilogues exist in the production form only");
     fold_accumulators<BN, TN>(acc, smem + NST * STAGE, wm, wn, r16, g);
     const auto pe = epi.plain();
     if (lepi_tile_uses_registers(pe, n0, BN)) run_epilogue<TN>(pe, m0 + wm * 64 + r16, n0 + wn * (BN / 2) + 4 * g, acc);
@@ -571,7 +508,7 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
       __syncthreads();
       lds_drain<BN>(pe, smem, m0, n0, tid);
     }
-  } else if constexpr (LEPI && STAG) {
+  } else {
     if constexpr (std::is_same<Epi, EpiResidPS>::value) {      // acc += bias (staged behind the ring by the loaders): one add the drain need not do
       const char* xs = smem + NST * STAGE;
 #pragma unroll
@@ -587,187 +524,8 @@ __global__ __launch_bounds__(768) void gemm_ps_split_kernel(const uint16_t* __re
       __syncthreads();
       lds_drain_any<BN>(epi, smem, m0, n0, nt, tid);
     }
-  } else {
-    run_epilogue<TN>(epi, m0 + wm * 64 + r16, n0 + wn * (BN / 2) + 4 * g, acc);
-  }
-  if (ABL == 4 && g_stamps != nullptr && blockIdx.x < g_stamp_cap && lane == 0 && tid != 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    g_stamps[(size_t)blockIdx.x * kStampStride + 6 + wave] = stamp_now();
-  }
-  if (ABL == 4 && g_stamps != nullptr && blockIdx.x < g_stamp_cap && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // epilogue stores of this wave have been accepted
-    const unsigned long long t3 = stamp_now();
-    unsigned long long* o = g_stamps + (size_t)blockIdx.x * kStampStride;
-    o[6] = t3;
-    o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3; o[18] = tc1; o[19] = tc2;
-    unsigned int xcc, hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    o[4] = xcc; o[5] = hwid;
   }
 }
-
-#ifdef RIBCA_DIAG
-// ---------------------------------------------------------------------------------------------- persistent form
-// Same tile, ring, roles and stagger as gemm_ps_split_kernel, but ONE workgroup per CU walks a sequence of tiles (tile ids
-// blockIdx.x, blockIdx.x + gridDim.x, ...; the XCD-aware id -> (m, n) map is unchanged, so a workgroup's tiles stay on its XCD and
-// mostly share their A tile) and the K steps of consecutive tiles form one continuous stream through the ring: while the
-// consumers write tile t out of their accumulator registers, the loader waves have already issued the first two K steps of
-// tile t + 1, so the 2 us "first stage in flight" prologue and the 0.5-3 us workgroup-launch gap that every tile of the
-// one-tile-per-workgroup kernel pays (tools/stamp_gemm.py) are hidden behind the epilogue.  The epilogue cannot park the tile
-// in the ring (it is live), so it is the register form: each lane writes its 4 x TN accumulator tiles directly.
-// Barrier accounting (raw s_barrier counts arrivals of all 12 waves): every wave executes 2 barriers per K step of every tile
-// of this workgroup, plus one: late consumers (waves 4-7) take theirs before the first step, everyone else after the last.
-template <int BN, class Epi>
-__global__ __launch_bounds__(768) void gemm_ps_persist_kernel(const uint16_t* __restrict__ A, int lda, const uint16_t* __restrict__ W, int ldw,
-                                                              int M, int Kp, int mtiles, int ntiles, Epi epi) {
-  constexpr int BM = 256, NST = 3, NLW = 4;
-  constexpr int TN = BN / 32;
-  constexpr int ROWS = BM + BN;
-  constexpr int STAGE = ROWS * ROWB;
-  constexpr int NGRP = ROWS / 8;
-  constexpr int GPL = (NGRP + NLW - 1) / NLW;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nblk = mtiles * ntiles;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nk = Kp / BK;
-  const int my_tiles = (int)blockIdx.x < nblk ? (nblk - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
-  auto tile_origin = [&](int seq, int& m0, int& n0) {      // seq-th tile of this workgroup
-    int bid = (int)blockIdx.x + seq * (int)gridDim.x;
-    const int xcd = bid & 7, loc = bid >> 3;
-    const int q = nblk >> 3, r = nblk & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    const int mt = bid / ntiles, nt = bid - mt * ntiles;
-    m0 = mt * BM; n0 = nt * BN;
-  };
-
-  if (wave >= 8) {
-    // ------------------------------------------------------------------ loader: issue iterator runs two K steps ahead
-    const int lw = wave - 8;
-    const uint16_t* src[GPL];
-    int dst[GPL];
-    auto set_tile = [&](int seq) {
-      int m0, n0;
-      tile_origin(seq, m0, n0);
-#pragma unroll
-      for (int i = 0; i < GPL; ++i) {
-        int grp = lw + NLW * i;
-        grp = grp < NGRP ? grp : NGRP - 1;
-        const int row = grp * 8 + (lane >> 3);
-        const int ch = (lane & 7) ^ swz_f(row);
-        if (row < BM) {
-          int gm = m0 + row;
-          gm = gm < M ? gm : M - 1;
-          src[i] = A + (size_t)gm * lda + ch * 8;
-        } else {
-          src[i] = W + (size_t)(n0 + row - BM) * ldw + ch * 8;
-        }
-        dst[i] = grp * 1024;
-      }
-    };
-    int iss_seq = 0, iss_kk = 0, iss_stage = 0;            // next (tile, K step) to issue and the ring slot it goes to
-    const long long total = (long long)my_tiles * nk;
-    long long issued = 0;
-    auto issue_next = [&]() {
-      if (issued >= total) return;
-      if (iss_kk == 0) set_tile(iss_seq);
-      char* st = smem + iss_stage * STAGE;
-      const int ko = iss_kk * (2 * BK);
-#pragma unroll
-      for (int i = 0; i < GPL; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + ko),
-                                         (__attribute__((address_space(3))) void*)(st + dst[i]), 16, 0, 0);
-      ++issued;
-      iss_stage = iss_stage + 1 == NST ? 0 : iss_stage + 1;
-      if (++iss_kk == nk) { iss_kk = 0; ++iss_seq; }
-    };
-    issue_next();
-    issue_next();
-    for (long long g = 0; g < total; ++g) {
-      if (issued > g + 1) wait_vmcnt<GPL>();               // one younger stage may stay in flight
-      else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();                        // opens step g: slot (g + 2) % 3 was read in step g - 1 and is free
-      asm volatile("" ::: "memory");
-      issue_next();
-      __builtin_amdgcn_s_barrier();                        // phase 2g + 1
-    }
-    __builtin_amdgcn_s_barrier();                          // the "+ 1"
-    return;
-  }
-
-  // -------------------------------------------------------------------- consumer
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r16 = lane & 15, g = lane >> 4;
-  int a_rd[4], w_rd[TN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) a_rd[i] = lds_off(wm * 64 + i * 16 + r16, 2 * g);
-#pragma unroll
-  for (int i = 0; i < TN; ++i) w_rd[i] = BM * ROWB + lds_off(wn * (BN / 2) + i * 16 + r16, 2 * g);
-  // Barrier schedule (B0, B1, ... counted over the whole workgroup; step g of the continuous K-step stream):
-  //   loaders      : B(2g)  issue(g + 2)  B(2g+1)                                   ... final B(2 total)
-  //   waves 0-3    : B0 | read(g)  B(2g+1)  mfma(g)  B(2g+2)                         -> epilogue AFTER the barrier that ends the tile
-  //   waves 4-7    : B0 | B(2g+1)  read(g)  B(2g+2)  mfma(g)                         -> epilogue after the tile's last mfma
-  // so an early wave has already released its partner's last MFMA phase when it starts writing its tile out, exactly as in
-  // the one-tile kernel, and every wave executes 2 total + 1 barriers.
-  const bool late = wave >= 4;
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  __builtin_amdgcn_s_barrier();                              // B0
-  int cur = 0;
-  for (int seq = 0; seq < my_tiles; ++seq) {
-    f32x4 acc[4][TN];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kk = 0; kk < nk; ++kk) {
-      f16x8 ahi[4], alo[4], whi[TN], wlo[TN];
-      if (late) __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      // Fragment reads as inline asm: for a plain LDS load hipcc would put s_waitcnt vmcnt(0) in front of the first MFMA of every
-      // tile (the kernel contains LDS-DMA), i.e. wait for the previous tile's epilogue stores -- the very overlap this form exists for.
-      const unsigned st = lds_base + (unsigned)(cur * STAGE);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        asm volatile("ds_read_b128 %0, %1" : "=v"(ahi[i]) : "v"(st + (unsigned)a_rd[i]) : "memory");
-        asm volatile("ds_read_b128 %0, %1" : "=v"(alo[i]) : "v"(st + (unsigned)(a_rd[i] ^ 16)) : "memory");
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        asm volatile("ds_read_b128 %0, %1" : "=v"(whi[j]) : "v"(st + (unsigned)w_rd[j]) : "memory");
-        asm volatile("ds_read_b128 %0, %1" : "=v"(wlo[j]) : "v"(st + (unsigned)(w_rd[j] ^ 16)) : "memory");
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(wlo[j], ahi[i], acc[i][j]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(whi[j], alo[i], acc[i][j]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_f16(whi[j], ahi[i], acc[i][j]);
-      if (!late) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-      cur = cur + 1 == NST ? 0 : cur + 1;
-    }
-    int m0, n0;
-    tile_origin(seq, m0, n0);
-    run_epilogue<TN>(epi, m0 + wm * 64 + r16, n0 + wn * (BN / 2) + 4 * g, acc);
-  }
-}
-
-#endif  // RIBCA_DIAG
 
 // ---------------------------------------------------------------------------------------------- host side
 int gemm_pick_bn(int N) {
@@ -781,128 +539,38 @@ int gemm_padded_n(int N) {
   return (N + bn - 1) / bn * bn;
 }
 
-static int g_variant = 0;   // 0 = production kernel; 3/4/5/7/9 = A/B and timing-ablation forms (tools/bench_gemm.py)
-void gemm_set_variant(int v) { g_variant = v; }
-int gemm_set_stamp_buffer(void* dev_ptr, long long capacity_blocks) {
-  const unsigned int cap = dev_ptr == nullptr || capacity_blocks <= 0 ? 0u : (unsigned int)(capacity_blocks > 0xffffffffll ? 0xffffffffll : capacity_blocks);
-  if (duo_set_stamp_buffer(dev_ptr, cap) != 0) return 1;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_cap), &cap, sizeof(cap)) != hipSuccess) return 1;
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &dev_ptr, sizeof(dev_ptr));
-}
-
-template <int BN, class Epi, int ABL = 0, bool STAG = false, bool LEPI = false>
+template <int BN, class Epi>
 static void launch_split(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   const int mtiles = (g.M + 255) / 256;
   const int ntiles = gemm_padded_n(g.N) / BN;
   const size_t lds = (size_t)3 * (256 + BN) * ROWB + ((Epi::kFold || std::is_same<Epi, EpiResidPS>::value) ? fold_lds_bytes<BN>() : 0);
   static unsigned long long attr_done = 0ull;
-  if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_ps_split_kernel<BN, Epi, ABL, STAG, LEPI>), (int)lds, attr_done)) return;
-  // tile time in 10 ns ticks: K steps of ~0.65/0.87/1.15 us (BN 64/96/128) + pipeline fill + epilogue
-  int deph = 0;
-  static const bool env_deph = getenv("RIBCA_GEMM_DEPH") != nullptr;
-  if ((g_variant == 15 || env_deph) && mtiles * ntiles >= 1024) deph = (g.Kp / BK) * (BN == 128 ? 115 : BN == 96 ? 87 : 65) + 400;
-  hipLaunchKernelGGL((gemm_ps_split_kernel<BN, Epi, ABL, STAG, LEPI>), dim3(mtiles * ntiles), dim3(768), lds, s, g.A, g.lda, g.W, g.ldw, g.M, g.Kp, mtiles,
-                     ntiles, epi, deph);
+  if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_ps_split_kernel<BN, Epi>), (int)lds, attr_done)) return;
+  hipLaunchKernelGGL((gemm_ps_split_kernel<BN, Epi>), dim3(mtiles * ntiles), dim3(768), lds, s, g.A, g.lda, g.W, g.ldw, g.M, g.Kp, mtiles, ntiles, epi);
 }
 
-#ifdef RIBCA_DIAG
-static int persist_mode() {       // RIBCA_GEMM_PERSIST=1 (or variant 30): persistent workgroups with cross-tile prefetch
-  static const int m = getenv("RIBCA_GEMM_PERSIST") ? atoi(getenv("RIBCA_GEMM_PERSIST")) : 0;
-  return m;
-}
-template <int BN, class Epi>
-static void launch_persist(const GemmArgs& g, const Epi& epi, hipStream_t s) {
-  const int mtiles = (g.M + 255) / 256;
-  const int ntiles = gemm_padded_n(g.N) / BN;
-  const size_t lds = (size_t)3 * (256 + BN) * ROWB;
-  static bool attr_set = false;
-  static int n_cu = 0;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ps_persist_kernel<BN, Epi>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (n_cu <= 0) n_cu = 256;
-    attr_set = true;
-  }
-  const int grid = mtiles * ntiles < n_cu ? mtiles * ntiles : n_cu;
-  hipLaunchKernelGGL((gemm_ps_persist_kernel<BN, Epi>), dim3(grid), dim3(768), lds, s, g.A, g.lda, g.W, g.ldw, g.M, g.Kp, mtiles, ntiles, epi);
-}
-#endif
-
-// Product build: ONE kernel form per (tile width, epilogue) -- loader waves + half-step stagger + LDS epilogue -- plus the
-// two-workgroups-per-CU kernel for mlp.fc1.  The A/B and timing-ablation forms of DESIGN.md section 6 (no stagger, no loads, no
-// epilogue, fewer MFMA passes, stamps, persistent workgroups, duo variants 40-49) exist only in the diagnostic library
-// (-DRIBCA_DIAG: `python -m multiplexed_image_annotator_amd.build --diag` -> libribca_hip_diag.so, used by tools/).
-// RIBCA_DUO_BN192 (bit 0: qkv, bit 1: fc1; default 3, 0 for A/B): 128 x 192 tiles with 4 waves as 1 x 4 on the two-workgroups-per-CU
-// kernel where N % 192 == 0 -- every W fragment is requested by ONE wave: 1.67 bytes from L2 per (row, column, K step) against 2.67 for
-// the 2 x 2 waves of the 192 x 96 tile (qkv at D = 576, fc1 at D = 144) and the same 1.67 as the 192 x 128 tile.  Same bits (the
-// accumulation order per element does not change); qkv launches 840 -> 785 ms per pass, fc1 1950 -> 1928, +0.2-0.3 % end to end in an
-// interleaved same-box A/B (profiles/r3/ab_duo_128x192.txt).
-static int duo_bn192() {
-  static const int v = getenv("RIBCA_DUO_BN192") ? atoi(getenv("RIBCA_DUO_BN192")) : 3;
-  return v;
-}
+// One kernel form per (tile width, epilogue) -- loader waves + half-step stagger + LDS epilogue -- plus the two-workgroups-per-CU kernel
+// (gemm_duo.hip) for the GELU and folded qkv products of weights that carry a fragment-order copy (GemmArgs::WF, set by the block runner):
+//  * GELU (mlp.fc1): same bits, 4-12 % less time on those launches and 1.4 % end to end
+//    (profiles/r2/duo_kernel/ab_end_to_end_fc1_on_duo_6rounds.txt);
+//  * the folded qkv product with V stored row-major (its 16-byte row stores are the GELU epilogue's shape): qkv family 1939 -> 1808 ms per
+//    pass, +0.65 % end to end in an interleaved same-box A/B (profiles/r3/ab_qkv_on_duo.txt);
+//  * where N % 192 == 0 (qkv at D = 576, fc1 at D = 144), the 128 x 192 tile with 4 waves as 1 x 4 -- every W fragment is requested by ONE
+//    wave: 1.67 bytes from L2 per (row, column, K step) against 2.67 for the 2 x 2 waves of the 192 x 96 tile.  Same bits; qkv launches
+//    840 -> 785 ms per pass, fc1 1950 -> 1928, +0.2-0.3 % end to end (profiles/r3/ab_duo_128x192.txt).
+// The residual products choose their form in launch_gemm_resid_ps.
 template <int BN, class Epi>
 static void launch_bn(const GemmArgs& g, const Epi& epi, hipStream_t s) {
-  // GELU GEMMs whose weight carries a fragment-order copy (GemmArgs::WF, set by the block runner for mlp.fc1) run on the
-  // two-workgroups-per-CU kernel: same bits, 4-12 % less time on those launches and 1.4 % end to end
-  // (profiles/r2/duo_kernel/ab_end_to_end_fc1_on_duo_6rounds.txt).  The residual and QKV epilogues stay here: there the duo form is
-  // 5-25 % slower.  RIBCA_GEMM_DUO=0: off.
-  if constexpr (std::is_same<Epi, EpiGelu>::value || std::is_same<Epi, EpiGeluLn>::value) {
-    static const bool duo_on = !(getenv("RIBCA_GEMM_DUO") && atoi(getenv("RIBCA_GEMM_DUO")) == 0);
-    if constexpr (std::is_same<Epi, EpiGeluLn>::value) {
-      if (g_variant == 0 && duo_on && (duo_bn192() & 2) && g.N % 192 == 0 && g.WF != nullptr && g.M >= 4096 && launch_duo<192, Epi>(g, epi, s, 0)) return;
+  constexpr bool gelu = std::is_same<Epi, EpiGelu>::value || std::is_same<Epi, EpiGeluLn>::value, qkv = std::is_same<Epi, EpiQKVLn>::value;
+  if constexpr (gelu || qkv) {
+    bool duo = g.WF != nullptr && g.M >= 4096;
+    if constexpr (qkv) duo = duo && epi.vrow;
+    if constexpr (!std::is_same<Epi, EpiGelu>::value) {
+      if (duo && g.N % 192 == 0 && launch_duo<192, Epi>(g, epi, s)) return;
     }
-    if (g_variant == 0 && duo_on && g.WF != nullptr && g.M >= 4096 && launch_duo<BN, Epi>(g, epi, s, 0)) return;
+    if (duo && launch_duo<BN, Epi>(g, epi, s)) return;
   }
-  // The folded qkv product too, now that V is stored row-major (round 2 measured this epilogue 5-25 % slower on the duo kernel because
-  // of its eight 2-byte V^T stores per value on one wave per SIMD; with 16-byte row stores it is the GELU epilogue's shape): qkv family
-  // 1939 -> 1808 ms per pass, +0.65 % end to end in an interleaved same-box A/B (profiles/r3/ab_qkv_on_duo.txt).  RIBCA_QKV_DUO=0: off.
-  if constexpr (std::is_same<Epi, EpiQKVLn>::value) {
-    static const bool qkv_duo = !(getenv("RIBCA_QKV_DUO") && atoi(getenv("RIBCA_QKV_DUO")) == 0);
-    if (g_variant == 0 && qkv_duo && (duo_bn192() & 1) && g.N % 192 == 0 && g.WF != nullptr && g.M >= 4096 && epi.vrow &&
-        launch_duo<192, Epi>(g, epi, s, 0))
-      return;
-    if (g_variant == 0 && qkv_duo && g.WF != nullptr && g.M >= 4096 && epi.vrow && launch_duo<BN, Epi>(g, epi, s, 0)) return;
-  }
-#ifdef RIBCA_DIAG
-  if constexpr (!std::is_same<Epi, EpiResidPS>::value) {
-    if (g_variant >= 40 && g_variant <= 49) {   // two workgroups per CU (gemm_duo.hip); 41-47 = its timing ablations (bit mask), 48 = stamps
-      if (launch_duo<BN, Epi>(g, epi, s, g_variant - 40)) return;   // 41 = no epilogue, 48 = stamps, 49 = both
-    }
-  }
-  if constexpr (std::is_same<Epi, EpiResidPS>::value || Epi::kFold) {      // these epilogues exist in the LDS-drain forms only
-    switch (g_variant) {
-      case 21: launch_split<BN, Epi, 6, true, true>(g, epi, s); return;
-      case 22: launch_split<BN, Epi, 7, true, true>(g, epi, s); return;
-      case 12: launch_split<BN, Epi, 4, true, true>(g, epi, s); return;
-      case 9: launch_split<BN, Epi, 3, true, true>(g, epi, s); return;
-      default: break;
-    }
-  } else {
-    if ((g_variant == 30 || (g_variant == 0 && persist_mode())) && (g.M + 255) / 256 * (gemm_padded_n(g.N) / BN) >= 512) {
-      launch_persist<BN, Epi>(g, epi, s);
-      return;
-    }
-    switch (g_variant) {
-      case 3: launch_split<BN, Epi, 0, false>(g, epi, s); return;   // no stagger (A/B reference)
-      case 4: launch_split<BN, Epi, 1, false>(g, epi, s); return;   // ablation: no loads
-      case 5: launch_split<BN, Epi, 2, false>(g, epi, s); return;   // ablation: loads only
-      case 7: launch_split<BN, Epi, 1, true>(g, epi, s); return;    // ablation: no loads, staggered
-      case 9: launch_split<BN, Epi, 3, true>(g, epi, s); return;    // ablation: no epilogue
-      case 20: launch_split<BN, Epi, 5, true>(g, epi, s); return;   // ablation: no loads, no epilogue (the K-loop structure alone)
-      case 21: launch_split<BN, Epi, 6, true, true>(g, epi, s); return;   // ablation: 2 MFMAs per operand pair
-      case 22: launch_split<BN, Epi, 7, true, true>(g, epi, s); return;   // ablation: 1 MFMA per operand pair
-      case 23: launch_split<BN, Epi, 8, true>(g, epi, s); return;   // ablation: 2 MFMAs, no epilogue
-      case 24: launch_split<BN, Epi, 9, true>(g, epi, s); return;   // ablation: 1 MFMA, no epilogue
-      case 12: launch_split<BN, Epi, 4, true, true>(g, epi, s); return;   // production kernel + diagnostic time stamps
-      case 14: launch_split<BN, Epi, 0, true>(g, epi, s); return;   // A/B: epilogue straight from the accumulator registers
-      default: break;
-    }
-  }
-#endif
-  launch_split<BN, Epi, 0, true, true>(g, epi, s);   // production: loader waves + half-step stagger + LDS epilogue
+  launch_split<BN, Epi>(g, epi, s);
 }
 
 template <class Epi>
@@ -915,27 +583,13 @@ static void launch_any(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   }
 }
 
-// RIBCA_NT bit 0: fc1 (GELU) output, bit 1: Q / K rows, bit 2: residual z  -- non-temporal epilogue stores (A/B switch)
-static int nt_mask() {
-  static const int m = getenv("RIBCA_NT") ? atoi(getenv("RIBCA_NT")) : 0;
-  return m;
-}
-void launch_gemm_resid(const GemmArgs& g, float* z, int ldz, hipStream_t s) {
-  static const int no_touch = (getenv("RIBCA_GEMM_TOUCH") && atoi(getenv("RIBCA_GEMM_TOUCH")) == 0) ? 2 : 0;
-  launch_any(g, EpiResid{z, ldz, g.bias, g.M, g.N, ((nt_mask() >> 2) & 1) | no_touch}, s);
-}
-void launch_gemm_gelu(const GemmArgs& g, uint16_t* out, int ldo, hipStream_t s) {
-  launch_any(g, EpiGelu{out, ldo, g.bias, g.M, g.N, nt_mask() & 1}, s);
-}
+void launch_gemm_resid(const GemmArgs& g, float* z, int ldz, hipStream_t s) { launch_any(g, EpiResid{z, ldz, g.bias, g.M, g.N}, s); }
+void launch_gemm_gelu(const GemmArgs& g, uint16_t* out, int ldo, hipStream_t s) { launch_any(g, EpiGelu{out, ldo, g.bias, g.M, g.N}, s); }
 // Tile width of the two-workgroups-per-CU form a residual GEMM would take (gemm_duo.hip launch_duo), and the columns of a wave's block
-// in it: 4 waves as 1 x 4 for 64- / 128- / 192-wide tiles, 2 x 2 for 96-wide ones.
-// RIBCA_RESID_DUO192 (default 1; 0 for A/B): where N % 192 == 0 the 128 x 192 tile (every W fragment requested once: 1.67 bytes from L2
-// per unit instead of 2.67) replaces the 192 x 96 one, and with it the long K loops pay too (fc2 at D = 384 / 576).
-static bool resid_duo192() {
-  static const bool on = !(getenv("RIBCA_RESID_DUO192") && atoi(getenv("RIBCA_RESID_DUO192")) == 0);
-  return on;
-}
-static int resid_duo_bn(int N) { return (resid_duo192() && N % 192 == 0) ? 192 : gemm_pick_bn(N); }
+// in it: 4 waves as 1 x 4 for 64- / 128- / 192-wide tiles, 2 x 2 for 96-wide ones.  Where N % 192 == 0 the 128 x 192 tile (every W
+// fragment requested once: 1.67 bytes from L2 per unit instead of 2.67) replaces the 192 x 96 one, and with it the long K loops pay too
+// (fc2 at D = 384 / 576).
+static int resid_duo_bn(int N) { return N % 192 == 0 ? 192 : gemm_pick_bn(N); }
 static int resid_duo_block(int N) {
   const int bn = resid_duo_bn(N);
   return (bn == 96 || bn == 192) ? 48 : bn / 4;
@@ -956,39 +610,37 @@ static bool resid_duo_pays(int N, int Kp) {
 }
 ResidStatGeom launch_gemm_resid_ps(const GemmArgs& g, uint16_t* z, int ldz, float2* part, const float2* prev, int prev_stride, hipStream_t s,
                                    bool force_duo, const MxAct* zmx) {
-  static const int no_touch = (getenv("RIBCA_GEMM_TOUCH") && atoi(getenv("RIBCA_GEMM_TOUCH")) == 0) ? 2 : 0;
-  // proj / fc2 of the classifiers' full blocks: two workgroups per CU, residual through the ring, load-free epilogue (EpiResidZK).
-  // RIBCA_RESID_DUO = 0: never, 1 (default): the shapes where it measured faster, 2: every shape it supports (A/B)
-  static const int duo_mode = getenv("RIBCA_RESID_DUO") ? atoi(getenv("RIBCA_RESID_DUO")) : 1;
+  // proj / fc2 of the classifiers' full blocks: two workgroups per CU, residual through the ring, load-free epilogue (EpiResidZK), on the
+  // shapes where it measured faster
   const int blk = resid_duo_block(g.N);
-  const bool want = force_duo || duo_mode == 2 || (duo_mode == 1 && resid_duo_pays(g.N, g.Kp));
+  const bool want = force_duo || resid_duo_pays(g.N, g.Kp);
   // (No threshold on M: this form is not bit-identical to the one-workgroup kernel -- the residual is added inside the accumulation,
   // the statistics are combined per wave block -- and a cell's result must not depend on the size of the chunk it was computed in.)
   // zmx: the new rows also in the MX3 format (gemm_mx.hip) -- the 128 x 192 tile of the two-workgroups form emits it; the caller asks for
   // it only where that form exists (N % 192 == 0, a fragment-order weight), and the choice is the model's, never the chunk's
   if (zmx != nullptr) {
-    if (g.WF == nullptr || g.N % 192 != 0 || g_variant != 0) {
-      launch_error("launch_gemm_resid_ps: an MX3 copy of the residual rows needs the 128 x 192 form (N %% 192 == 0, a fragment-order weight, "
-                   "gemm variant 0): N = %d, WF %s, variant %d", g.N, g.WF ? "given" : "missing", g_variant);
+    if (g.WF == nullptr || g.N % 192 != 0) {
+      launch_error("launch_gemm_resid_ps: an MX3 copy of the residual rows needs the 128 x 192 form (N %% 192 == 0, a fragment-order weight): "
+                   "N = %d, WF %s", g.N, g.WF ? "given" : "missing");
       return ResidStatGeom{g.N / 48, 48};
     }
     EpiResidZK epi{z, ldz, g.bias, g.M, g.N, part, prev, prev_stride};
     epi.zmx = *zmx;
-    if (!launch_duo<192, EpiResidZK>(g, epi, s, 0)) launch_error("launch_gemm_resid_ps: the 128 x 192 two-workgroups form refused N = %d, Kp = %d", g.N, g.Kp);
+    if (!launch_duo<192, EpiResidZK>(g, epi, s)) launch_error("launch_gemm_resid_ps: the 128 x 192 two-workgroups form refused N = %d, Kp = %d", g.N, g.Kp);
     return ResidStatGeom{g.N / 48, 48};
   }
-  if (want && g_variant == 0 && g.WF != nullptr && g.N % blk == 0 && g.N % 8 == 0) {
+  if (want && g.WF != nullptr && g.N % blk == 0 && g.N % 8 == 0) {
     const EpiResidZK epi{z, ldz, g.bias, g.M, g.N, part, prev, prev_stride};
     bool done = false;
     switch (resid_duo_bn(g.N)) {
-      case 192: done = launch_duo<192, EpiResidZK>(g, epi, s, 0); break;
-      case 128: done = launch_duo<128, EpiResidZK>(g, epi, s, 0); break;
-      case 64: done = launch_duo<64, EpiResidZK>(g, epi, s, 0); break;
-      default: done = launch_duo<96, EpiResidZK>(g, epi, s, 0); break;
+      case 192: done = launch_duo<192, EpiResidZK>(g, epi, s); break;
+      case 128: done = launch_duo<128, EpiResidZK>(g, epi, s); break;
+      case 64: done = launch_duo<64, EpiResidZK>(g, epi, s); break;
+      default: done = launch_duo<96, EpiResidZK>(g, epi, s); break;
     }
     if (done) return ResidStatGeom{g.N / blk, blk};
   }
-  launch_any(g, EpiResidPS{z, ldz, g.bias, g.M, g.N, no_touch, part, prev, prev_stride}, s);
+  launch_any(g, EpiResidPS{z, ldz, g.bias, g.M, g.N, part, prev, prev_stride}, s);
   return ResidStatGeom{gemm_resid_tiles(g.N), gemm_resid_bn(g.N)};
 }
 int gemm_resid_part_rows(int N) {
@@ -997,18 +649,18 @@ int gemm_resid_part_rows(int N) {
   return fine > coarse ? fine : coarse;
 }
 void launch_gemm_gelu_ln(const GemmArgs& g, const float2* rowstat, const float* csum, uint16_t* out, int ldo, hipStream_t s) {
-  launch_any(g, EpiGeluLn{out, ldo, g.bias, g.M, g.N, nt_mask() & 1, rowstat, csum}, s);
+  launch_any(g, EpiGeluLn{out, ldo, g.bias, g.M, g.N, rowstat, csum}, s);
 }
 void launch_gemm_qkv_ln(const GemmArgs& g, const float2* rowstat, const float* csum, uint16_t* q, uint16_t* k, uint16_t* vt, const AttnGeom& a,
                         float scale, hipStream_t s, int n_off, int cls_rows, int rs_stride) {
-  launch_any(g, EpiQKVLn{q, k, vt, g.bias, a.D, a.hd, a.hdq, a.hdv, scale, g.M, g.N, a.T, a.TP, a.H, a.KP, (nt_mask() >> 1) & 1,
+  launch_any(g, EpiQKVLn{q, k, vt, g.bias, a.D, a.hd, a.hdq, a.hdv, scale, g.M, g.N, a.T, a.TP, a.H, a.KP,
                          (unsigned)((0x100000000ull + (unsigned long long)a.T - 1) / (unsigned long long)a.T), rowstat, csum, attention_v_rowmajor(a) ? 1 : 0,
                          n_off, cls_rows, rs_stride}, s);
 }
 int gemm_resid_tiles(int N) { return gemm_padded_n(N) / gemm_pick_bn(N); }
 int gemm_resid_bn(int N) { return gemm_pick_bn(N); }
 void launch_gemm_qkv(const GemmArgs& g, uint16_t* q, uint16_t* k, uint16_t* vt, const AttnGeom& a, float scale, hipStream_t s) {
-  launch_any(g, EpiQKV{q, k, vt, g.bias, a.D, a.hd, a.hdq /* Q/K row pitch: compact */, a.hdv, scale, g.M, g.N, a.T, a.TP, a.H, a.KP, (nt_mask() >> 1) & 1,
+  launch_any(g, EpiQKV{q, k, vt, g.bias, a.D, a.hd, a.hdq /* Q/K row pitch: compact */, a.hdv, scale, g.M, g.N, a.T, a.TP, a.H, a.KP,
                        (unsigned)((0x100000000ull + (unsigned long long)a.T - 1) / (unsigned long long)a.T), nullptr, nullptr, attention_v_rowmajor(a) ? 1 : 0}, s);
 }
 void launch_gemm_rowmap(const GemmArgs& g, float* out, int ldo, const float* add, int ldadd, const int* slot, const int* addrow, int R,

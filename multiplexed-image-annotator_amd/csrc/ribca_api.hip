@@ -466,7 +466,7 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
       // (the MX3 copy of the new rows is read by the next block's qkv GEMM: not wanted where that runs inside the fused per-cell kernel, which
       // reads the packed-split rows, nor in front of the last block)
       const bool emit = mz && !fused_attn && next_full;
-      const ResidStatGeom sg = launch_gemm_mx_resid(hmx, MxWeight{L.fc2mxh, L.fc2mxx}, Mc, D, L.fc2b, w.zps, ld_x, w.part, w.rs, 1, s, 0, emit ? &zmx : nullptr);
+      const ResidStatGeom sg = launch_gemm_mx_resid(hmx, MxWeight{L.fc2mxh, L.fc2mxx}, Mc, D, L.fc2b, w.zps, ld_x, w.part, w.rs, 1, s, emit ? &zmx : nullptr);
       launch_ln_finalize(w.part, sg.tiles, Mc, sg.bn, D, w.rs, s);
     }
     return;

@@ -143,7 +143,7 @@ __device__ __forceinline__ void ps_store4(uint16_t* row, int k, const float v[4]
 // 8-byte pieces -- half the store instructions and 64 contiguous bytes per row and instruction.  Both lanes must be active.
 typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t u32x4;
 template <int PX>
-__device__ __forceinline__ void ps_store4_pair(uint16_t* row, int k, const float v[4], bool nt = false) {
+__device__ __forceinline__ void ps_store4_pair(uint16_t* row, int k, const float v[4]) {
   uint2 hi, lo;
   split4(v, hi, lo);
   const bool odd = (k & 4) != 0;
@@ -159,19 +159,13 @@ __device__ __forceinline__ void ps_store4_pair(uint16_t* row, int k, const float
     // ds_bpermute round trip through the LDS unit (two per tile, each waited for, in the register epilogues)
     const auto rx = __builtin_amdgcn_permlane16_swap(hi.x, lo.x, false, false);
     const auto ry = __builtin_amdgcn_permlane16_swap(hi.y, lo.y, false, false);
-    const u32x4 o = {rx[0], ry[0], rx[1], ry[1]};      // even row: 8 x hi, odd row: 8 x lo
-    u32x4* dst = reinterpret_cast<u32x4*>(row + ps_off(k & ~7) + (odd ? 8 : 0));
-    if (nt) __builtin_nontemporal_store(o, dst);
-    else *dst = o;
+    *reinterpret_cast<u32x4*>(row + ps_off(k & ~7) + (odd ? 8 : 0)) = u32x4{rx[0], ry[0], rx[1], ry[1]};      // even row: 8 x hi, odd row: 8 x lo
     return;
   } else {
     recv.x = __shfl_xor(send.x, PX, 64);
     recv.y = __shfl_xor(send.y, PX, 64);
   }
-  const u32x4 o = odd ? u32x4{recv.x, recv.y, lo.x, lo.y} : u32x4{hi.x, hi.y, recv.x, recv.y};
-  u32x4* dst = reinterpret_cast<u32x4*>(row + ps_off(k & ~7) + (odd ? 8 : 0));
-  if (nt) __builtin_nontemporal_store(o, dst);      // streamed once, read by a later launch: keep it out of this XCD's L2
-  else *dst = o;
+  *reinterpret_cast<u32x4*>(row + ps_off(k & ~7) + (odd ? 8 : 0)) = odd ? u32x4{recv.x, recv.y, lo.x, lo.y} : u32x4{hi.x, hi.y, recv.x, recv.y};
 }
 
 __device__ __forceinline__ f32x4 mfma_f16(f16x8 a, f16x8 b, f32x4 c) {

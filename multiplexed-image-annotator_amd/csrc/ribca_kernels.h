@@ -8,16 +8,14 @@ namespace ribca {
 
 // ----- GEMM (gemm_split16.hip): C = A * W^T with A [M][2*Kp] and W [Np][2*Kp] in packed-split fp16 ---------------
 int gemm_pick_bn(int N);            // column-tile width used for an N-wide weight (64 / 96 / 128)
-int gemm_padded_n(int N);
-int gemm_set_stamp_buffer(void* dev_ptr, long long capacity_blocks);   // diagnostics (variant 12): 20 x uint64 per workgroup; larger grids do not stamp
-void gemm_set_variant(int v);      // 0 = production; 3/4/5/7/9 = A/B and timing-ablation forms of the same kernel           // N rounded up to that tile width (rows the packed weight must have)
+int gemm_padded_n(int N);           // N rounded up to that tile width (rows the packed weight must have)
 
 struct GemmArgs {
   const uint16_t* A; int lda;       // activations, row stride in 16-bit elements (= 2*Kp)
   const uint16_t* W; int ldw;       // packed weight, Np rows
   int M, N, Kp;
   const float* bias;                // [N]
-  const uint16_t* WF = nullptr;     // the same weight in fragment order (gemm_duo.hip, launch_pack_wf); nullptr = made on demand
+  const uint16_t* WF = nullptr;     // the same weight in fragment order (gemm_duo.hip, launch_pack_wf); nullptr: one-workgroup kernel only
 };
 // W [Np][2*Kp] packed-split -> fragment order for the two-workgroups-per-CU kernel: block (jt, s) of 2 KB = [hi | lo] x 64 lanes x 16 B
 void launch_pack_wf(const uint16_t* W, int ldw, int Np, int Kp, uint16_t* WF, hipStream_t s);
@@ -32,7 +30,7 @@ void launch_gemm_gelu(const GemmArgs& g, uint16_t* out, int ldo, hipStream_t s);
 // Returns the geometry of `part` it used: with a fragment-order weight (g.WF) the GEMM runs on the two-workgroups-per-CU
 // kernel with the residual tile riding the A ring (EpiResidZK, gemm_duo.hip) -- for the shapes where that measured faster, or for
 // every shape it supports with force_duo -- and the statistics come per WAVE column block (16 / 32 / 48 columns) instead of per column
-// tile; ln_finalize takes either.  RIBCA_RESID_DUO = 0 / 1 / 2: never / where it pays (default) / wherever supported.
+// tile; ln_finalize takes either.
 struct ResidStatGeom { int tiles, bn; };
 // an activation matrix in the three-plane MX3 format (described with the MX GEMM below)
 struct MxAct { uint16_t* hi; unsigned char* l8; unsigned char* sc; int Kp; int M; };
@@ -86,7 +84,7 @@ bool launch_gemm_gelu_mx(const GemmArgs& g, const float2* rowstat, const float* 
 // z_ps = (z_ps - prev mean) + A W^T + bias, statistics per 48-column wave block (as launch_gemm_resid_ps on the duo kernel)
 // zmx: as for launch_gemm_resid_ps (N % 192 == 0)
 ResidStatGeom launch_gemm_mx_resid(const MxAct& A, const MxWeight& W, int M, int N, const float* bias, uint16_t* z, int ldz, float2* part,
-                                   const float2* prev, int prev_stride, hipStream_t s, int abl = 0, const MxAct* zmx = nullptr);
+                                   const float2* prev, int prev_stride, hipStream_t s, const MxAct* zmx = nullptr);
 // attn.qkv / mlp.fc1 with the LayerNorm fold on the MX kernel: A = the residual rows in MX3 (N % 192 == 0); the fc1 form writes its GELU
 // output in MX3 (out.Kp == N).  Arguments as launch_gemm_qkv_ln / launch_gemm_gelu_mx.
 void launch_gemm_mx_qkv_ln(const MxAct& A, const MxWeight& W, int M, int N, const float* bias, const float2* rowstat, const float* csum, uint16_t* q,

@@ -62,10 +62,6 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 extern "C" {
 
 int32_t ribca_gemm_padded_n(int32_t N) { if (table() == nullptr) return 0; return gemm_padded_n(N); }
-int ribca_set_gemm_variant(int32_t v) {
-  RIBCA_NEED_TABLE(); gemm_set_variant(v); return 0; }
-int ribca_set_gemm_stamps(void* dev_buffer, int64_t capacity_blocks) {
-  RIBCA_NEED_TABLE(); return gemm_set_stamp_buffer(dev_buffer, capacity_blocks); }
 
 int ribca_test_pack_weight(const float* w, int32_t N, int32_t K, uint16_t* out, int32_t Np, int32_t Kp, void* stream) {
   RIBCA_NEED_TABLE();
@@ -160,7 +156,7 @@ int ribca_test_gemm_mx_resid(const uint16_t* A, int32_t lda, const uint16_t* W, 
   launch_mx_pack_act(A, lda, M, Kp, a, s);
   launch_mx_pack_w(W, ldw, (N + 15) / 16 * 16, Kp, Kp, wh_scratch, wx_scratch, s);
   const MxWeight w{wh_scratch, wx_scratch};
-  const ResidStatGeom sg = launch_gemm_mx_resid(a, w, M, N, bias, z_ps, ldz, reinterpret_cast<float2*>(part), reinterpret_cast<const float2*>(prev), 1, s, 0, nullptr);
+  const ResidStatGeom sg = launch_gemm_mx_resid(a, w, M, N, bias, z_ps, ldz, reinterpret_cast<float2*>(part), reinterpret_cast<const float2*>(prev), 1, s, nullptr);
   if (rowstat) launch_ln_finalize(reinterpret_cast<const float2*>(part), sg.tiles, M, sg.bn, N, reinterpret_cast<float2*>(rowstat), s);
   RIBCA_FINISH();
   return 0;
@@ -174,7 +170,7 @@ int ribca_test_gemm_mx_resid_packed(const uint16_t* hi, const uint8_t* l8, const
   hipStream_t s = (hipStream_t)stream;
   const MxAct a{const_cast<uint16_t*>(hi), const_cast<uint8_t*>(l8), const_cast<uint8_t*>(sc), Kp, M};
   const MxWeight w{wh, wx};
-  const ResidStatGeom sg = launch_gemm_mx_resid(a, w, M, N, bias, z_ps, ldz, reinterpret_cast<float2*>(part), reinterpret_cast<const float2*>(prev), 1, s, 0, nullptr);
+  const ResidStatGeom sg = launch_gemm_mx_resid(a, w, M, N, bias, z_ps, ldz, reinterpret_cast<float2*>(part), reinterpret_cast<const float2*>(prev), 1, s, nullptr);
   if (rowstat) launch_ln_finalize(reinterpret_cast<const float2*>(part), sg.tiles, M, sg.bn, N, reinterpret_cast<float2*>(rowstat), s);
   RIBCA_FINISH();
   return 0;
@@ -252,7 +248,7 @@ int ribca_test_gemm_resid_zmx(int32_t kind, const uint16_t* A, int32_t lda, cons
     launch_mx_pack_act(A, lda, M, Kp, a, s);
     launch_mx_pack_w(W, ldw, N, Kp, Kp, w_scratch, wx_scratch, s);
     sg = launch_gemm_mx_resid(a, MxWeight{w_scratch, wx_scratch}, M, N, bias, z_ps, ldz, reinterpret_cast<float2*>(part), reinterpret_cast<const float2*>(prev), 1,
-                              s, 0, &zmx);
+                              s, &zmx);
   } else {
     return fail("ribca_test_gemm_resid_zmx: kind must be 0 or 1");
   }
@@ -302,13 +298,6 @@ int ribca_test_cell_attention(const uint16_t* z_ps, int32_t lda, const uint16_t*
                             1.0f / sqrtf((float)(D / kHeads)), (hipStream_t)stream);
   RIBCA_FINISH();
   return 0;
-}
-int ribca_is_diag_build(void) {
-#ifdef RIBCA_DIAG
-  return 1;
-#else
-  return 0;
-#endif
 }
 int ribca_test_qkv_attention(const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D, int32_t Kp,
                              const float* bias, uint16_t* q, uint16_t* k, uint16_t* vt, uint16_t* out, int32_t ldo, void* stream) {

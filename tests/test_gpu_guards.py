@@ -187,28 +187,6 @@ def test_cell_attention_one_cell_between_guard_bands(dev, d):
 
 
 # ------------------------------------------------------------------------------------------------ refused requests are statuses
-def test_gemm_variant_on_an_mx_model_is_a_status_not_an_abort(dev):
-    """ribca_set_gemm_variant(v != 0) followed by ribca_vit_forward on a D = 384 model reached `g_variant != 0 -> abort()` in
-    launch_gemm_resid_ps (the MX3 copy of the residual rows exists on the production form only) and killed the interpreter"""
-    from multiplexed_image_annotator_amd import ops, synth
-    from multiplexed_image_annotator_amd._lib import RibcaError, lib
-    if not lib().ribca_mxz_enabled(384):
-        pytest.skip("RIBCA_MX / RIBCA_MXZ switched off: the residual rows are not kept in MX3")
-    sd = synth.make_vit_state_dict("immune_extended", synth.SEED_BASE + 3, depth=3)
-    model = ops.VitModel(sd, dev)
-    patches = rnd((5, model.C, 40, 40), 91, dev)
-    good = model.predict_proba(patches, list(range(model.C)))
-    lib().ribca_set_gemm_variant(3)
-    try:
-        with pytest.raises(RibcaError, match="128 x 192"):
-            model.predict_proba(patches, list(range(model.C)))
-        torch.cuda.synchronize()
-    finally:
-        lib().ribca_set_gemm_variant(0)
-    again = model.predict_proba(patches, list(range(model.C)))
-    assert torch.equal(good, again)      # the error was consumed: nothing stale is reported by the next call
-
-
 def test_unsupported_attention_geometry_is_a_status(dev):
     """launch_attention used to abort() on a head dimension it has no kernel for (D = 96: hd = 8)"""
     from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
@@ -245,3 +223,8 @@ def test_mx_launchers_refuse_shapes_without_a_tile_form(dev):
     torch.cuda.synchronize()
     assert st != 0 and b"192" in lib().ribca_last_error()
     assert torch.all(hi_p == 0)
+    # the error was consumed: the next valid call (N = 384, whole 192-column tiles) succeeds and reports nothing stale
+    st = lib().ribca_test_gemm_mx_fc1(ptr(z_ps), 2 * dp, ptr(w_ps), 2 * dp, m, 384, dp, ptr(bias2), ptr(csum), ptr(rs), ptr(a_hi), ptr(a_l8), ptr(a_sc),
+                                      ptr(wh), ptr(wx), ptr(hi_p), ptr(l8_p), ptr(sc_p), stream_ptr())
+    torch.cuda.synchronize()
+    assert st == 0

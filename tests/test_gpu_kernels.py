@@ -339,8 +339,7 @@ def test_gemm_fold_gelu(dev, m, d, mean, std):
 def test_gemm_duo_bit_identical(dev):
     """gemm_duo.hip (two workgroups per CU, weights in fragment order straight to registers; the forward's mlp.fc1 kernel for
     M >= 4096) accumulates every output element in the one-workgroup kernel's order: GELU outputs must be equal bit for bit,
-    ragged M and every column-tile width included.  (The residual / QKV forms of that kernel are diagnostic-library variants:
-    tools/check_gemm_variant.py under RIBCA_DIAG=1.)"""
+    ragged M and every column-tile width included."""
     from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
     for m, n, k in [(4096, 576, 144), (5000, 1152, 288), (7001, 1536, 384), (11100, 2304, 576), (4100, 64, 64), (6000, 192, 96)]:
         kp = (k + 31) // 32 * 32

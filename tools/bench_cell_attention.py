@@ -1,11 +1,7 @@
 #!/usr/bin/env python3
-"""Times the per-cell fused qkv + attention kernel (cell_attention.hip) on 1024 cells against the unfused pair, per D.
-RIBCA_CELL_DBG=1: no attention phase, 2: no MFMAs / fragment reads in the qkv phase (weight stream + barriers only), 3: both
-(results wrong by construction: timing ablations)."""
+"""Times the per-cell fused qkv + attention kernel (cell_attention.hip) on 1024 cells against the unfused pair, per D."""
 import os
 import sys
-
-os.environ.setdefault("RIBCA_DIAG", "1")      # the RIBCA_CELL_DBG ablations exist in libribca_hip_diag.so only (build --diag)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -54,4 +50,4 @@ for d in (384, 288, 144):
             best = min(best, e0.elapsed_time(e1) / 5)
         res[name] = best
     flops = cells * (2.0 * 101 * d * 3 * d + 4.0 * 101 * 101 * d)
-    print(f"D={d} cells={cells} dbg={os.environ.get('RIBCA_CELL_DBG', '0')}: " + "  ".join(f"{k_}: {v * 1e3:.1f} us ({flops / v / 1e9:.0f} TF alg)" for k_, v in res.items()), flush=True)
+    print(f"D={d} cells={cells}: " + "  ".join(f"{k_}: {v * 1e3:.1f} us ({flops / v / 1e9:.0f} TF alg)" for k_, v in res.items()), flush=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""times the MX residual GEMM alone (packed operands, statistics included) for the fc2 shapes; RIBCA_LIB selects a timing-ablation build
-(tools/build_mx_variant.py).  usage: python tools/bench_mx_only.py [cells] [tag]"""
+"""times the MX residual GEMM alone (packed operands, statistics included) for the fc2 shapes; RIBCA_LIB selects another build
+(tools/build_ab_lib.py).  usage: python tools/bench_mx_only.py [cells] [tag]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -5,7 +5,7 @@
     RIBCA_LIB=libribca_ab_old.so python tools/bench_mx_only.py          (the hooks resolve to the matching _test.so: _lib.TEST_LIB_PATH)
 
 `rev` = WORK takes the working tree (with extra -D flags: a timing variant of the current sources).  The libraries are git-ignored and travel
-to the GPU box (named libribca_ab_*: .gpurunignore only drops libribca_hip_diag*); delete them when the A/B is done.
+to the GPU box; delete them when the A/B is done.
 RIBCA_AB_PATCH=<file>: a patch (-p1, paths from the repo root) applied to the temporary copy before compiling -- experiments that never touch the tree."""
 import concurrent.futures
 import os

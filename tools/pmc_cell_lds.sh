@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 P="SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
 for LIB in libribca_hip.so "$@"; do
   tag=${LIB%.so}
-  RIBCA_DIAG=0 RIBCA_LIB=$LIB timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace --output-format csv -d "$OUT/$tag" -o p -- python3 "$ROOT/tools/bench_cell_attention.py" 1024 \
+  RIBCA_LIB=$LIB timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace --output-format csv -d "$OUT/$tag" -o p -- python3 "$ROOT/tools/bench_cell_attention.py" 1024 \
     > "$OUT/$tag.txt" 2> "$OUT/$tag.log" || echo "$tag failed"
 done
 python3 - "$OUT" <<'PY'
