@@ -158,16 +158,42 @@ int ribca_colorize(const int32_t* mask, int64_t n_pixels, const int32_t* label_t
  * x, y (n_cells) fp64 cell centroids (mean column, mean row), cell_type (n_cells) int32 in [0, n_types).  For every cell the
  * n_neighbors nearest cells in fp64 (itself first; ties towards the lower index -- the reference's ball tree leaves ties
  * unspecified) and matrix[type(cell)][type(neighbour)] += 1 for the other n_neighbors - 1.  matrix (n_types, n_types) uint64 is
- * ACCUMULATED into (zero it first; call once per image for the integrated mode).  n_neighbors <= 32, n_types <= 32. */
+ * ACCUMULATED into (zero it first; call once per image for the integrated mode).  n_neighbors <= 32, n_types <= 254 (the most the uint8
+ * index image of ribca_colorize holds; up to 32 types the counts go through an LDS histogram, above that straight to matrix with integer
+ * atomics -- either way order-independent, so the result is deterministic). */
 int ribca_knn_cooccurrence(const double* x, const double* y, const int32_t* cell_type, int32_t n_cells, int32_t n_neighbors, int32_t n_types,
                            uint64_t* matrix, void* stream);
 
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
- * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200) -> counts (n_cells, n_sizes, n_types) uint16 =
+ * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The
  * reference divides each row by its sum and feeds PCA + KMeans on the host.  Synchronises the stream once (reads sizes). */
 int ribca_knn_compositions(const double* x, const double* y, const int32_t* cell_type, int32_t n_cells, int32_t n_types, const int32_t* sizes,
                            int32_t n_sizes, uint16_t* counts, void* stream);
+
+/* ---- extra cell types (Annotator._find_extra_cell_types, model.py:642-675: umap.UMAP(n_components=5).fit_transform of the intensity rows
+ * of every "Others" cell, then HDBSCAN on the host).  umap-learn 0.5's fit_transform restated; DESIGN.md section "Extra cell types". */
+
+/* Exact k nearest rows of x (n, dim) fp32, the row itself included: idx (n, k) int32 and dist (n, k) fp32, each row sorted by (distance,
+ * index).  A distance is sqrt of the fp32 sum of squared differences taken in dimension order (no |x|^2 + |y|^2 - 2 x.y expansion).
+ * k <= min(n, 64), dim <= 256. */
+int ribca_knn_dense(const float* x, int32_t n, int32_t dim, int32_t k, int32_t* idx, float* dist, void* stream);
+
+/* umap's smooth_knn_dist (local_connectivity 1, bandwidth 1, target log2(k) over neighbours 1..k-1, 64 bisection steps, tolerance 1e-5,
+ * floor 1e-3 x the row mean -- the mean of all n k distances for a row without a positive distance) and compute_membership_strengths over
+ * the output of ribca_knn_dense: sigma (n), rho (n), w (n, k) fp32 with w = 0 for the row itself, 1 where d - rho <= 0, else
+ * exp(-(d - rho) / sigma).  2 <= k <= 64. */
+int ribca_umap_fuzzy_weights(const int32_t* idx, const float* dist, int32_t n, int32_t k, float* sigma, float* rho, float* w, void* stream);
+
+/* n_epochs epochs of umap's optimize_layout_euclidean (move_other) on emb (n, dim) fp32 in place, dim <= 8.  The graph is symmetric CSR:
+ * indptr (n + 1) int64, indices (nnz) int32, rev (nnz) int64 = position of edge (k, j) for edge (j, k), eps (nnz) fp64 = epochs_per_sample.
+ * Two deliberate deviations from umap: every epoch is a Jacobi step (each vertex sums its out-edge and negative-sample forces, then the
+ * move_other terms of its in-edges, in CSR order, and all vertices move after the epoch: no atomics, bit-reproducible), and negative
+ * sample p of edge e in epoch t is a counter-based hash of (seed, t, e, p) mod n.  ws: device workspace of at least
+ * 2 * align256(8 nnz) + align256(4 n dim) bytes.  Synchronises the stream once (reads indptr[n]). */
+int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
+                        double a, double b, double gamma, double alpha0, double neg_rate, int32_t n_epochs, uint64_t seed, void* ws,
+                        int64_t ws_bytes, void* stream);
 
 /* ---- vote (Annotator.merge_by_voting, model.py:481-633) ------------------------------------------------------ */
 /* Global class ids: 0..16 = key order of utils.get_void_vote (utils.py:143-146), 17 = "Others".

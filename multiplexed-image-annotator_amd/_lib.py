@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libribca_hip.so")
@@ -34,6 +34,10 @@ SIGNATURES = {
     "ribca_colorize": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ribca_knn_cooccurrence": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ribca_knn_compositions": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ribca_knn_dense": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ribca_umap_fuzzy_weights": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ribca_umap_optimize": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
+                                      c_double, c_int32, c_uint64, c_void_p, c_int64, c_void_p]),
     "ribca_u16_to_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_gauss1d": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "ribca_bg_subtract": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),

@@ -35,6 +35,19 @@ MODEL_DIR = "src/multiplexed_image_annotator/cell_type_annotation/models"   # CW
 _GID = {name: i for i, name in enumerate(ops.GLOBAL_NAMES)}
 
 
+def tile_mode_env(min_cells) -> Optional[str]:
+    """RIBCA_TILE_MODE as the sharding rule (dist.tile_mode) sees it.  The extra-cell-types step (min_cells > 0) pools the "Others" cells of
+    every image of the batch, which tile-per-rank mode keeps on different ranks: there the rule picks cell sharding, and an explicit
+    RIBCA_TILE_MODE=1 is refused (on every rank alike, before anything else runs)."""
+    env = os.environ.get("RIBCA_TILE_MODE")
+    if min_cells is not None and min_cells > 0:
+        if env == "1":
+            raise ValueError("RIBCA_TILE_MODE=1 cannot be combined with min_cells > 0: the extra cell types are clustered over the 'Others' "
+                             "cells of all images together, which tile-per-rank mode keeps on different ranks")
+        return "0"
+    return env
+
+
 class _LazyPredictions:
     """list of {cell type: probability} dicts (model.py:412-414) built on first access from the (n, K) table."""
 
@@ -89,6 +102,7 @@ def _load_state_dict(path: str) -> Dict[str, torch.Tensor]:
 class Annotator(object):
     def __init__(self, marker_list_path, image_path, device, main_dir='./', batch_id='', strict=True, infer=True, min_cells=-1,
                  normalize=True, blur=False, amax=1, confidence=0.25, cell_size=30, cell_type_confidence=None, n_jobs=0):
+        tile_env = tile_mode_env(min_cells)      # refuses RIBCA_TILE_MODE=1 with min_cells > 0 before any file is read
         self.device = device
         self.cell_types = ["B cell", "CD4 T cell", "CD8 T cell", "Dendritic cell", "Regulatory T cell", "Granulocyte cell", "Mast cell",
                            "M1 macrophage cell", "M2 macrophage cell", "Natural killer cell", "Plasma cell", "Endothelial cell",
@@ -111,7 +125,7 @@ class Annotator(object):
         # multi-rank runs: whole images per rank when the batch CSV has at least one per rank (reference main.py:39-52 batch_run; BASELINE
         # config 5: replicas only, nothing exchanged, every rank writes the CSVs of its own images under their batch-wide numbers), cells of
         # every image otherwise (contiguous shards, one all-gather per image, rank 0 writes)
-        self.tile_mode = dist.tile_mode(self.preprocessor._n_images, self.world_size, os.environ.get("RIBCA_TILE_MODE"))
+        self.tile_mode = dist.tile_mode(self.preprocessor._n_images, self.world_size, tile_env)
         self._loaded = False
         self.n_jobs = n_jobs
         self._n_images = 0
@@ -124,9 +138,8 @@ class Annotator(object):
         self.struct_pred, self.nerve_pred = [], []
         self.confidence_thresh = confidence
         self.extra_cell_types = self.min_cells > 0
-        if self.extra_cell_types:
-            raise NotImplementedError("min_cells > 0 (UMAP/HDBSCAN re-clustering of 'Others', model.py:642-675) is post-analysis "
-                                      "outside the accelerated hot path")
+        self.extra_names: List[str] = []      # "Additional type c" of this run: label id len(ops.GLOBAL_NAMES) + position
+        self.extra_stats: Dict[str, float] = {}
         self.n_regions = 0
         self.temp_dir = os.path.join(log_dir, "tmp")
         self.result_dir = os.path.join(main_dir, "results")
@@ -367,6 +380,8 @@ class Annotator(object):
             self.confidence.append([-1 if c == -1 else c for c in conf_h])    # int -1 marks a thresholded cell, as in model.py:507
             self._conf_arrays.append(conf_h)
         self.logger.log("Finished predicting cell types and tissue structures.")
+        if self.extra_cell_types:
+            self._find_extra_cell_types(min_samples=self.min_cells)
         self.cell_types = self._get_unique_cell_types()
         self.cell_types = np.delete(self.cell_types, np.where(self.cell_types == "Others"))
         self.cell_types = np.append(self.cell_types, "Others")
@@ -394,6 +409,62 @@ class Annotator(object):
                 out.append(rows)
             self._annotations_all = out
         return self._annotations_all
+
+    # ---- extra cell types (model.py:642-675) ---------------------------------------------------------------------------------
+    def _find_extra_cell_types(self, root_cell_type="Others", min_samples=10):
+        """The cells the vote left as "Others", pooled over every image of the batch with their intensity rows, are embedded with UMAP
+        (5 components, GPU: manifold.umap_embed) and clustered with HDBSCAN(min_cluster_size=min_samples) on the host; cluster c becomes
+        "Additional type c", noise stays "Others", and every pooled cell gets confidence -1.  With 10 or fewer such cells they all stay
+        "Others".  Cell-sharded multi-rank runs: rank 0 clusters and broadcasts the label vector (one collective); every rank validates the
+        HDBSCAN parameters first, so that none raises while another waits."""
+        import time
+        pooled = [(i, j) for i in range(len(self.annotations)) for j, name in enumerate(self.annotations[i]) if name == root_cell_type]
+        if len(pooled) == 0:
+            return
+        if len(pooled) <= 10:
+            self._apply_extra_labels(pooled, None)
+            return
+        from sklearn.cluster import HDBSCAN
+        HDBSCAN(min_cluster_size=min_samples)._validate_params()      # what fit() would raise, on every rank before the collective
+        cluster = np.zeros(len(pooled), dtype=np.int64)
+        t_embed = t_cluster = 0.0
+        if self.rank == 0:
+            from . import manifold
+            x = np.stack([self.preprocessor.intensity_full[i][j] for i, j in pooled])
+            t0 = time.perf_counter()
+            emb = manifold.umap_embed(x, n_components=5)
+            t_embed = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            cluster = HDBSCAN(min_cluster_size=min_samples).fit(emb).labels_.astype(np.int64)
+            t_cluster = (time.perf_counter() - t0) * 1e3
+        if self.world_size > 1:
+            cluster = dist.broadcast_from_rank0(torch.from_numpy(cluster)).numpy()
+        self._apply_extra_labels(pooled, cluster)
+        n_clusters = int(cluster.max()) + 1 if len(cluster) else 0
+        n_noise = int((cluster < 0).sum())
+        self.extra_stats = {"pooled": len(pooled), "clusters": n_clusters, "noise": n_noise, "embed_ms": t_embed, "cluster_ms": t_cluster}
+        self.logger.log("Extra cell types: {} pooled 'Others' cells, {} clusters found, {} cells left as noise; embed {:.1f} ms, cluster "
+                        "{:.1f} ms.".format(len(pooled), n_clusters, n_noise, t_embed, t_cluster))
+
+    def _apply_extra_labels(self, pooled, cluster: Optional[np.ndarray]) -> None:
+        """pooled[m] = (image, cell position) gets "Additional type {cluster[m]}" (label id len(GLOBAL_NAMES) + cluster[m]) or "Others"
+        for noise / cluster None, and confidence -1 (the int of model.py, -1.0 in the float32 table behind export_annotations)."""
+        base = len(ops.GLOBAL_NAMES)
+        if cluster is not None and len(cluster) and cluster.max() >= 0:
+            self.extra_names = [f"Additional type {c}" for c in range(int(cluster.max()) + 1)]
+        else:
+            self.extra_names = []
+        for m, (i, j) in enumerate(pooled):
+            c = -1 if cluster is None else int(cluster[m])
+            if c >= 0:
+                self.annotations[i][j] = self.extra_names[c]
+                self.label_ids[i][j] = base + c
+            else:
+                self.annotations[i][j] = "Others"
+                self.label_ids[i][j] = ops.OTHERS
+            self.confidence[i][j] = -1
+            if i < len(self._conf_arrays):
+                self._conf_arrays[i][j] = np.float32(-1.0)
 
     def _get_unique_cell_types(self):
         seen = set()
@@ -481,9 +552,7 @@ class Annotator(object):
         reference's per-cell fancy indexing."""
         pre = self.preprocessor
         ids = pre.cell_ids[image_idx]
-        types = {str(t): k for k, t in enumerate(self.cell_types)}
-        gid_to_type = np.array([types.get(name, 0) for name in ops.GLOBAL_NAMES], dtype=np.int64)
-        tidx = gid_to_type[self.label_ids[image_idx]]
+        tidx = self._cell_type_ints(image_idx)
         palette = np.array(self.colors, dtype=np.uint8)
         conf = np.array([float(c) for c in self.confidence[image_idx]], dtype=np.float32)
         return ops.colorize(pre.masks_dev[image_idx], ids, palette[tidx], colors.confidence_colors(conf), (tidx + 1).astype(np.uint8))
@@ -516,9 +585,13 @@ class Annotator(object):
                     Image.fromarray(t_idx.cpu().numpy()).save("./src/multiplexed_image_annotator/cell_type_annotation/_working_dir_temp/output_img_2.png")
 
     # ---- neighbourhood analysis (model.py:798-800 -> spatial_methods.py:13-130) -----------------------------------------
+    def _label_names(self) -> List[str]:
+        """name of every label id: the 18 global classes, then this run's extra cell types"""
+        return list(ops.GLOBAL_NAMES) + list(getattr(self, "extra_names", []))
+
     def _cell_type_ints(self, image_idx: int) -> np.ndarray:
         types = {str(t): k for k, t in enumerate(self.cell_types)}
-        gid_to_type = np.array([types.get(name, 0) for name in ops.GLOBAL_NAMES], dtype=np.int64)
+        gid_to_type = np.array([types.get(name, 0) for name in self._label_names()], dtype=np.int64)
         return gid_to_type[self.label_ids[image_idx]]
 
     def neighborhood_matrix(self, image_indices, n_neighbors=25) -> np.ndarray:

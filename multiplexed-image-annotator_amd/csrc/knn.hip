@@ -4,7 +4,8 @@
 // (d = dx*dx; d += dy*dy, no contraction), ties broken towards the lower index:
 //   one thread per query cell, candidates streamed through LDS in tiles, the 32 best kept sorted in registers (a new candidate
 //   enters at the bottom and bubbles up through statically indexed compare-exchanges), then neighbours 1..k-1 (0 is the cell
-//   itself) are counted into a per-workgroup LDS matrix and flushed with one atomic per non-zero entry.
+//   itself) are counted into a per-workgroup LDS matrix and flushed with one atomic per non-zero entry (up to 32 cell types; above that,
+//   up to 254, each count is an integer atomic straight into the global matrix -- order-independent as well, so still deterministic).
 // n = 1e5 cells -> 1e10 distance evaluations, tens of milliseconds; the reference needs minutes.
 #include <algorithm>
 
@@ -15,7 +16,8 @@ namespace ribca {
 
 constexpr int KNN_MAX = 32;
 constexpr int KNN_TILE = 1024;
-constexpr int KNN_TYPES = 32;
+constexpr int KNN_TYPES = 32;        // LDS histogram of the co-occurrence kernel up to this many types
+constexpr int KNN_MAX_TYPES = 254;   // the most the uint8 index image of colorize holds (type index + 1)
 
 __device__ __forceinline__ bool knn_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
 
@@ -26,7 +28,9 @@ __global__ __launch_bounds__(256) void knn_cooccurrence_kernel(const double* __r
   __shared__ unsigned int hist[KNN_TYPES * KNN_TYPES];
   const int tid = threadIdx.x;
   const int q = blockIdx.x * blockDim.x + tid;
-  for (int i = tid; i < T * T; i += blockDim.x) hist[i] = 0;
+  const bool lds_hist = T <= KNN_TYPES;
+  if (lds_hist)
+    for (int i = tid; i < T * T; i += blockDim.x) hist[i] = 0;
   const double qx = q < n ? x[q] : 0.0, qy = q < n ? y[q] : 0.0;
   double bd[KNN_MAX];
   int bi[KNN_MAX];
@@ -64,8 +68,12 @@ __global__ __launch_bounds__(256) void knn_cooccurrence_kernel(const double* __r
     const int tq = type[q];
 #pragma unroll
     for (int p = 1; p < KNN_MAX; ++p)
-      if (p < k) atomicAdd(&hist[tq * T + type[bi[p]]], 1u);
+      if (p < k) {
+        if (lds_hist) atomicAdd(&hist[tq * T + type[bi[p]]], 1u);
+        else if ((unsigned)tq < (unsigned)T && (unsigned)type[bi[p]] < (unsigned)T) atomicAdd(&matrix[(size_t)tq * T + type[bi[p]]], 1ull);
+      }
   }
+  if (!lds_hist) return;      // uniform over the workgroup
   __syncthreads();
   for (int i = tid; i < T * T; i += blockDim.x)
     if (hist[i]) atomicAdd(&matrix[i], (unsigned long long)hist[i]);
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(256) void knn_composition_kernel(const double* __re
   __shared__ int bi[KC_BUF];
   __shared__ int s_cnt;
   __shared__ double s_tau;
-  __shared__ unsigned int hist[KC_LISTS * KNN_TYPES];
+  __shared__ unsigned int hist[KC_LISTS * KNN_MAX_TYPES];      // n_lists * T used
   const int tid = threadIdx.x;
   const int q = blockIdx.x;
   const double qx = x[q], qy = y[q];
@@ -160,14 +168,14 @@ __global__ __launch_bounds__(256) void knn_composition_kernel(const double* __re
 
 int launch_knn_compositions(const double* x, const double* y, const int32_t* type, int n, int k, int T, int n_lists, const int* list_dev,
                             uint16_t* counts, hipStream_t s) {
-  if (k < 2 || k > KC_MAXK || k > n || T < 1 || T > KNN_TYPES || n_lists < 1 || n_lists > KC_LISTS) return 1;
+  if (k < 2 || k > KC_MAXK || k > n || T < 1 || T > KNN_MAX_TYPES || n_lists < 1 || n_lists > KC_LISTS) return 1;
   hipLaunchKernelGGL(knn_composition_kernel, dim3(n), dim3(256), 0, s, x, y, type, n, k, T, n_lists, list_dev, counts);
   return 0;
 }
 
 int launch_knn_cooccurrence(const double* x, const double* y, const int32_t* type, int n, int k, int T, unsigned long long* matrix,
                             hipStream_t s) {
-  if (k < 1 || k > KNN_MAX || T < 1 || T > KNN_TYPES || k > n) return 1;
+  if (k < 1 || k > KNN_MAX || T < 1 || T > KNN_MAX_TYPES || k > n) return 1;
   hipLaunchKernelGGL(knn_cooccurrence_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, y, type, n, k, T, matrix);
   return 0;
 }

@@ -925,7 +925,7 @@ int ribca_knn_cooccurrence(const double* x, const double* y, const int32_t* cell
   if (n_cells <= 0) return fail("ribca_knn_cooccurrence: no cells");
   if (n_neighbors > n_cells) return fail("ribca_knn_cooccurrence: n_neighbors exceeds the number of cells");
   if (launch_knn_cooccurrence(x, y, cell_type, n_cells, n_neighbors, n_types, reinterpret_cast<unsigned long long*>(matrix), (hipStream_t)stream))
-    return fail("ribca_knn_cooccurrence: n_neighbors must be in [1, 32] and n_types in [1, 32]");
+    return fail("ribca_knn_cooccurrence: n_neighbors must be in [1, 32] and n_types in [1, 254]");
   RIBCA_FINISH();
   return 0;
 }
@@ -943,7 +943,41 @@ int ribca_knn_compositions(const double* x, const double* y, const int32_t* cell
   const int k = host[n_sizes - 1] + 1;
   if (k > n_cells) return fail("ribca_knn_compositions: more neighbours requested than cells");
   if (launch_knn_compositions(x, y, cell_type, n_cells, k, n_types, n_sizes, sizes, counts, (hipStream_t)stream))
-    return fail("ribca_knn_compositions: needs max(sizes) <= 255 and n_types <= 32");
+    return fail("ribca_knn_compositions: needs max(sizes) <= 255 and n_types in [1, 254]");
+  RIBCA_FINISH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------- extra cell types (umap.hip)
+int ribca_knn_dense(const float* x, int32_t n, int32_t dim, int32_t k, int32_t* idx, float* dist, void* stream) {
+  if (!x || !idx || !dist) return fail("ribca_knn_dense: NULL buffer");
+  if (n <= 0 || dim <= 0) return fail("ribca_knn_dense: bad sizes");
+  if (k > n) return fail("ribca_knn_dense: k exceeds the number of rows");
+  if (launch_knn_dense(x, n, dim, k, idx, dist, (hipStream_t)stream)) return fail("ribca_knn_dense: needs 1 <= k <= 64 and dim <= 256");
+  RIBCA_FINISH();
+  return 0;
+}
+
+int ribca_umap_fuzzy_weights(const int32_t* idx, const float* dist, int32_t n, int32_t k, float* sigma, float* rho, float* w, void* stream) {
+  if (!idx || !dist || !sigma || !rho || !w) return fail("ribca_umap_fuzzy_weights: NULL buffer");
+  if (launch_umap_fuzzy_weights(idx, dist, n, k, sigma, rho, w, (hipStream_t)stream))
+    return fail("ribca_umap_fuzzy_weights: needs n >= 1 and 2 <= k <= 64");
+  RIBCA_FINISH();
+  return 0;
+}
+
+int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
+                        double a, double b, double gamma, double alpha0, double neg_rate, int32_t n_epochs, uint64_t seed, void* ws,
+                        int64_t ws_bytes, void* stream) {
+  if (!emb || !indptr || !indices || !rev || !eps || !ws) return fail("ribca_umap_optimize: NULL buffer");
+  if (n <= 0 || dim <= 0 || dim > 8 || n_epochs < 0) return fail("ribca_umap_optimize: needs n >= 1, 1 <= dim <= 8, n_epochs >= 0");
+  int64_t nnz = 0;
+  HIP_TRY(hipMemcpyAsync(&nnz, indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (nnz < 0) return fail("ribca_umap_optimize: indptr[n] is negative");
+  if (ws_bytes < umap_optimize_ws_bytes(n, dim, nnz)) return fail("ribca_umap_optimize: workspace too small");
+  if (launch_umap_optimize(emb, n, dim, indptr, indices, rev, eps, nnz, a, b, gamma, alpha0, neg_rate, n_epochs, seed, ws, (hipStream_t)stream))
+    return fail("ribca_umap_optimize: bad arguments (neg_rate must be positive)");
   RIBCA_FINISH();
   return 0;
 }

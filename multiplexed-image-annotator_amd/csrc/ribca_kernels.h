@@ -164,13 +164,25 @@ int launch_extract_patches_scaled(const PatchArgs& a, int ps, const double* aa_t
 void launch_colorize(const int32_t* mask, long long npx, const int32_t* label_to_cell, int L, const uint8_t* type_rgb, const uint8_t* conf_rgb,
                      const uint8_t* type_idx, uint8_t* out_type, uint8_t* out_conf, uint8_t* out_idx, hipStream_t s);
 
-// ----- k nearest neighbours + cell-type co-occurrence (knn.hip); non-zero return = unsupported k / T
+// ----- k nearest neighbours + cell-type co-occurrence (knn.hip); non-zero return = unsupported k / T (n_types <= 254)
 int launch_knn_cooccurrence(const double* x, const double* y, const int32_t* type, int n, int k, int T, unsigned long long* matrix,
                             hipStream_t s);
 
 // per cell: counts of each type among its nearest list[l] other cells (k = list[last] + 1 <= 256 neighbours incl. itself)
 int launch_knn_compositions(const double* x, const double* y, const int32_t* type, int n, int k, int T, int n_lists, const int* list_dev,
                             uint16_t* counts, hipStream_t s);
+
+// ----- umap embedding of the extra-cell-types step (umap.hip); non-zero return = unsupported sizes
+// exact k nearest rows of an fp32 (n, dim) matrix, itself included, sorted by (distance, index); k <= 64, dim <= 256
+int launch_knn_dense(const float* x, int n, int dim, int k, int32_t* idx, float* dist, hipStream_t s);
+// umap smooth_knn_dist + compute_membership_strengths over a k-NN table; 2 <= k <= 64
+int launch_umap_fuzzy_weights(const int32_t* idx, const float* dist, int n, int k, float* sigma, float* rho, float* w, hipStream_t s);
+// bytes of workspace launch_umap_optimize carves (sampling state per edge, positions after the epoch)
+int64_t umap_optimize_ws_bytes(int n, int dim, int64_t nnz);
+// n_epochs Jacobi epochs of umap's layout SGD (move_other) on a symmetric CSR graph; dim <= 8
+int launch_umap_optimize(float* emb, int n, int dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
+                         int64_t nnz, double a, double b, double gamma, double alpha0, double neg_rate, int n_epochs, uint64_t seed, void* ws,
+                         hipStream_t s);
 
 // ----- whole-image normalisation (normalize.hip) ---------------------------------------------------------------
 void launch_u16_to_f32(const uint16_t* in, float* out, long long n, hipStream_t s);

@@ -57,6 +57,18 @@ def all_reduce_sum(t: torch.Tensor, group=None) -> torch.Tensor:
     return out
 
 
+def broadcast_from_rank0(t: torch.Tensor, group=None) -> torch.Tensor:
+    """Rank 0's copy of a small host tensor on every rank (the extra-cell-types label vector of a cell-sharded run: one collective)."""
+    import torch.distributed as dist
+    if world()[1] == 1:
+        return t
+    out = t.clone()
+    if dist.get_backend(group) == "nccl":      # RCCL moves device buffers only
+        out = out.cuda()
+    dist.broadcast(out, src=0, group=group)
+    return out.cpu()
+
+
 def all_reduce_min_int(v: int, group=None) -> int:
     """Smallest of one integer per rank (control plane: keeps data-dependent branches of a multi-rank pipeline in step)."""
     import torch.distributed as dist

@@ -271,6 +271,48 @@ def knn_compositions(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
     return c.reshape(n, len(sizes) * n_types)
 
 
+# ------------------------------------------------------------------------------------------- umap embedding (extra cell types)
+def knn_dense(x: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact k nearest rows of the (n, dim) fp32 device matrix x, the row itself included: (n, k) int32 indices and (n, k) fp32
+    Euclidean distances, each row sorted by (distance, index)."""
+    x = x.contiguous()
+    n, dim = x.shape
+    idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
+    dist = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    check(lib().ribca_knn_dense(ptr(x), n, dim, int(k), ptr(idx), ptr(dist), stream_ptr()), "ribca_knn_dense")
+    return idx, dist
+
+
+def umap_fuzzy_weights(idx: torch.Tensor, dist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """umap's smooth_knn_dist + compute_membership_strengths over a knn_dense table: sigma (n), rho (n), weights (n, k), fp32."""
+    n, k = idx.shape
+    sigma = torch.empty(n, dtype=torch.float32, device=idx.device)
+    rho = torch.empty(n, dtype=torch.float32, device=idx.device)
+    w = torch.empty((n, k), dtype=torch.float32, device=idx.device)
+    check(lib().ribca_umap_fuzzy_weights(ptr(idx.contiguous()), ptr(dist.contiguous()), n, k, ptr(sigma), ptr(rho), ptr(w), stream_ptr()),
+          "ribca_umap_fuzzy_weights")
+    return sigma, rho, w
+
+
+def umap_optimize_ws_bytes(n: int, dim: int, nnz: int) -> int:
+    """workspace of umap_optimize (include/ribca_hip.h): the sampling state of every edge and the positions after an epoch"""
+    def al(v):
+        return (v + 255) // 256 * 256
+    return 2 * al(8 * nnz) + al(4 * n * dim)
+
+
+def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, rev: torch.Tensor, eps: torch.Tensor, a: float, b: float,
+                  n_epochs: int, seed: int, gamma: float = 1.0, alpha0: float = 1.0, neg_rate: float = 5.0) -> torch.Tensor:
+    """n_epochs of umap's layout SGD on emb (n, dim <= 8) fp32 in place (deterministic Jacobi epochs, hashed negative samples)."""
+    n, dim = emb.shape
+    nnz = int(indices.numel())
+    ws = torch.empty(umap_optimize_ws_bytes(n, dim, nnz), dtype=torch.uint8, device=emb.device)
+    check(lib().ribca_umap_optimize(ptr(emb), n, dim, ptr(indptr), ptr(indices), ptr(rev), ptr(eps), float(a), float(b), float(gamma),
+                                    float(alpha0), float(neg_rate), int(n_epochs), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ws), ws.numel(),
+                                    stream_ptr()), "ribca_umap_optimize")
+    return emb
+
+
 # ------------------------------------------------------------------------------------------- whole-image normalisation
 def _gauss_weights(sigma: float) -> np.ndarray:
     """Taps at distance 0..R of scipy.ndimage.gaussian_filter(sigma, truncate=4.0), computed as scipy computes them."""
