@@ -172,7 +172,8 @@ int ribca_knn_compositions(const double* x, const double* y, const int32_t* cell
                            int32_t n_sizes, uint16_t* counts, void* stream);
 
 /* ---- extra cell types (Annotator._find_extra_cell_types, model.py:642-675: umap.UMAP(n_components=5).fit_transform of the intensity rows
- * of every "Others" cell, then HDBSCAN on the host).  umap-learn 0.5's fit_transform restated; DESIGN.md section "Extra cell types". */
+ * of every "Others" cell, then HDBSCAN).  umap-learn 0.5's fit_transform and sklearn's HDBSCAN defaults restated; DESIGN.md section
+ * "Extra cell types". */
 
 /* Exact k nearest rows of x (n, dim) fp32, the row itself included: idx (n, k) int32 and dist (n, k) fp32, each row sorted by (distance,
  * index).  A distance is sqrt of the fp32 sum of squared differences taken in dimension order (no |x|^2 + |y|^2 - 2 x.y expansion).
@@ -194,6 +195,25 @@ int ribca_umap_fuzzy_weights(const int32_t* idx, const float* dist, int32_t n, i
 int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
                         double a, double b, double gamma, double alpha0, double neg_rate, int32_t n_epochs, uint64_t seed, void* ws,
                         int64_t ws_bytes, void* stream);
+
+/* HDBSCAN* on dense fp32 points, the O(n^2) part (csrc/hdbscan.hip; the tree part after the spanning tree is host code, manifold.py).  The
+ * arithmetic is fixed so that a numpy loop reproduces it bit for bit: d2(i, j) = fp32 sum of squared differences in dimension order (no fma
+ * contraction, as in ribca_knn_dense); every comparison is made on squared values.
+ *
+ * core2 (n) fp32 = the min_samples-th smallest d2(i, .) with the point itself counted (sklearn's kneighbors(X, min_samples)[:, -1], squared).
+ * n >= 2, 1 <= dim <= 64, 1 <= min_samples <= n (up to 64 a sorted list in registers, above that a bisection on the bit pattern of d2 with
+ * one counting pass per step: no per-row list).  ws: 256 bytes.  Synchronises the stream once; a core distance that is not finite (NaN or
+ * infinite coordinates) is an error. */
+int ribca_core_distance(const float* x, int32_t n, int32_t dim, int32_t min_samples, float* core2, void* ws, int64_t ws_bytes, void* stream);
+
+/* The minimum spanning tree of the mutual-reachability graph, mreach2(i, j) = max(core2(i), core2(j), d2(i, j)), under the total order
+ * (mreach2, min(i, j), max(i, j)) -- under it the tree is unique, so the result does not depend on the launch geometry: n - 1 edges with
+ * edges_u < edges_v (int32) and edges_w = sqrt(mreach2) (fp32), in an unspecified but reproducible order.  Boruvka rounds (at most
+ * ceil(log2 n)); the n x n matrix is never formed.  n >= 2, 1 <= dim <= 64.  ws: device workspace of at least
+ * 256 + align256(8 n) + 9 * align256(4 n) bytes.  Synchronises the stream once per round (reads the number of components left); a negative
+ * or non-finite core distance is an error. */
+int ribca_mreach_mst(const float* x, int32_t n, int32_t dim, const float* core2, int32_t* edges_u, int32_t* edges_v, float* edges_w, void* ws,
+                     int64_t ws_bytes, void* stream);
 
 /* ---- vote (Annotator.merge_by_voting, model.py:481-633) ------------------------------------------------------ */
 /* Global class ids: 0..16 = key order of utils.get_void_vote (utils.py:143-146), 17 = "Others".

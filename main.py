@@ -4,7 +4,7 @@
 Runs marker parsing -> preprocess -> predict -> export_annotations -> tissue_region_analysis -> neighborhood_analysis ->
 colorize, as the reference does (main.py:19-28); its plotting steps (heat-maps, pie charts, legends) are CPU work downstream
 of the CSV and are not part of this accelerated path.  ``--min-cells N`` (N > 0) re-clusters the cells the vote left as "Others" into
-"Additional type c" labels (GPU UMAP embedding + HDBSCAN, as the reference's min_cells).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+"Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os

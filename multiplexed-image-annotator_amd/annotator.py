@@ -413,10 +413,11 @@ class Annotator(object):
     # ---- extra cell types (model.py:642-675) ---------------------------------------------------------------------------------
     def _find_extra_cell_types(self, root_cell_type="Others", min_samples=10):
         """The cells the vote left as "Others", pooled over every image of the batch with their intensity rows, are embedded with UMAP
-        (5 components, GPU: manifold.umap_embed) and clustered with HDBSCAN(min_cluster_size=min_samples) on the host; cluster c becomes
-        "Additional type c", noise stays "Others", and every pooled cell gets confidence -1.  With 10 or fewer such cells they all stay
-        "Others".  Cell-sharded multi-rank runs: rank 0 clusters and broadcasts the label vector (one collective); every rank validates the
-        HDBSCAN parameters first, so that none raises while another waits."""
+        (5 components, GPU: manifold.umap_embed) and clustered with HDBSCAN(min_cluster_size=min_samples) -- manifold.hdbscan (core
+        distances and spanning tree on the GPU), or sklearn's host call with RIBCA_HDBSCAN=sklearn; cluster c becomes "Additional type c",
+        noise stays "Others", and every pooled cell gets confidence -1.  With 10 or fewer such cells they all stay "Others".  Cell-sharded
+        multi-rank runs: rank 0 clusters and broadcasts the label vector (one collective); every rank validates the HDBSCAN parameters
+        first, so that none raises while another waits."""
         import time
         pooled = [(i, j) for i in range(len(self.annotations)) for j, name in enumerate(self.annotations[i]) if name == root_cell_type]
         if len(pooled) == 0:
@@ -424,27 +425,38 @@ class Annotator(object):
         if len(pooled) <= 10:
             self._apply_extra_labels(pooled, None)
             return
-        from sklearn.cluster import HDBSCAN
-        HDBSCAN(min_cluster_size=min_samples)._validate_params()      # what fit() would raise, on every rank before the collective
+        from . import manifold
+        backend = manifold.hdbscan_backend()
+        # what fit() would raise, on every rank before the collective
+        if backend == "sklearn":
+            from sklearn.cluster import HDBSCAN
+            HDBSCAN(min_cluster_size=min_samples)._validate_params()
+        else:
+            manifold.validate_hdbscan_params(min_samples)
         cluster = np.zeros(len(pooled), dtype=np.int64)
         t_embed = t_cluster = 0.0
+        split = {"core": 0.0, "mst": 0.0, "tree": 0.0}
         if self.rank == 0:
-            from . import manifold
             x = np.stack([self.preprocessor.intensity_full[i][j] for i, j in pooled])
             t0 = time.perf_counter()
             emb = manifold.umap_embed(x, n_components=5)
             t_embed = (time.perf_counter() - t0) * 1e3
             t0 = time.perf_counter()
-            cluster = HDBSCAN(min_cluster_size=min_samples).fit(emb).labels_.astype(np.int64)
+            if backend == "sklearn":
+                cluster = HDBSCAN(min_cluster_size=min_samples).fit(emb).labels_.astype(np.int64)
+            else:
+                cluster = manifold.hdbscan(emb, min_samples, timings=split)
             t_cluster = (time.perf_counter() - t0) * 1e3
         if self.world_size > 1:
             cluster = dist.broadcast_from_rank0(torch.from_numpy(cluster)).numpy()
         self._apply_extra_labels(pooled, cluster)
         n_clusters = int(cluster.max()) + 1 if len(cluster) else 0
         n_noise = int((cluster < 0).sum())
-        self.extra_stats = {"pooled": len(pooled), "clusters": n_clusters, "noise": n_noise, "embed_ms": t_embed, "cluster_ms": t_cluster}
+        self.extra_stats = {"pooled": len(pooled), "clusters": n_clusters, "noise": n_noise, "embed_ms": t_embed, "cluster_ms": t_cluster,
+                            "backend": backend, "core_ms": split["core"], "mst_ms": split["mst"], "tree_ms": split["tree"]}
         self.logger.log("Extra cell types: {} pooled 'Others' cells, {} clusters found, {} cells left as noise; embed {:.1f} ms, cluster "
-                        "{:.1f} ms.".format(len(pooled), n_clusters, n_noise, t_embed, t_cluster))
+                        "{:.1f} ms ({}: core {:.1f}, mst {:.1f}, tree {:.1f}).".format(len(pooled), n_clusters, n_noise, t_embed, t_cluster,
+                                                                                      backend, split["core"], split["mst"], split["tree"]))
 
     def _apply_extra_labels(self, pooled, cluster: Optional[np.ndarray]) -> None:
         """pooled[m] = (image, cell position) gets "Additional type {cluster[m]}" (label id len(GLOBAL_NAMES) + cluster[m]) or "Others"

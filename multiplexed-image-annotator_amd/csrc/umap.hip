@@ -1,6 +1,6 @@
 // The numeric core of the "extra cell types" step (reference Annotator._find_extra_cell_types, model.py:642-675): umap-learn 0.5's
 // fit_transform restated for the GPU -- exact k-NN in marker space, the fuzzy membership weights of every neighbour, and the layout SGD
-// (optimize_layout_euclidean with move_other).  The graph union, the spectral start and HDBSCAN stay on the host (manifold.py).
+// (optimize_layout_euclidean with move_other).  The graph union and the spectral start stay on the host (manifold.py); HDBSCAN's O(n^2) part is hdbscan.hip.
 //
 // knn_dense: one thread per query row, candidate rows streamed through LDS tiles that every lane reads at the same address (a broadcast:
 //   no bank conflicts), the KM best (distance, index) pairs kept sorted in registers as in knn.hip.  Distances are fp32 sums of squared

@@ -1,13 +1,17 @@
-"""GPU UMAP embedding for the extra-cell-types step (reference Annotator._find_extra_cell_types, model.py:642-675, which calls
+"""GPU UMAP embedding and HDBSCAN for the extra-cell-types step (reference Annotator._find_extra_cell_types, model.py:642-675, which calls
 ``umap.UMAP(n_components=5).fit_transform``).  umap-learn 0.5's ``fit_transform`` defaults restated: the k-NN search, the fuzzy
 membership weights and the layout SGD run in the HIP library (csrc/umap.hip); the graph union, the pruning, the (a, b) fit and the
 spectral start are small host steps in scipy, as in umap itself.  DESIGN.md section "Extra cell types" lists the two deliberate
 deviations of the SGD (Jacobi epochs, hashed negative samples): same input and seed, same bits.
+
+``hdbscan`` restates ``sklearn.cluster.HDBSCAN(min_cluster_size).fit(x).labels_`` with sklearn's defaults: the core distances and the minimum
+spanning tree of the mutual-reachability graph -- the O(n^2) part -- run in the HIP library (csrc/hdbscan.hip); the tree part (single linkage,
+condensing, stabilities, excess-of-mass selection, labels) is host code below, written as small functions over plain arrays.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import scipy.sparse
@@ -188,3 +192,243 @@ def umap_embed(x: np.ndarray, n_components: int = 5, n_neighbors: int = 15, seed
     if timings is not None:
         timings.update(t)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------- HDBSCAN
+def hdbscan_backend() -> str:
+    """RIBCA_HDBSCAN=gpu (default) | sklearn: which clustering Annotator._find_extra_cell_types calls (read per call; sklearn is the
+    reference's own host call, kept for A/B)."""
+    v = os.environ.get("RIBCA_HDBSCAN") or "gpu"
+    if v not in ("gpu", "sklearn"):
+        raise ValueError(f"RIBCA_HDBSCAN must be 'gpu' or 'sklearn', got {v!r}")
+    return v
+
+
+def validate_hdbscan_params(min_cluster_size, min_samples=None, n: Optional[int] = None) -> int:
+    """sklearn's rules for the two parameters (ValueError, as HDBSCAN.fit raises): min_cluster_size an int >= 2, min_samples None or an
+    int >= 1 and at most the number of rows.  Returns the effective min_samples (min_cluster_size where None)."""
+    import numbers
+
+    def is_int(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if not is_int(min_cluster_size) or min_cluster_size < 2:
+        raise ValueError(f"The 'min_cluster_size' parameter of HDBSCAN must be an int in the range [2, inf). Got {min_cluster_size!r} instead.")
+    if min_samples is not None and (not is_int(min_samples) or min_samples < 1):
+        raise ValueError(f"The 'min_samples' parameter of HDBSCAN must be an int in the range [1, inf) or None. Got {min_samples!r} instead.")
+    ms = int(min_cluster_size if min_samples is None else min_samples)
+    if n is not None and ms > n:
+        raise ValueError(f"min_samples ({ms}) must be at most the number of samples in X ({n})")
+    return ms
+
+
+def sort_mst_edges(u: np.ndarray, v: np.ndarray, w: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """the spanning tree's edges (u < v) in the total order (weight, u, v): the order the single-linkage tree is built in"""
+    u, v, w = np.asarray(u), np.asarray(v), np.asarray(w)
+    order = np.lexsort((v, u, w))
+    return u[order], v[order], w[order]
+
+
+def single_linkage(u: np.ndarray, v: np.ndarray, w: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The dendrogram of sorted spanning-tree edges, in scipy's layout: merge i makes node n + i out of left[i] = the node that holds u[i]
+    and right[i] = the node that holds v[i] (the side of the edge's first end is the left child, as in sklearn's make_single_linkage),
+    at height value[i] = w[i], with size[i] points.  Union-find with path compression over the 2 n - 1 nodes."""
+    m = len(u)
+    n = m + 1
+    top = list(range(2 * n - 1))
+    count = [1] * n + [0] * m
+    left, right = [0] * m, [0] * m
+    for i, (a, b) in enumerate(zip(np.asarray(u).tolist(), np.asarray(v).tolist())):
+        ra = a
+        while top[ra] != ra:
+            ra = top[ra]
+        while a != ra:
+            nxt = top[a]
+            top[a] = ra
+            a = nxt
+        rb = b
+        while top[rb] != rb:
+            rb = top[rb]
+        while b != rb:
+            nxt = top[b]
+            top[b] = rb
+            b = nxt
+        node = n + i
+        top[ra] = top[rb] = node
+        left[i], right[i] = ra, rb
+        count[node] = count[ra] + count[rb]
+    return (np.asarray(left, dtype=np.int64), np.asarray(right, dtype=np.int64), np.asarray(w, dtype=np.float64),
+            np.asarray(count[n:], dtype=np.int64))
+
+
+def condense_tree(left: np.ndarray, right: np.ndarray, value: np.ndarray, size: np.ndarray,
+                  min_cluster_size: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The dendrogram with every side smaller than min_cluster_size dropped: rows (parent, child, lambda = 1 / height, size of the child).
+    The root is cluster n.  The dendrogram is walked breadth first from the top (left child before right); a merge whose two sides both
+    reach min_cluster_size is a true split -- its left side gets the next free cluster id, then its right side -- a side below the size
+    falls out of the parent point by point (the points of its subtree breadth first, size 1 each) and the other side, if large enough,
+    keeps the parent's id.  Cluster ids therefore grow from the root down, and the row order is the walk's order (both are what sklearn's
+    _condense_tree produces; the stabilities are summed in row order)."""
+    m = len(left)
+    n = m + 1
+    root = 2 * m
+    lt, rt, ht, sz = left.tolist(), right.tolist(), value.tolist(), size.tolist()
+    order = [root]
+    i = 0
+    while i < len(order):
+        x = order[i]
+        i += 1
+        if x >= n:
+            order.append(lt[x - n])
+            order.append(rt[x - n])
+    cluster_of = [0] * (root + 1)
+    cluster_of[root] = n
+    next_id = n + 1
+    dropped = bytearray(root + 1)
+    rows_p: List[int] = []
+    rows_c: List[int] = []
+    rows_l: List[float] = []
+    rows_s: List[int] = []
+
+    def fall_out(sub, par, lam):
+        queue = [sub]
+        j = 0
+        while j < len(queue):
+            y = queue[j]
+            j += 1
+            dropped[y] = 1
+            if y < n:
+                rows_p.append(par)
+                rows_c.append(y)
+                rows_l.append(lam)
+                rows_s.append(1)
+            else:
+                queue.append(lt[y - n])
+                queue.append(rt[y - n])
+
+    for node in order:
+        if node < n or dropped[node]:
+            continue
+        k = node - n
+        a, b, d = lt[k], rt[k], ht[k]
+        lam = 1.0 / d if d > 0.0 else np.inf
+        na = sz[a - n] if a >= n else 1
+        nb = sz[b - n] if b >= n else 1
+        par = cluster_of[node]
+        if na >= min_cluster_size and nb >= min_cluster_size:
+            for side, cnt in ((a, na), (b, nb)):
+                cluster_of[side] = next_id
+                rows_p.append(par)
+                rows_c.append(next_id)
+                rows_l.append(lam)
+                rows_s.append(cnt)
+                next_id += 1
+        elif na < min_cluster_size and nb < min_cluster_size:
+            fall_out(a, par, lam)
+            fall_out(b, par, lam)
+        elif na < min_cluster_size:
+            cluster_of[b] = par
+            fall_out(a, par, lam)
+        else:
+            cluster_of[a] = par
+            fall_out(b, par, lam)
+    return (np.asarray(rows_p, dtype=np.int64), np.asarray(rows_c, dtype=np.int64), np.asarray(rows_l, dtype=np.float64),
+            np.asarray(rows_s, dtype=np.int64))
+
+
+def cluster_stabilities(parent: np.ndarray, child: np.ndarray, lam: np.ndarray, size: np.ndarray) -> np.ndarray:
+    """stability[c - root] = sum over the rows with parent c of (lambda - birth(c)) * size, birth = the lambda of the row that made c (0 for
+    the root), summed in row order (np.bincount adds in input order)."""
+    root = int(parent.min())
+    births = np.full(max(int(child.max()), root) + 1, np.nan)
+    births[child] = lam
+    births[root] = 0.0
+    with np.errstate(invalid="ignore"):      # duplicated points: inf - inf, as in sklearn
+        contrib = (lam - births[parent]) * size
+    return np.bincount(parent - root, weights=contrib, minlength=int(parent.max()) - root + 1)
+
+
+def select_clusters(parent: np.ndarray, child: np.ndarray, size: np.ndarray, stability: np.ndarray) -> List[int]:
+    """Excess of mass with the root excluded (allow_single_cluster=False): from the highest cluster id down, a cluster whose children's
+    summed (already propagated) stability exceeds its own passes that sum up and is not selected; otherwise it is selected and everything
+    below it is not.  Returns the selected ids in ascending order."""
+    root = int(parent.min())
+    stab = stability.tolist()
+    kids: Dict[int, List[int]] = {}
+    inner = size > 1
+    for p, c in zip(parent[inner].tolist(), child[inner].tolist()):
+        kids.setdefault(p, []).append(c)
+    chosen = [True] * len(stab)
+    chosen[0] = False
+    for node in range(root + len(stab) - 1, root, -1):
+        sub = 0.0
+        for c in kids.get(node, ()):
+            sub += stab[c - root]
+        if sub > stab[node - root]:
+            chosen[node - root] = False
+            stab[node - root] = sub
+        else:
+            stack = list(kids.get(node, ()))
+            while stack:
+                c = stack.pop()
+                chosen[c - root] = False
+                stack.extend(kids.get(c, ()))
+    return [root + k for k, on in enumerate(chosen) if on]
+
+
+def assign_labels(parent: np.ndarray, child: np.ndarray, size: np.ndarray, clusters: Sequence[int]) -> np.ndarray:
+    """Every point gets the number of the nearest selected cluster on its way up the condensed tree, -1 where that way reaches the root.
+    The selected clusters are numbered in ascending id (sklearn's tree_to_labels rule)."""
+    root = int(parent.min())
+    top = np.arange(int(parent.max()) + 1, dtype=np.int64)
+    selected = set(int(c) for c in clusters)
+    inner = size > 1
+    for c, p in sorted(zip(child[inner].tolist(), parent[inner].tolist())):      # ascending id: a parent before its children
+        if c not in selected:
+            top[c] = top[p]
+    number = np.full(len(top), -1, dtype=np.int64)
+    for k, c in enumerate(sorted(selected)):
+        number[c] = k
+    labels = np.full(root, -1, dtype=np.int64)
+    pts = ~inner
+    labels[child[pts]] = number[top[parent[pts]]]
+    return labels
+
+
+def labels_from_mst(u: np.ndarray, v: np.ndarray, w: np.ndarray, min_cluster_size: int) -> np.ndarray:
+    """the tree part of HDBSCAN: spanning-tree edges (any order, u < v) -> labels (n) int64, -1 = noise"""
+    su, sv, sw = sort_mst_edges(u, v, w)
+    tree = condense_tree(*single_linkage(su, sv, sw), int(min_cluster_size))
+    parent, child, lam, size = tree
+    clusters = select_clusters(parent, child, size, cluster_stabilities(parent, child, lam, size))
+    return assign_labels(parent, child, size, clusters)
+
+
+def hdbscan(x: np.ndarray, min_cluster_size: int, min_samples: Optional[int] = None, timings: Optional[Dict[str, float]] = None) -> np.ndarray:
+    """sklearn.cluster.HDBSCAN(min_cluster_size, min_samples).fit(x).labels_ with sklearn's defaults (euclidean, alpha 1, excess of mass, no
+    single cluster, epsilon 0) -> (n) int64, -1 = noise.  Ties between equal mutual-reachability weights are broken by point index, where
+    sklearn's depend on the visiting order of its Prim loop: the clusters agree up to their numbering and a handful of border points
+    (DESIGN.md section "Extra cell types").  ``timings`` (optional) receives the milliseconds of the stages: core, mst, tree."""
+    import time
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError(f"hdbscan expects a 2-D array, got {x.ndim} dimension(s)")
+    n = x.shape[0]
+    ms = validate_hdbscan_params(min_cluster_size, min_samples, n)
+    if not np.isfinite(x).all():
+        raise ValueError("Input X contains NaN or infinity.")
+    dev = _lib.require_gpu()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    t = {}
+    t0 = time.perf_counter()
+    xd = torch.from_numpy(x).to(dev)
+    core2 = ops.core_distance(xd, ms)      # synchronises (reads the non-finite flag)
+    t["core"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    u, v, w = (a.cpu().numpy() for a in ops.mreach_mst(xd, core2))
+    t["mst"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    labels = labels_from_mst(u, v, w, int(min_cluster_size))
+    t["tree"] = (time.perf_counter() - t0) * 1e3
+    if timings is not None:
+        timings.update(t)
+    return labels

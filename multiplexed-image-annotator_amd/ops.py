@@ -313,6 +313,41 @@ def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor
     return emb
 
 
+# ------------------------------------------------------------------------------------------- HDBSCAN (extra cell types)
+def core_distance(x: torch.Tensor, min_samples: int) -> torch.Tensor:
+    """core2 (n) fp32: the min_samples-th smallest squared distance of every row of the (n, dim <= 64) fp32 device matrix x, the row itself
+    counted (include/ribca_hip.h: fp32 sums of squared differences in dimension order)."""
+    x = x.contiguous()
+    n, dim = x.shape
+    core2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws = torch.empty(256, dtype=torch.uint8, device=x.device)
+    check(lib().ribca_core_distance(ptr(x), n, dim, int(min_samples), ptr(core2), ptr(ws), ws.numel(), stream_ptr()), "ribca_core_distance")
+    return core2
+
+
+def mreach_mst_ws_bytes(n: int) -> int:
+    """workspace of mreach_mst (include/ribca_hip.h): the control words and ten per-point / per-label arrays"""
+    def al(v):
+        return (v + 255) // 256 * 256
+    return 256 + al(8 * n) + 9 * al(4 * n)
+
+
+def mreach_mst(x: torch.Tensor, core2: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The minimum spanning tree of the mutual-reachability graph of x (n, dim <= 64) under the total order (mreach2, min(i, j), max(i, j)):
+    u < v (n - 1) int32 and w = sqrt(mreach2) (n - 1) fp32, in a reproducible order."""
+    x = x.contiguous()
+    n, dim = x.shape
+    m = max(n - 1, 0)
+    u = torch.empty(m, dtype=torch.int32, device=x.device)
+    v = torch.empty(m, dtype=torch.int32, device=x.device)
+    w = torch.empty(m, dtype=torch.float32, device=x.device)
+    if ws is None:
+        ws = torch.empty(mreach_mst_ws_bytes(n), dtype=torch.uint8, device=x.device)
+    check(lib().ribca_mreach_mst(ptr(x), n, dim, ptr(core2.contiguous()), ptr(u), ptr(v), ptr(w), ptr(ws), ws.numel(), stream_ptr()),
+          "ribca_mreach_mst")
+    return u, v, w
+
+
 # ------------------------------------------------------------------------------------------- whole-image normalisation
 def _gauss_weights(sigma: float) -> np.ndarray:
     """Taps at distance 0..R of scipy.ndimage.gaussian_filter(sigma, truncate=4.0), computed as scipy computes them."""
