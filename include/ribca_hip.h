@@ -171,6 +171,47 @@ int ribca_knn_cooccurrence(const double* x, const double* y, const int32_t* cell
 int ribca_knn_compositions(const double* x, const double* y, const int32_t* cell_type, int32_t n_cells, int32_t n_types, const int32_t* sizes,
                            int32_t n_sizes, uint16_t* counts, void* stream);
 
+/* ---- tissue regions (spatial_methods.tissue_region_partition, spatial_methods.py:133-198: PCA(0.99) + KMeans of the composition table on the
+ * host, unseeded).  csrc/regions.hip; scikit-learn 1.7's defaults restated and seeded, DESIGN.md section 11.  All arithmetic is fixed so that a
+ * numpy loop reproduces it bit for bit: integer sums for the PCA statistics, fp64 sums in a stated order with no fma contraction elsewhere, no
+ * float atomics.  Supported range, everywhere below: n >= 1, 1 <= F <= 2032 (8 sizes x 254 types), 1 <= d <= 2032, 1 <= k <= min(n, 256);
+ * outside it an entry point returns 1 with a text. */
+
+/* counts (n, F) int16 = the output of ribca_knn_compositions seen as n rows of F = n_sizes * n_types columns, every count in 0 .. 255 (else an
+ * error): colsum (F) int64 = column sums, gram (F, F) int64 = counts^T counts -- exact, whatever the launch geometry.  Both are overwritten.
+ * ws: 256 bytes.  Synchronises the stream once (reads the range flag). */
+int ribca_region_gram(const int16_t* counts, int32_t n, int32_t F, int64_t* colsum, int64_t* gram, void* ws, int64_t ws_bytes, void* stream);
+
+/* y (n, d) fp64: y[i, j] = sum over f = 0 .. F - 1, in that order, of (counts[i, f] / size_col[f] - mean[f]) * comps[j, f]; size_col, mean (F)
+ * and comps (d, F) fp64.  The fp64 composition table is never formed.  d <= F. */
+int ribca_region_project(const int16_t* counts, int32_t n, int32_t F, const double* size_col, const double* mean, const double* comps, int32_t d,
+                         double* y, void* stream);
+
+/* One k-means++ step: for each of the n_cand <= 8 candidate rows cand[t] of y (n, d) fp64, cand_d2[t, i] = min(closest[i], d2(i, cand[t]))
+ * (closest NULL = no minimum yet) with d2 = the fp64 sum of squared differences in dimension order, and pot[t] = the sum of cand_d2[t, :]
+ * taken as: rows of every chunk of 1024 in ascending order, then the chunks in ascending order.  ws: 8 * n_cand * ceil(n / 1024) bytes. */
+int ribca_kmeans_trials(const double* y, int32_t n, int32_t d, const int32_t* cand, int32_t n_cand, const double* closest, double* cand_d2,
+                        double* pot, void* ws, int64_t ws_bytes, void* stream);
+
+/* labels[i] = the j with the least (d2(i, centres[j]), j); mind2 (n, optional) = that d2; changed[0] (uint32) = number of rows whose label
+ * differs from the one labels held on entry. */
+int ribca_kmeans_assign(const double* y, int32_t n, int32_t d, const double* centres, int32_t k, int32_t* labels, double* mind2, uint32_t* changed,
+                        void* stream);
+
+/* The M step.  sums (k, d) fp64 and counts (k) int32: per (cluster, dimension) the rows of every chunk of 1024 added in ascending order, then the
+ * chunks added in ascending order.  Then ribca_kmeans_finalize.  ws: ribca_kmeans_update_ws_bytes(n, d, k) bytes. */
+int64_t ribca_kmeans_update_ws_bytes(int32_t n, int32_t d, int32_t k);
+int ribca_kmeans_update(const double* y, int32_t n, int32_t d, const int32_t* labels, int32_t k, const double* centres_old, double* centres_new,
+                        double* sums, int32_t* counts, const uint32_t* changed, double* stat, void* ws, int64_t ws_bytes, void* stream);
+/* centres_new = sums / counts (the old centre where a count is 0); stat (1 + 2 k) fp64: [0] = changed[0] (0 if NULL), [1 + j] = counts[j],
+ * [1 + k + j] = sum over the dimensions in ascending order of (centres_new[j, f] - centres_old[j, f])^2.  What the host reads per iteration. */
+int ribca_kmeans_finalize(const double* sums, const int32_t* counts, int32_t k, int32_t d, const double* centres_old, double* centres_new,
+                          const uint32_t* changed, double* stat, void* stream);
+/* scikit-learn's rule for empty clusters, on the sums: for m = 0 .. n_empty - 1 in order, row far_rows[m] is subtracted from the sum of its
+ * cluster (labels[far_rows[m]], count - 1) and becomes the sum of cluster empty_ids[m] (count 1).  Call ribca_kmeans_finalize afterwards. */
+int ribca_kmeans_relocate(const double* y, int32_t n, int32_t d, int32_t k, const int32_t* labels, const int32_t* far_rows, const int32_t* empty_ids,
+                          int32_t n_empty, double* sums, int32_t* counts, void* stream);
+
 /* ---- extra cell types (Annotator._find_extra_cell_types, model.py:642-675: umap.UMAP(n_components=5).fit_transform of the intensity rows
  * of every "Others" cell, then HDBSCAN).  umap-learn 0.5's fit_transform and sklearn's HDBSCAN defaults restated; DESIGN.md section
  * "Extra cell types". */

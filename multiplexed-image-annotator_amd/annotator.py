@@ -643,9 +643,15 @@ class Annotator(object):
 
     # ---- tissue regions (model.py:802-804 -> spatial_methods.py:133-198) -------------------------------------------------
     def tissue_region_analysis(self, n, method="kmeans"):
-        """Per-cell region labels from the cell-type make-up of each cell's 10 ... 200 nearest neighbours.  The 201-NN search and
-        the counting run on the GPU (ops.knn_compositions); PCA(0.99) and the clustering are the same scikit-learn calls as in
-        the reference (their random start is not seeded there either, so labels are reproducible only up to that)."""
+        """Per-cell region labels from the cell-type make-up of each cell's 10 ... 200 nearest neighbours.  The 201-NN search and the
+        counting run on the GPU; for method="kmeans" so do PCA(0.99) and k-means (regions.pca_project / regions.kmeans: scikit-learn's
+        defaults restated and seeded with RIBCA_REGION_SEED, so the labels are a pure function of the tables every rank holds), or, with
+        RIBCA_REGIONS=sklearn, the reference's two unseeded host calls.  The other methods are the reference's scikit-learn calls."""
+        if method == "kmeans":
+            from . import regions
+            backend = regions.region_backend()
+            if backend == "gpu":
+                return self._tissue_regions_gpu(n)
         from sklearn.cluster import HDBSCAN, KMeans, SpectralClustering
         from sklearn.decomposition import PCA
         self.n_regions = n
@@ -667,6 +673,38 @@ class Annotator(object):
                 raise UnboundLocalError("local variable 'clusterer' referenced before assignment")
             labels = clusterer.fit_predict(comp)
             self.tissue_regions.append({int(k): labels[j] for j, k in enumerate(self.preprocessor.cell_ids[i].tolist())})
+
+    def _tissue_regions_gpu(self, n):
+        """method="kmeans" on the GPU, no scikit-learn import.  ``region_stats`` holds one record per image."""
+        import time
+        from . import regions
+        seed = regions.default_seed()
+        # what KMeans.fit would raise, before any launch
+        regions.validate_n_clusters(n, min((len(ids) for ids in self.preprocessor.cell_ids[:self._n_images]), default=None))
+        self.n_regions = n
+        self.tissue_regions = []
+        self.region_stats = []
+        for i in range(self._n_images):
+            tab = self.preprocessor.cell_tables[i]
+            x = tab[:, 5].astype(np.float64) / tab[:, 6].astype(np.float64)
+            y = tab[:, 4].astype(np.float64) / tab[:, 6].astype(np.float64)
+            types = self._cell_type_ints(i)
+            counts = ops.knn_composition_counts(x, y, types, int(types.max()) + 1)
+            t0 = time.perf_counter()
+            emb = regions.pca_project(counts, ops.TISSUE_NEIGHBOURHOODS)
+            torch.cuda.synchronize()
+            pca_ms = (time.perf_counter() - t0) * 1e3
+            info = {}
+            t0 = time.perf_counter()
+            labels = regions.kmeans(emb, n, seed, timings=info)
+            kmeans_ms = (time.perf_counter() - t0) * 1e3
+            self.tissue_regions.append({int(k): int(labels[j]) for j, k in enumerate(self.preprocessor.cell_ids[i].tolist())})
+            stats = {"n": int(counts.shape[0]), "F": int(counts.shape[1] * counts.shape[2]), "d": int(emb.shape[1]), "k": int(n),
+                     "iterations": int(info["iterations"]), "pca_ms": pca_ms, "kmeans_ms": kmeans_ms, "backend": "gpu", "seed": seed}
+            self.region_stats.append(stats)
+            self.logger.log("Tissue regions, image {}: {} cells, {} columns -> {} components, k = {}, {} Lloyd iterations; PCA {:.1f} ms, "
+                            "k-means {:.1f} ms (gpu, seed {}).".format(i, stats["n"], stats["F"], stats["d"], n, stats["iterations"], pca_ms,
+                                                                       kmeans_ms, seed))
 
     # ---- outside the accelerated path ------------------------------------------------------------------------------
     def _skip(self, what: str):

@@ -250,11 +250,11 @@ def knn_cooccurrence(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
 TISSUE_NEIGHBOURHOODS = (10, 20, 30, 50, 75, 100, 150, 200)       # spatial_methods.py:155
 
 
-def knn_compositions(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, sizes: Sequence[int] = TISSUE_NEIGHBOURHOODS,
-                     device=None) -> np.ndarray:
-    """(n, len(sizes) * n_types) float64: for every cell and every neighbourhood size the fraction of each cell type among its
-    nearest other cells -- the ``compositions`` matrix of the reference's tissue_region_partition (spatial_methods.py:158-176).
-    The k-NN search and the counting run on the GPU; the division count / size is done here in fp64 as numpy does it there."""
+def knn_composition_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, sizes: Sequence[int] = TISSUE_NEIGHBOURHOODS,
+                           device=None) -> torch.Tensor:
+    """(n, len(sizes), n_types) int16 device tensor: for every cell and every neighbourhood size the number of cells of each type among
+    its nearest other cells (every row sums to its size) -- the integers behind ``knn_compositions``, left on the device for the
+    tissue-region step (regions.pca_project)."""
     dev = device or _lib.require_gpu()
     n = len(x)
     if max(sizes) + 1 > n:
@@ -266,9 +266,87 @@ def knn_compositions(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
     counts = torch.empty((n, len(sizes), n_types), dtype=torch.int16, device=dev)
     check(lib().ribca_knn_compositions(ptr(xd), ptr(yd), ptr(td), n, int(n_types), ptr(sd), len(sizes), ptr(counts), stream_ptr()),
           "ribca_knn_compositions")
-    c = counts.cpu().numpy().astype(np.float64)
+    return counts
+
+
+def knn_compositions(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, sizes: Sequence[int] = TISSUE_NEIGHBOURHOODS,
+                     device=None) -> np.ndarray:
+    """(n, len(sizes) * n_types) float64: for every cell and every neighbourhood size the fraction of each cell type among its
+    nearest other cells -- the ``compositions`` matrix of the reference's tissue_region_partition (spatial_methods.py:158-176).
+    The k-NN search and the counting run on the GPU; the division count / size is done here in fp64 as numpy does it there."""
+    n = len(x)
+    c = knn_composition_counts(x, y, cell_type, n_types, sizes, device).cpu().numpy().astype(np.float64)
     c /= c.sum(axis=2, keepdims=True)
     return c.reshape(n, len(sizes) * n_types)
+
+
+# ------------------------------------------------------------------------------------------- tissue regions (PCA + k-means, csrc/regions.hip)
+def region_gram(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Column sums (F) and Gram matrix (F, F) of the (n, F) int16 device count table, exact int64."""
+    counts = counts.contiguous()
+    n, f = counts.shape
+    colsum = torch.empty(f, dtype=torch.int64, device=counts.device)
+    gram = torch.empty((f, f), dtype=torch.int64, device=counts.device)
+    ws = torch.empty(256, dtype=torch.uint8, device=counts.device)
+    check(lib().ribca_region_gram(ptr(counts), n, f, ptr(colsum), ptr(gram), ptr(ws), ws.numel(), stream_ptr()), "ribca_region_gram")
+    return colsum, gram
+
+
+def region_project(counts: torch.Tensor, size_col: torch.Tensor, mean: torch.Tensor, comps: torch.Tensor) -> torch.Tensor:
+    """y (n, d) fp64 = (counts / size_col - mean) @ comps.T with every output summed over the columns in ascending order."""
+    counts = counts.contiguous()
+    n, f = counts.shape
+    d = comps.shape[0]
+    y = torch.empty((n, d), dtype=torch.float64, device=counts.device)
+    check(lib().ribca_region_project(ptr(counts), n, f, ptr(size_col.contiguous()), ptr(mean.contiguous()), ptr(comps.contiguous()), d, ptr(y),
+                                     stream_ptr()), "ribca_region_project")
+    return y
+
+
+def kmeans_trials(y: torch.Tensor, cand: torch.Tensor, closest: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One k-means++ step on y (n, d) fp64: (L, n) min(closest, d2 to candidate row cand[t]) and (L) potentials (fixed-order sums)."""
+    n, d = y.shape
+    m = int(cand.numel())
+    cand_d2 = torch.empty((m, n), dtype=torch.float64, device=y.device)
+    pot = torch.empty(m, dtype=torch.float64, device=y.device)
+    ws = torch.empty(max(8 * m * ((n + 1023) // 1024), 8), dtype=torch.uint8, device=y.device)
+    check(lib().ribca_kmeans_trials(ptr(y), n, d, ptr(cand), m, ptr(closest), ptr(cand_d2), ptr(pot), ptr(ws), ws.numel(), stream_ptr()),
+          "ribca_kmeans_trials")
+    return cand_d2, pot
+
+
+def kmeans_assign(y: torch.Tensor, centres: torch.Tensor, labels: torch.Tensor, mind2: Optional[torch.Tensor], changed: torch.Tensor) -> None:
+    """labels (n) int32 in place: the centre with the least (d2, index); mind2 (n) fp64; changed (1) int32 = labels that moved."""
+    n, d = y.shape
+    check(lib().ribca_kmeans_assign(ptr(y), n, d, ptr(centres), centres.shape[0], ptr(labels), ptr(mind2), ptr(changed), stream_ptr()),
+          "ribca_kmeans_assign")
+
+
+def kmeans_update_ws_bytes(n: int, d: int, k: int) -> int:
+    return int(lib().ribca_kmeans_update_ws_bytes(n, d, k))
+
+
+def kmeans_update(y: torch.Tensor, labels: torch.Tensor, centres_old: torch.Tensor, centres_new: torch.Tensor, sums: torch.Tensor,
+                  counts: torch.Tensor, changed: Optional[torch.Tensor], stat: torch.Tensor, ws: torch.Tensor) -> None:
+    """The M step in the fixed summation order (include/ribca_hip.h): sums, counts, centres_new and stat (1 + 2 k) are written."""
+    n, d = y.shape
+    check(lib().ribca_kmeans_update(ptr(y), n, d, ptr(labels), centres_old.shape[0], ptr(centres_old), ptr(centres_new), ptr(sums), ptr(counts),
+                                    ptr(changed), ptr(stat), ptr(ws), ws.numel(), stream_ptr()), "ribca_kmeans_update")
+
+
+def kmeans_finalize(sums: torch.Tensor, counts: torch.Tensor, centres_old: torch.Tensor, centres_new: torch.Tensor,
+                    changed: Optional[torch.Tensor], stat: torch.Tensor) -> None:
+    k, d = sums.shape
+    check(lib().ribca_kmeans_finalize(ptr(sums), ptr(counts), k, d, ptr(centres_old), ptr(centres_new), ptr(changed), ptr(stat), stream_ptr()),
+          "ribca_kmeans_finalize")
+
+
+def kmeans_relocate(y: torch.Tensor, labels: torch.Tensor, far_rows: torch.Tensor, empty_ids: torch.Tensor, sums: torch.Tensor,
+                    counts: torch.Tensor) -> None:
+    """scikit-learn's empty-cluster rule on the sums: row far_rows[m] moves from its cluster's sum to empty cluster empty_ids[m]."""
+    n, d = y.shape
+    check(lib().ribca_kmeans_relocate(ptr(y), n, d, sums.shape[0], ptr(labels), ptr(far_rows), ptr(empty_ids), int(far_rows.numel()), ptr(sums),
+                                      ptr(counts), stream_ptr()), "ribca_kmeans_relocate")
 
 
 # ------------------------------------------------------------------------------------------- umap embedding (extra cell types)

@@ -14,6 +14,7 @@ from __future__ import annotations
 import math
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 SEED_BASE = 0x524942430000  # "RIBC" << 16, config k uses SEED_BASE + k
@@ -420,3 +421,22 @@ def make_image_for_mask(mask: torch.Tensor, n_channels: int, seed: int, positive
 FULL_PANEL_MARKERS: List[str] = ['DAPI', 'CD3', 'CD4', 'CD8', 'CD11c', 'CD15', 'CD20', 'CD45', 'CD56', 'CD68', 'CD138',
                                  'CD163', 'FoxP3', 'Granzyme B', 'Trypase']
 BASIC_PANEL_MARKERS: List[str] = ['CD45', 'CD20', 'CD4', 'CD8', 'DAPI', 'CD11c', 'CD3']
+
+
+def planted_bands(n: int, n_types: int, n_bands: int, seed: int):
+    """A tissue with planted regions for the tissue-region step: n cell centroids on a jittered square grid (no two distances tie), cut into
+    n_bands vertical bands, each with its own Dirichlet mix of the n_types cell types.  Returns x, y (fp64), cell type (int32), band (int64).
+    Every type occurs at least once (type t is forced on cell t), so that the type axis has n_types entries."""
+    rng = np.random.RandomState(seed)
+    side = int(np.ceil(np.sqrt(n)))
+    cell = np.arange(n)
+    x = (cell % side).astype(np.float64) * 10.0 + rng.uniform(-4.0, 4.0, n)
+    y = (cell // side).astype(np.float64) * 10.0 + rng.uniform(-4.0, 4.0, n)
+    band = np.minimum((x / (side * 10.0 / n_bands)).astype(np.int64), n_bands - 1)
+    band = np.maximum(band, 0)
+    mix = rng.dirichlet(np.full(n_types, 0.6), size=n_bands)
+    u = rng.uniform(size=n)
+    types = np.array([np.searchsorted(np.cumsum(mix[b]), v) for b, v in zip(band.tolist(), u.tolist())], dtype=np.int64)
+    types = np.minimum(types, n_types - 1).astype(np.int32)
+    types[:n_types] = np.arange(n_types, dtype=np.int32)
+    return x, y, types, band
