@@ -256,6 +256,37 @@ int ribca_core_distance(const float* x, int32_t n, int32_t dim, int32_t min_samp
 int ribca_mreach_mst(const float* x, int32_t n, int32_t dim, const float* core2, int32_t* edges_u, int32_t* edges_v, float* edges_w, void* ws,
                      int64_t ws_bytes, void* stream);
 
+/* ---- spectral start of the embedding on the GPU (umap's spectral_layout; csrc/spectral.hip).  The three operations of a
+ * block eigensolver that touch all n rows; the solver itself (manifold.spectral_component_gpu) is host code over them.  All fp64, every
+ * product and sum rounded on its own, the order of every sum fixed: a numpy loop reproduces each bit (tests/spectral_numpy.py). */
+
+/* y = alpha (S x) + beta x + gamma z, S = D^-1/2 A D^-1/2: A the symmetric canonical CSR graph of ribca_umap_optimize (indptr (n + 1) int64,
+ * indices (nnz) int32, weights (nnz) fp32), dinv (n) fp64 = 1 / sqrt(degree); x, y, z (n, m) row-major fp64, 1 <= m <= 16.
+ * (S x)[i, c] = the sum, started at 0, over the entries e of row i in CSR order of ((dinv[i] * (double) w[e]) * dinv[j_e]) * x[j_e, c]; then
+ * v = alpha * that; v = v + beta * x[i, c] unless beta == 0; v = v + gamma * z[i, c] unless z is NULL.  A row without entries gives
+ * beta x + gamma z.  y must not be x; y may be z.  Entries outside [0, nnz) and columns outside [0, n) are skipped, never read. */
+int ribca_spectral_spmm(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t nnz, const double* dinv, int32_t n, int32_t m,
+                        const double* x, double alpha, double beta, double gamma, const double* z, double* y, void* stream);
+
+/* g (p, q) = u^T v for u (n, p), v (n, q) fp64, p, q <= 48: per output the rows of every chunk of 1024 added in ascending order (started at 0),
+ * then the chunks added in ascending order (started at 0).  ws: ribca_spectral_gram_ws_bytes(n, p, q) = 8 p q ceil(n / 1024) bytes. */
+int64_t ribca_spectral_gram_ws_bytes(int32_t n, int32_t p, int32_t q);
+int ribca_spectral_gram(const double* u, const double* v, int32_t n, int32_t p, int32_t q, double* g, void* ws, int64_t ws_bytes, void* stream);
+
+/* x (n, m) = u (n, p) c (p, m), p, m <= 48: x[i, j] = (x[i, j] if add, else 0) + u[i, 0] * c[0, j] + ... + u[i, p - 1] * c[p - 1, j], added in
+ * that order.  x must not be u. */
+int ribca_spectral_combine(const double* u, int32_t n, int32_t p, const double* c, int32_t m, int32_t add, double* x, void* stream);
+
+/* ---- scatter plot (Annotator.umap_visualization, model.py:746-765; csrc/scatter.hip) ---------------------------------------------------
+ * points (n, 2) fp32, rgb (n, 3) uint8 -> out (height, width, 3) uint8, white background.  Point i has its centre at column
+ * rint(x * (float) ax + (float) bx), row rint(y * (float) ay + (float) by) (fp32, no contraction) and covers the pixels at offsets (dx, dy) with
+ * dx^2 + dy^2 <= radius^2 + 1 (|dx|, |dy| <= radius <= 16) that lie on the canvas; where discs overlap the point with the highest index
+ * shows (integer atomicMax: reproducible bytes).  A centre that is not finite or not on the canvas is skipped; *skipped (HOST) = how many.
+ * ws: ribca_scatter_raster_ws_bytes(height, width) bytes.  height, width <= 16384.  Synchronises the stream once. */
+int64_t ribca_scatter_raster_ws_bytes(int32_t height, int32_t width);
+int ribca_scatter_raster(const float* points, const uint8_t* rgb, int32_t n, double ax, double bx, double ay, double by, int32_t height, int32_t width,
+                         int32_t radius, uint8_t* out, int64_t* skipped, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- vote (Annotator.merge_by_voting, model.py:481-633) ------------------------------------------------------ */
 /* Global class ids: 0..16 = key order of utils.get_void_vote (utils.py:143-146), 17 = "Others".
  * p_a (n, k_a) and optional p_b (n, k_b) are softmax outputs; map_* (k) int8 give each class's global id;

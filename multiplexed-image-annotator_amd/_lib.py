@@ -49,6 +49,14 @@ SIGNATURES = {
                                       c_double, c_int32, c_uint64, c_void_p, c_int64, c_void_p]),
     "ribca_core_distance": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_mreach_mst": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_spectral_spmm": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_double, c_double, c_double,
+                                      c_void_p, c_void_p, c_void_p]),
+    "ribca_spectral_gram_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ribca_spectral_gram": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_spectral_combine": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "ribca_scatter_raster_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ribca_scatter_raster": (c_int32, [c_void_p, c_void_p, c_int32, c_double, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_void_p,
+                                       POINTER(c_int64), c_void_p, c_int64, c_void_p]),
     "ribca_u16_to_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_gauss1d": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "ribca_bg_subtract": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),

@@ -1,9 +1,9 @@
 """``Annotator``: drop-in for the reference orchestrator on its hot path (cell_type_annotation/model.py:90-919):
 same constructor, ``preprocess()``, ``predict(batch_size)``, ``export_annotations()``, ``clear_tmp()``,
 ``get_cell_type_names()`` and the attributes downstream code reads (``annotations``, ``confidence``, ``annotations_all``,
-``cell_types``, ``channel_parser``, ``preprocessor``, ``*_pred``).  Compute runs in the HIP library; the plotting methods of
-the reference (heat-maps, pie charts, UMAP) are outside the accelerated path: they log and return, so the
-reference's own call sequence (main.py:19-28) completes against this class.
+``cell_types``, ``channel_parser``, ``preprocessor``, ``*_pred``).  Compute runs in the HIP library; the heat-map and pie-chart methods of
+the reference are outside the accelerated path: they log and return, so the reference's own call sequence
+(main.py:19-28) completes against this class; ``umap_visualization()`` embeds and draws on the GPU.
 """
 from __future__ import annotations
 
@@ -720,5 +720,62 @@ class Annotator(object):
         """model.py:860-913 (pie charts): not drawn; the CSVs hold the labels."""
         return self._skip("cell_type_composition")
 
+    UMAP_CANVAS = (1200, 1600)      # rows, columns of {batch_id}_umap.png
+    UMAP_RADIUS = 2
+
     def umap_visualization(self, *_a, **_k):
-        return self._skip("umap_visualization")
+        """model.py:746-765: a 2-D UMAP of the intensity rows of every cell of the batch, coloured by cell type with the palette ``paint``
+        uses, as ``{batch_id}_umap.png`` (1200 x 1600, filled discs in data order on white, no axes or legend: manifold.umap_embed with two
+        components, then ops.scatter_raster) and ``{batch_id}_umap.csv`` (Image, Cell Index, Cell Type, UMAP 1, UMAP 2: the same points, for
+        a plot with axes).  The spectral start runs on the GPU unless RIBCA_SPECTRAL=scipy; the embedding is seeded (RIBCA_UMAP_SEED), so
+        two runs write the same bytes -- the reference's is not.  Returns the (n_cells, 2) float32 embedding and records ``umap_stats``.
+        Cell-sharded multi-rank runs: rank 0 embeds, broadcasts the embedding (one collective) and writes.  Skipped with a log line, returning
+        None: fewer than 4 cells, and tile-per-rank mode (no rank holds the other ranks' intensity rows)."""
+        import time
+        if len(self.annotations) == 0:
+            raise ValueError("No annotations to visualize")
+        if self.tile_mode:
+            self.logger.log("umap_visualization: skipped (tile-per-rank mode: the intensity rows stay on the rank that owns the image)")
+            return None
+        from . import manifold
+        backend = manifold.spectral_backend("gpu")      # validated on every rank before the collective
+        rows = [(i, j, name) for i in range(len(self.annotations)) for j, name in enumerate(self.annotations[i])]
+        n = len(rows)
+        if n < 4:
+            self.logger.log(f"umap_visualization: skipped ({n} cells: too few to embed)")
+            return None
+        seed = manifold.default_seed()
+        emb = np.zeros((n, 2), dtype=np.float32)
+        t: Dict = {}
+        if self.rank == 0:
+            x = np.concatenate([a for a in self.preprocessor.intensity_full[:len(self.annotations)] if a is not None], axis=0)
+            assert len(x) == n
+            emb = manifold.umap_embed(x, n_components=2, seed=seed, timings=t, spectral=backend)
+        if self.world_size > 1:
+            emb = dist.broadcast_from_rank0(torch.from_numpy(emb)).numpy()
+        raster_ms, skipped = 0.0, 0
+        if self._writes_files():
+            from PIL import Image
+            t0 = time.perf_counter()
+            types = {str(c): k for k, c in enumerate(self.cell_types)}
+            palette = np.array(self.colors, dtype=np.uint8)
+            rgb = palette[np.array([types[name] for _, _, name in rows], dtype=np.int64)]
+            h, w = self.UMAP_CANVAS
+            dev = torch.device("cuda", torch.cuda.current_device())
+            img, skipped = ops.scatter_raster(torch.from_numpy(emb).to(dev), torch.from_numpy(np.ascontiguousarray(rgb)).to(dev), h, w,
+                                              ops.scatter_affine(emb, h, w), self.UMAP_RADIUS)
+            Image.fromarray(img.cpu().numpy()).save(os.path.join(self.result_dir, f"{self.batch_id}_umap.png"))
+            raster_ms = (time.perf_counter() - t0) * 1e3
+            with open(os.path.join(self.result_dir, f"{self.batch_id}_umap.csv"), "w") as f:
+                f.write("Image,Cell Index,Cell Type,UMAP 1,UMAP 2\n")
+                for (i, j, name), (u, v) in zip(rows, emb.tolist()):
+                    f.write(f"{self._image_number(i)},{int(self.preprocessor.cell_ids[i][j])},{name},{u:.9g},{v:.9g}\n")
+        self.umap_stats = {"n": n, "seed": seed, "spectral_backend": t.get("spectral_backend", backend),
+                           "spectral_iterations": t.get("spectral_iterations"), "spectral_spmm": t.get("spectral_spmm"),
+                           "spectral_gpu_components": t.get("spectral_gpu_components", 0), "raster_ms": raster_ms,
+                           "skipped_points": skipped, **{k + "_ms": t.get(k, 0.0) for k in ("knn", "fuzzy", "graph", "init", "sgd")}}
+        s = self.umap_stats
+        self.logger.log("UMAP plot: {} cells; knn {:.1f}, fuzzy {:.1f}, graph {:.1f}, init {:.1f} ({}, {} filter passes), sgd {:.1f}, raster {:.1f} ms; "
+                        "seed {}.".format(n, s["knn_ms"], s["fuzzy_ms"], s["graph_ms"], s["init_ms"], s["spectral_backend"],
+                                          s["spectral_iterations"], s["sgd_ms"], raster_ms, seed))
+        return emb

@@ -90,13 +90,192 @@ def reverse_edges(g: scipy.sparse.csr_matrix) -> np.ndarray:
     return rev
 
 
-def _spectral_component(g: scipy.sparse.csr_matrix, dim: int) -> Optional[np.ndarray]:
+def spectral_backend(default: str = "scipy") -> str:
+    """RIBCA_SPECTRAL=gpu | scipy: who computes the spectral start (read per call).  ``scipy`` is umap's own host call (eigsh); ``gpu`` is
+    spectral_component_gpu.  The caller names its default: the extra-cell-types step "scipy", the whole-batch plot "gpu"."""
+    v = os.environ.get("RIBCA_SPECTRAL") or default
+    if v not in ("gpu", "scipy"):
+        raise ValueError(f"RIBCA_SPECTRAL must be 'gpu' or 'scipy', got {v!r}")
+    return v
+
+
+#: a connected component below this many vertices stays on eigsh whatever the backend: ARPACK needs a few milliseconds there, and the GPU
+#: solver's fixed cost (a few dozen launches and small read-backs per iteration) is of the same size
+SPECTRAL_GPU_MIN_ROWS = 256
+SPECTRAL_MAX_DIM = 12      # block = wanted + guard columns <= 16, the widest ribca_spectral_spmm
+
+
+class GpuSpectralPrims:
+    """The three primitives of csrc/spectral.hip behind the interface spectral_component_gpu is written over (tests/spectral_numpy.py holds the
+    numpy twin, bit-equal operation by operation).  A block is an (n, m) fp64 device tensor; small matrices cross as numpy arrays."""
+
+    def __init__(self, device=None):
+        self.dev = device or _lib.require_gpu()
+        self._ws = None
+
+    def graph(self, g: scipy.sparse.csr_matrix, dinv: np.ndarray):
+        return (torch.from_numpy(g.indptr.astype(np.int64)).to(self.dev), torch.from_numpy(g.indices.astype(np.int32)).to(self.dev),
+                torch.from_numpy(g.data.astype(np.float32)).to(self.dev), torch.from_numpy(np.ascontiguousarray(dinv, dtype=np.float64)).to(self.dev))
+
+    def upload(self, a: np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
+
+    def download(self, h) -> np.ndarray:
+        return h.cpu().numpy()
+
+    def empty(self, n: int, m: int):
+        return torch.empty((n, m), dtype=torch.float64, device=self.dev)
+
+    def spmm(self, graph, x, out, alpha=1.0, beta=0.0, gamma=0.0, z=None):
+        return ops.spectral_spmm(graph[0], graph[1], graph[2], graph[3], x, out, alpha, beta, gamma, z)
+
+    def gram(self, u, v) -> np.ndarray:
+        need = ops.spectral_gram_ws_bytes(u.shape[0], u.shape[1], v.shape[1])
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.dev)
+        return ops.spectral_gram(u, v, self._ws).cpu().numpy()
+
+    def combine(self, u, c: np.ndarray, out, add=False):
+        return ops.spectral_combine(u, self.upload(c), out, add)
+
+
+def _orthonormalise(prims, src, tmp, dst) -> bool:
+    """dst = an orthonormal basis of the columns of src: two passes of src T with T = D^-1 V L^-1/2 from the eigendecomposition V L V^T of the
+    diagonally scaled Gram matrix (a Cholesky factor would do on a well-conditioned block; this form also survives a filtered block whose
+    columns lean on one another).  Gram + combine only.  False: a column vanished or is not finite."""
+    for a, b in ((src, tmp), (tmp, dst)):
+        gm = prims.gram(a, a)
+        gm = (gm + gm.T) * 0.5
+        d = np.sqrt(np.diag(gm))
+        if not np.isfinite(d).all() or (d <= 0).any():
+            return False
+        lam, vec = np.linalg.eigh(gm / np.outer(d, d))
+        lam = np.maximum(lam, lam.max() * 1e-15)
+        prims.combine(a, (vec / np.sqrt(lam)) / d[:, None], b)
+    return True
+
+
+def spectral_component_gpu(g: scipy.sparse.csr_matrix, dim: int, tol: float = 1e-5, max_spmm: int = 20000, prims=None, seed: int = 0,
+                           info: Optional[Dict] = None) -> Optional[np.ndarray]:
+    """The eigenvectors 1..dim of L = I - S, S = D^-1/2 A D^-1/2, of one connected graph by the smallest non-trivial eigenvalues: (n, dim)
+    fp64, unit columns, in each column the entry of largest magnitude (the first of them) positive -- or None where initial_embedding falls
+    back to the seeded uniform start (fewer than dim + 2 vertices, a vertex without weight, ``max_spmm`` column products spent before every
+    wanted pair has ||S x - theta x||_2 <= tol, a block that lost rank).
+
+    Chebyshev-filtered subspace iteration on S with Rayleigh-Ritz.  The trivial eigenvector sqrt(deg) / ||sqrt(deg)||
+    is known and projected out of every block, never computed.  The block holds dim wanted and a few guard columns (16 at most) and starts
+    from RandomState(seed).  Every pass: Q = orthonormal basis of the block, H = Q^T S Q, (theta, W) = eigh(H), X = Q W, residuals; then the
+    block becomes p(S) X with p the Chebyshev polynomial that is bounded by 1 / T_m(..) on [-1, cut] and 1 at 1, cut = the lowest Ritz value
+    of the block, the degree m taken from the gap between the last wanted Ritz value and cut.  All work on n rows goes through ``prims``
+    (spmm / gram / combine: GpuSpectralPrims, or the numpy twin of the tests); the host keeps the small eigh and the decisions, so two
+    bit-equal sets of primitives give bit-equal results.  ``info`` receives iterations, spmm (column products), spmm_calls, block, degrees,
+    eigenvalues (of L) and residuals."""
+    n = g.shape[0]
+    if dim < 1 or dim > SPECTRAL_MAX_DIM:
+        raise ValueError(f"spectral_component_gpu needs 1 <= dim <= {SPECTRAL_MAX_DIM}, got {dim}")
+    stats = {"iterations": 0, "spmm": 0, "spmm_calls": 0, "degrees": []}
+
+    def give_up():
+        if info is not None:
+            info.update(stats)
+        return None
+
+    if n < dim + 2:
+        return give_up()
+    g = g.tocsr()
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(g.indptr))
+    deg = np.bincount(rows, weights=g.data.astype(np.float64), minlength=n)      # fp64 row sums in CSR order
+    if not (deg > 0).all() or not np.isfinite(deg).all():
+        return give_up()
+    root = np.sqrt(deg)
+    if prims is None:
+        prims = GpuSpectralPrims()
+    b = min(16, max(dim + 6, 2 * dim), n - 1)
+    stats["block"] = b
+    gr = prims.graph(g, 1.0 / root)
+    v0 = prims.upload((root / np.sqrt(np.dot(root, root)))[:, None])
+    q, sq, x, r, t = (prims.empty(n, b) for _ in range(5))
+    cur = prims.upload(np.random.RandomState(seed).normal(size=(n, b)))
+
+    def spend(cols):
+        if stats["spmm"] + cols > max_spmm:
+            return False
+        stats["spmm"] += cols
+        stats["spmm_calls"] += 1
+        return True
+
+    while True:
+        prims.combine(v0, -prims.gram(v0, cur), cur, add=True)      # project the trivial eigenvector out
+        if not _orthonormalise(prims, cur, t, q):
+            return give_up()
+        if not spend(b):
+            return give_up()
+        prims.spmm(gr, q, sq)
+        h = prims.gram(q, sq)
+        theta, w = np.linalg.eigh((h + h.T) * 0.5)
+        theta, w = theta[::-1].copy(), np.ascontiguousarray(w[:, ::-1])      # descending in S = ascending in L
+        prims.combine(q, w, x)
+        prims.combine(sq, w, r)
+        prims.combine(q, -(w * theta[None, :]), r, add=True)      # r = S x - x diag(theta)
+        res = np.sqrt(np.maximum(np.diag(prims.gram(r, r)), 0.0))
+        stats["eigenvalues"] = (1.0 - theta[:dim]).tolist()
+        stats["residuals"] = res[:dim].tolist()
+        if not np.isfinite(res).all():
+            return give_up()
+        if (res[:dim] <= tol).all():
+            break
+        stats["iterations"] += 1
+        cut = float(min(max(theta[-1], -0.9), 1.0))
+        if not cut < 1.0 - 1e-12:
+            return give_up()
+        gap = float(theta[dim - 1]) - cut
+        m = 16      # the first pass sees the Ritz values of a random block: they say nothing yet
+        if stats["iterations"] > 1 and gap > 0:
+            want = min(max(10.0 * float(res[:dim].max()) / tol, 1e2), 1e5)      # damping wanted from this pass
+            m = int(np.ceil(np.log(2.0 * want) / np.arccosh(1.0 + 2.0 * gap / (1.0 + cut))))
+        m = min(max(m, 8), 64)
+        stats["degrees"].append(m)
+        if not spend(b * m):
+            return give_up()
+        # t -> (t - c) / e sends [-1, cut] to [-1, 1]; the three-term recurrence scaled so that the polynomial is 1 at t = 1
+        e, c = (cut + 1.0) / 2.0, (cut - 1.0) / 2.0
+        s1 = e / (1.0 - c)
+        sig = s1
+        stats["spmm_calls"] += m - 1
+        prims.spmm(gr, x, r, alpha=s1 / e, beta=-c * s1 / e)
+        prev, cur = x, r
+        for _ in range(2, m + 1):
+            nxt = 1.0 / (2.0 / s1 - sig)
+            prims.spmm(gr, cur, prev, alpha=2.0 * nxt / e, beta=-2.0 * nxt * c / e, gamma=-sig * nxt, z=prev)
+            prev, cur = cur, prev
+            sig = nxt
+    norms = np.sqrt(np.diag(prims.gram(x, x)))[:dim]
+    out = prims.download(x)[:, :dim] / norms[None, :]
+    for j in range(dim):
+        if out[np.argmax(np.abs(out[:, j])), j] < 0:
+            out[:, j] = -out[:, j]
+    if info is not None:
+        info.update(stats)
+    return np.ascontiguousarray(out)
+
+
+def _spectral_component(g: scipy.sparse.csr_matrix, dim: int, spectral: str = "scipy", seed: int = 0,
+                        info: Optional[Dict] = None) -> Optional[np.ndarray]:
     """spectral_layout of one connected graph: the eigenvectors 1..dim of the normalised Laplacian by the smallest eigenvalues (eigsh,
-    which="SM", v0 = ones, tol 1e-4), or None where umap falls back to a random start (eigsh fails, or too few vertices)."""
+    which="SM", v0 = ones, tol 1e-4), or None where umap falls back to a random start (eigsh fails, or too few vertices).
+    ``spectral`` = "gpu": spectral_component_gpu instead, for a graph of SPECTRAL_GPU_MIN_ROWS vertices or more."""
     from scipy.sparse.linalg import eigsh
     n = g.shape[0]
     if n < dim + 2:
         return None
+    if spectral == "gpu" and n >= SPECTRAL_GPU_MIN_ROWS:
+        sub: Dict = {}
+        out = spectral_component_gpu(g, dim, seed=seed, info=sub)
+        if info is not None:
+            for key in ("iterations", "spmm", "spmm_calls"):
+                info[key] = info.get(key, 0) + sub.get(key, 0)
+            info["gpu_components"] = info.get("gpu_components", 0) + 1
+        return out
     deg = np.asarray(g.sum(axis=0)).ravel()
     d = scipy.sparse.spdiags(1.0 / np.sqrt(deg), 0, n, n)
     lap = scipy.sparse.identity(n, format="csr") - d @ g @ d
@@ -110,20 +289,27 @@ def _spectral_component(g: scipy.sparse.csr_matrix, dim: int) -> Optional[np.nda
     return vecs[:, order]
 
 
-def spectral_init(g: scipy.sparse.csr_matrix, dim: int, rng: np.random.RandomState) -> np.ndarray:
-    """umap's spectral start.  A disconnected graph: every component is laid out on its own (spectral, or seeded uniform in [-1, 1) where
+def spectral_init(g: scipy.sparse.csr_matrix, dim: int, rng: np.random.RandomState, spectral: Optional[str] = None, seed: int = 0,
+                  info: Optional[Dict] = None) -> np.ndarray:
+    """umap's spectral start (``spectral``: None = spectral_backend("scipy"), or "gpu" / "scipy"; every component goes the same way).  A disconnected graph: every component is laid out on its own (spectral, or seeded uniform in [-1, 1) where
     umap would fall back), scaled to max |x| = 1 and centred on its own point of a grid of spacing 3 -- a simplification of umap's
     multi_component_layout, deterministic for a given seed.  Returns None for umap's global random fallback."""
     from scipy.sparse.csgraph import connected_components
+    if spectral is None:
+        spectral = spectral_backend("scipy")
+    elif spectral not in ("gpu", "scipy"):
+        raise ValueError(f"spectral must be 'gpu' or 'scipy', got {spectral!r}")
+    if info is not None:
+        info["spectral_backend"] = spectral
     n_comp, labels = connected_components(g, directed=False)
     if n_comp == 1:
-        return _spectral_component(g, dim)
+        return _spectral_component(g, dim, spectral, seed, info)
     out = np.zeros((g.shape[0], dim), dtype=np.float64)
     side = int(np.ceil(n_comp ** (1.0 / dim) - 1e-9))
     for c in range(n_comp):      # component numbers follow the lowest vertex index (connected_components' labelling)
         members = np.flatnonzero(labels == c)
         sub = g[members][:, members]
-        lay = _spectral_component(sub, dim)
+        lay = _spectral_component(sub, dim, spectral, seed, info)
         if lay is None:
             lay = rng.uniform(low=-1.0, high=1.0, size=(len(members), dim)) if len(members) > 1 else np.zeros((1, dim))
         m = np.abs(lay).max()
@@ -134,12 +320,13 @@ def spectral_init(g: scipy.sparse.csr_matrix, dim: int, rng: np.random.RandomSta
     return out
 
 
-def initial_embedding(g: scipy.sparse.csr_matrix, dim: int, seed: int) -> np.ndarray:
+def initial_embedding(g: scipy.sparse.csr_matrix, dim: int, seed: int, spectral: Optional[str] = None, info: Optional[Dict] = None) -> np.ndarray:
     """simplicial_set_embedding's start: the spectral layout scaled to max |x| = 10 plus N(0, 1e-4) noise, or uniform [-10, 10) where
-    the spectral layout is unavailable; then every column rescaled to [0, 10].  fp32."""
+    the spectral layout is unavailable; then every column rescaled to [0, 10].  fp32.  ``spectral`` as in spectral_init; ``info`` receives
+    spectral_backend and, from the GPU solver, its iterations and SpMM counts."""
     n = g.shape[0]
     rng = np.random.RandomState(seed)
-    init = spectral_init(g, dim, rng)
+    init = spectral_init(g, dim, rng, spectral, seed, info)
     if init is None:
         emb = rng.uniform(low=-10.0, high=10.0, size=(n, dim)).astype(np.float32)
     else:
@@ -151,10 +338,11 @@ def initial_embedding(g: scipy.sparse.csr_matrix, dim: int, seed: int) -> np.nda
 
 
 def umap_embed(x: np.ndarray, n_components: int = 5, n_neighbors: int = 15, seed: Optional[int] = None,
-               timings: Optional[Dict[str, float]] = None) -> np.ndarray:
+               timings: Optional[Dict[str, float]] = None, spectral: Optional[str] = None) -> np.ndarray:
     """umap.UMAP(n_components, n_neighbors).fit_transform(x) with umap-learn 0.5's defaults (euclidean, min_dist 0.1, spread 1,
     5 negative samples, learning rate 1, spectral start) -> (n, n_components) float32.  ``timings`` (optional) receives the milliseconds
-    of the stages: knn, fuzzy, graph, init, sgd."""
+    of the stages: knn, fuzzy, graph, init, sgd, and spectral_backend (with spectral_iterations, spectral_spmm and spectral_gpu_components from the GPU solver).
+    ``spectral``: who computes the spectral start -- None = spectral_backend("scipy"), or "gpu" / "scipy"."""
     import time
     seed = default_seed() if seed is None else int(seed)
     dev = _lib.require_gpu()
@@ -181,8 +369,12 @@ def umap_embed(x: np.ndarray, n_components: int = 5, n_neighbors: int = 15, seed
     a, b = find_ab_params()
     t["graph"] = (time.perf_counter() - t0) * 1e3
     t0 = time.perf_counter()
-    emb = initial_embedding(g, n_components, seed)
+    sinfo: Dict = {}
+    emb = initial_embedding(g, n_components, seed, spectral, sinfo)
     t["init"] = (time.perf_counter() - t0) * 1e3
+    t["spectral_backend"] = sinfo["spectral_backend"]
+    if "iterations" in sinfo:
+        t["spectral_iterations"], t["spectral_spmm"], t["spectral_gpu_components"] = sinfo["iterations"], sinfo["spmm"], sinfo["gpu_components"]
     t0 = time.perf_counter()
     emb_d = torch.from_numpy(emb).to(dev)
     ops.umap_optimize(emb_d, torch.from_numpy(g.indptr.astype(np.int64)).to(dev), torch.from_numpy(g.indices.astype(np.int32)).to(dev),

@@ -391,6 +391,105 @@ def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor
     return emb
 
 
+# ------------------------------------------------------------------------------------------- spectral start (csrc/spectral.hip)
+def _f64(t: torch.Tensor, cols: Optional[int] = None) -> torch.Tensor:
+    if t.dtype != torch.float64 or t.dim() != 2 or not t.is_cuda:
+        raise ValueError("the spectral primitives take 2-D float64 device tensors")
+    if cols is not None and t.shape[1] != cols:
+        raise ValueError(f"expected {cols} columns, got {t.shape[1]}")
+    return t
+
+
+def spectral_spmm(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, dinv: torch.Tensor, x: torch.Tensor,
+                  out: Optional[torch.Tensor] = None, alpha: float = 1.0, beta: float = 0.0, gamma: float = 0.0,
+                  z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (n, m) fp64 = alpha (S x) + beta x + gamma z with S = D^-1/2 A D^-1/2 of the symmetric CSR graph (int64 indptr, int32 indices, fp32
+    weights, fp64 dinv = 1 / sqrt(degree)); every row one sequential sum in CSR order (include/ribca_hip.h).  out may be z, never x."""
+    n, m = _f64(x).shape
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or weights.dtype != torch.float32 or dinv.dtype != torch.float64:
+        raise ValueError("spectral_spmm takes int64 indptr, int32 indices, float32 weights and float64 dinv")
+    if indptr.numel() != n + 1 or dinv.numel() != n or indices.numel() != weights.numel():
+        raise ValueError("spectral_spmm: the graph does not match x")
+    if out is None:
+        out = torch.empty_like(x)
+    if z is not None:
+        _f64(z, m)
+    if _f64(out, m).shape[0] != n or (z is not None and z.shape[0] != n):
+        raise ValueError("spectral_spmm: x, z and out differ in shape")
+    check(lib().ribca_spectral_spmm(ptr(indptr), ptr(indices), ptr(weights), int(indices.numel()), ptr(dinv), n, m, ptr(x), float(alpha), float(beta),
+                                    float(gamma), ptr(z), ptr(out), stream_ptr()), "ribca_spectral_spmm")
+    return out
+
+
+def spectral_gram_ws_bytes(n: int, p: int, q: int) -> int:
+    return int(lib().ribca_spectral_gram_ws_bytes(n, p, q))
+
+
+def spectral_gram(u: torch.Tensor, v: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(p, q) fp64 device tensor u^T v, summed in chunks of 1024 rows in ascending order, then over the chunks in ascending order."""
+    n, p = _f64(u).shape
+    if _f64(v).shape[0] != n:
+        raise ValueError("spectral_gram: u and v differ in rows")
+    q = v.shape[1]
+    g = torch.empty((p, q), dtype=torch.float64, device=u.device)
+    if ws is None:
+        ws = torch.empty(max(spectral_gram_ws_bytes(n, p, q), 8), dtype=torch.uint8, device=u.device)
+    check(lib().ribca_spectral_gram(ptr(u), ptr(v), n, p, q, ptr(g), ptr(ws), ws.numel(), stream_ptr()), "ribca_spectral_gram")
+    return g
+
+
+def spectral_combine(u: torch.Tensor, c: torch.Tensor, out: Optional[torch.Tensor] = None, add: bool = False) -> torch.Tensor:
+    """out (n, m) = u (n, p) c (p, m), a sequential sum over p; ``add`` starts every sum at out's own value instead of 0."""
+    n, p = _f64(u).shape
+    m = _f64(c).shape[1]
+    if c.shape[0] != p:
+        raise ValueError("spectral_combine: u and c do not match")
+    if out is None:
+        if add:
+            raise ValueError("spectral_combine: add needs out")
+        out = torch.empty((n, m), dtype=torch.float64, device=u.device)
+    if _f64(out, m).shape[0] != n:
+        raise ValueError("spectral_combine: out has the wrong shape")
+    check(lib().ribca_spectral_combine(ptr(u), n, p, ptr(c), m, 1 if add else 0, ptr(out), stream_ptr()), "ribca_spectral_combine")
+    return out
+
+
+# ------------------------------------------------------------------------------------------- scatter plot (csrc/scatter.hip)
+SCATTER_MARGIN = 0.05
+
+
+def scatter_affine(points: np.ndarray, height: int, width: int, margin: float = SCATTER_MARGIN) -> Tuple[float, float, float, float]:
+    """(ax, bx, ay, by) in fp64: column = ax x + bx sends [min x - margin span, max x + margin span] to [0, width - 1], row = ay y + by sends
+    the same range of y to [height - 1, 0] (y grows upwards, as in a plot).  A span of 0 counts as 1; non-finite rows are left out."""
+    pts = np.asarray(points, dtype=np.float64)
+    pts = pts[np.isfinite(pts).all(axis=1)]
+    if len(pts) == 0:
+        return 1.0, 0.0, -1.0, float(height - 1)
+    out = []
+    for c, size, flip in ((0, width, False), (1, height, True)):
+        lo, hi = float(pts[:, c].min()), float(pts[:, c].max())
+        span = hi - lo if hi > lo else 1.0
+        lo, hi = lo - margin * span, hi + margin * span
+        a = (size - 1) / (hi - lo)
+        out += [-a, a * hi] if flip else [a, -a * lo]
+    return tuple(out)
+
+
+def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: int, affine: Sequence[float], radius: int = 2) -> Tuple[torch.Tensor, int]:
+    """(height, width, 3) uint8 device image of the (n, 2) fp32 device points as filled discs in their (n, 3) uint8 colours on white, later
+    points over earlier ones, and the number of points skipped (centre not finite or off the canvas).  include/ribca_hip.h states the pixels."""
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 2 or rgb.dtype != torch.uint8 or rgb.shape != (points.shape[0], 3):
+        raise ValueError("scatter_raster takes (n, 2) float32 points and (n, 3) uint8 colours")
+    ax, bx, ay, by = (float(v) for v in affine)
+    out = torch.empty((int(height), int(width), 3), dtype=torch.uint8, device=points.device)
+    ws = torch.empty(max(int(lib().ribca_scatter_raster_ws_bytes(int(height), int(width))), 256), dtype=torch.uint8, device=points.device)
+    skipped = ctypes.c_int64(0)
+    n = points.shape[0]
+    check(lib().ribca_scatter_raster(ptr(points) if n else None, ptr(rgb) if n else None, n, ax, bx, ay, by, int(height), int(width), int(radius),
+                                     ptr(out), ctypes.byref(skipped), ptr(ws), ws.numel(), stream_ptr()), "ribca_scatter_raster")
+    return out, int(skipped.value)
+
+
 # ------------------------------------------------------------------------------------------- HDBSCAN (extra cell types)
 def core_distance(x: torch.Tensor, min_samples: int) -> torch.Tensor:
     """core2 (n) fp32: the min_samples-th smallest squared distance of every row of the (n, dim <= 64) fp32 device matrix x, the row itself
