@@ -324,6 +324,12 @@ BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, bool fold = false)
   return w;
 }
 // pads (tokens >= T, head dims >= hd, feature columns >= D) are never written by any kernel: zero them once per call
+// The contract (DESIGN.md section 4.1 has the table; tests/test_gpu_scratch.py pins it with junk in the workspace):
+//   must be zero when read, zeroed HERE and nowhere else (once per call, not per chunk -- so no kernel may ever write one of them):
+//     xa, zps  feature columns D .. Dp (the K pad of proj / qkv / fc1);     q, k, vt  head dims hd .. hdq (the Q K^T product runs over them);
+//     vt of a one-tile attention (imputer)  pad keys T .. KP - 1, read under P = 0;     zmx  columns D .. Kz of the three planes
+//   don't-care: the pad token rows T .. TP - 1 of q, k and row-major vt (never fetched, or masked), every row beyond the chunk's bc * T rows
+//     of every buffer, and all of part, rs, h, enc_zf / dec_zf, tok_ps, tables (written before they are read): none of them is touched here
 int zero_pads(const BlockWs& w, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(w.xa, 0, w.xa_bytes, s));
   if (w.zps) HIP_TRY(hipMemsetAsync(w.zps, 0, w.xa_bytes, s));     // same shape as xa: the K pad of the next GEMM must read as zeros

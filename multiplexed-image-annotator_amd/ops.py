@@ -281,13 +281,14 @@ def knn_compositions(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
 
 
 # ------------------------------------------------------------------------------------------- tissue regions (PCA + k-means, csrc/regions.hip)
-def region_gram(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def region_gram(counts: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Column sums (F) and Gram matrix (F, F) of the (n, F) int16 device count table, exact int64."""
     counts = counts.contiguous()
     n, f = counts.shape
     colsum = torch.empty(f, dtype=torch.int64, device=counts.device)
     gram = torch.empty((f, f), dtype=torch.int64, device=counts.device)
-    ws = torch.empty(256, dtype=torch.uint8, device=counts.device)
+    if ws is None:
+        ws = torch.empty(256, dtype=torch.uint8, device=counts.device)
     check(lib().ribca_region_gram(ptr(counts), n, f, ptr(colsum), ptr(gram), ptr(ws), ws.numel(), stream_ptr()), "ribca_region_gram")
     return colsum, gram
 
@@ -303,13 +304,15 @@ def region_project(counts: torch.Tensor, size_col: torch.Tensor, mean: torch.Ten
     return y
 
 
-def kmeans_trials(y: torch.Tensor, cand: torch.Tensor, closest: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+def kmeans_trials(y: torch.Tensor, cand: torch.Tensor, closest: Optional[torch.Tensor],
+                  ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One k-means++ step on y (n, d) fp64: (L, n) min(closest, d2 to candidate row cand[t]) and (L) potentials (fixed-order sums)."""
     n, d = y.shape
     m = int(cand.numel())
     cand_d2 = torch.empty((m, n), dtype=torch.float64, device=y.device)
     pot = torch.empty(m, dtype=torch.float64, device=y.device)
-    ws = torch.empty(max(8 * m * ((n + 1023) // 1024), 8), dtype=torch.uint8, device=y.device)
+    if ws is None:
+        ws = torch.empty(max(8 * m * ((n + 1023) // 1024), 8), dtype=torch.uint8, device=y.device)
     check(lib().ribca_kmeans_trials(ptr(y), n, d, ptr(cand), m, ptr(closest), ptr(cand_d2), ptr(pot), ptr(ws), ws.numel(), stream_ptr()),
           "ribca_kmeans_trials")
     return cand_d2, pot
@@ -380,11 +383,13 @@ def umap_optimize_ws_bytes(n: int, dim: int, nnz: int) -> int:
 
 
 def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, rev: torch.Tensor, eps: torch.Tensor, a: float, b: float,
-                  n_epochs: int, seed: int, gamma: float = 1.0, alpha0: float = 1.0, neg_rate: float = 5.0) -> torch.Tensor:
+                  n_epochs: int, seed: int, gamma: float = 1.0, alpha0: float = 1.0, neg_rate: float = 5.0,
+                  ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """n_epochs of umap's layout SGD on emb (n, dim <= 8) fp32 in place (deterministic Jacobi epochs, hashed negative samples)."""
     n, dim = emb.shape
     nnz = int(indices.numel())
-    ws = torch.empty(umap_optimize_ws_bytes(n, dim, nnz), dtype=torch.uint8, device=emb.device)
+    if ws is None:
+        ws = torch.empty(umap_optimize_ws_bytes(n, dim, nnz), dtype=torch.uint8, device=emb.device)
     check(lib().ribca_umap_optimize(ptr(emb), n, dim, ptr(indptr), ptr(indices), ptr(rev), ptr(eps), float(a), float(b), float(gamma),
                                     float(alpha0), float(neg_rate), int(n_epochs), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ws), ws.numel(),
                                     stream_ptr()), "ribca_umap_optimize")
@@ -475,14 +480,16 @@ def scatter_affine(points: np.ndarray, height: int, width: int, margin: float = 
     return tuple(out)
 
 
-def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: int, affine: Sequence[float], radius: int = 2) -> Tuple[torch.Tensor, int]:
+def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: int, affine: Sequence[float], radius: int = 2,
+                   ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, int]:
     """(height, width, 3) uint8 device image of the (n, 2) fp32 device points as filled discs in their (n, 3) uint8 colours on white, later
     points over earlier ones, and the number of points skipped (centre not finite or off the canvas).  include/ribca_hip.h states the pixels."""
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 2 or rgb.dtype != torch.uint8 or rgb.shape != (points.shape[0], 3):
         raise ValueError("scatter_raster takes (n, 2) float32 points and (n, 3) uint8 colours")
     ax, bx, ay, by = (float(v) for v in affine)
     out = torch.empty((int(height), int(width), 3), dtype=torch.uint8, device=points.device)
-    ws = torch.empty(max(int(lib().ribca_scatter_raster_ws_bytes(int(height), int(width))), 256), dtype=torch.uint8, device=points.device)
+    if ws is None:
+        ws = torch.empty(max(int(lib().ribca_scatter_raster_ws_bytes(int(height), int(width))), 256), dtype=torch.uint8, device=points.device)
     skipped = ctypes.c_int64(0)
     n = points.shape[0]
     check(lib().ribca_scatter_raster(ptr(points) if n else None, ptr(rgb) if n else None, n, ax, bx, ay, by, int(height), int(width), int(radius),
@@ -491,13 +498,14 @@ def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: 
 
 
 # ------------------------------------------------------------------------------------------- HDBSCAN (extra cell types)
-def core_distance(x: torch.Tensor, min_samples: int) -> torch.Tensor:
+def core_distance(x: torch.Tensor, min_samples: int, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """core2 (n) fp32: the min_samples-th smallest squared distance of every row of the (n, dim <= 64) fp32 device matrix x, the row itself
     counted (include/ribca_hip.h: fp32 sums of squared differences in dimension order)."""
     x = x.contiguous()
     n, dim = x.shape
     core2 = torch.empty(n, dtype=torch.float32, device=x.device)
-    ws = torch.empty(256, dtype=torch.uint8, device=x.device)
+    if ws is None:
+        ws = torch.empty(256, dtype=torch.uint8, device=x.device)
     check(lib().ribca_core_distance(ptr(x), n, dim, int(min_samples), ptr(core2), ptr(ws), ws.numel(), stream_ptr()), "ribca_core_distance")
     return core2
 
