@@ -179,7 +179,8 @@ int ribca_knn_compositions(const double* x, const double* y, const int32_t* cell
 
 /* counts (n, F) int16 = the output of ribca_knn_compositions seen as n rows of F = n_sizes * n_types columns, every count in 0 .. 255 (else an
  * error): colsum (F) int64 = column sums, gram (F, F) int64 = counts^T counts -- exact, whatever the launch geometry.  Both are overwritten.
- * ws: 256 bytes.  Synchronises the stream once (reads the range flag). */
+ * ws: ribca_region_gram_ws_bytes(n, F) bytes.  Synchronises the stream once (reads the range flag). */
+int64_t ribca_region_gram_ws_bytes(int32_t n, int32_t F);
 int ribca_region_gram(const int16_t* counts, int32_t n, int32_t F, int64_t* colsum, int64_t* gram, void* ws, int64_t ws_bytes, void* stream);
 
 /* y (n, d) fp64: y[i, j] = sum over f = 0 .. F - 1, in that order, of (counts[i, f] / size_col[f] - mean[f]) * comps[j, f]; size_col, mean (F)
@@ -189,7 +190,9 @@ int ribca_region_project(const int16_t* counts, int32_t n, int32_t F, const doub
 
 /* One k-means++ step: for each of the n_cand <= 8 candidate rows cand[t] of y (n, d) fp64, cand_d2[t, i] = min(closest[i], d2(i, cand[t]))
  * (closest NULL = no minimum yet) with d2 = the fp64 sum of squared differences in dimension order, and pot[t] = the sum of cand_d2[t, :]
- * taken as: rows of every chunk of 1024 in ascending order, then the chunks in ascending order.  ws: 8 * n_cand * ceil(n / 1024) bytes. */
+ * taken as: rows of every chunk of 1024 in ascending order, then the chunks in ascending order.  ws: ribca_kmeans_trials_ws_bytes(n, n_cand)
+ * bytes (the query sees n and n_cand only: it is 0 where they are out of range, not where d is). */
+int64_t ribca_kmeans_trials_ws_bytes(int32_t n, int32_t n_cand);
 int ribca_kmeans_trials(const double* y, int32_t n, int32_t d, const int32_t* cand, int32_t n_cand, const double* closest, double* cand_d2,
                         double* pot, void* ws, int64_t ws_bytes, void* stream);
 
@@ -232,7 +235,8 @@ int ribca_umap_fuzzy_weights(const int32_t* idx, const float* dist, int32_t n, i
  * Two deliberate deviations from umap: every epoch is a Jacobi step (each vertex sums its out-edge and negative-sample forces, then the
  * move_other terms of its in-edges, in CSR order, and all vertices move after the epoch: no atomics, bit-reproducible), and negative
  * sample p of edge e in epoch t is a counter-based hash of (seed, t, e, p) mod n.  ws: device workspace of at least
- * 2 * align256(8 nnz) + align256(4 n dim) bytes.  Synchronises the stream once (reads indptr[n]). */
+ * ribca_umap_optimize_ws_bytes(n, dim, nnz) bytes.  Synchronises the stream once (reads indptr[n]). */
+int64_t ribca_umap_optimize_ws_bytes(int32_t n, int32_t dim, int64_t nnz);
 int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
                         double a, double b, double gamma, double alpha0, double neg_rate, int32_t n_epochs, uint64_t seed, void* ws,
                         int64_t ws_bytes, void* stream);
@@ -243,16 +247,17 @@ int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indpt
  *
  * core2 (n) fp32 = the min_samples-th smallest d2(i, .) with the point itself counted (sklearn's kneighbors(X, min_samples)[:, -1], squared).
  * n >= 2, 1 <= dim <= 64, 1 <= min_samples <= n (up to 64 a sorted list in registers, above that a bisection on the bit pattern of d2 with
- * one counting pass per step: no per-row list).  ws: 256 bytes.  Synchronises the stream once; a core distance that is not finite (NaN or
- * infinite coordinates) is an error. */
+ * one counting pass per step: no per-row list).  ws: ribca_core_distance_ws_bytes(n, dim, min_samples) bytes.  Synchronises the stream once; a
+ * core distance that is not finite (NaN or infinite coordinates) is an error. */
+int64_t ribca_core_distance_ws_bytes(int32_t n, int32_t dim, int32_t min_samples);
 int ribca_core_distance(const float* x, int32_t n, int32_t dim, int32_t min_samples, float* core2, void* ws, int64_t ws_bytes, void* stream);
 
 /* The minimum spanning tree of the mutual-reachability graph, mreach2(i, j) = max(core2(i), core2(j), d2(i, j)), under the total order
  * (mreach2, min(i, j), max(i, j)) -- under it the tree is unique, so the result does not depend on the launch geometry: n - 1 edges with
  * edges_u < edges_v (int32) and edges_w = sqrt(mreach2) (fp32), in an unspecified but reproducible order.  Boruvka rounds (at most
- * ceil(log2 n)); the n x n matrix is never formed.  n >= 2, 1 <= dim <= 64.  ws: device workspace of at least
- * 256 + align256(8 n) + 9 * align256(4 n) bytes.  Synchronises the stream once per round (reads the number of components left); a negative
- * or non-finite core distance is an error. */
+ * ceil(log2 n)); the n x n matrix is never formed.  n >= 2, 1 <= dim <= 64.  ws: device workspace of at least ribca_mreach_mst_ws_bytes(n)
+ * bytes.  Synchronises the stream once per round (reads the number of components left); a negative or non-finite core distance is an error. */
+int64_t ribca_mreach_mst_ws_bytes(int32_t n);
 int ribca_mreach_mst(const float* x, int32_t n, int32_t dim, const float* core2, int32_t* edges_u, int32_t* edges_v, float* edges_w, void* ws,
                      int64_t ws_bytes, void* stream);
 

@@ -34,8 +34,10 @@ SIGNATURES = {
     "ribca_colorize": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ribca_knn_cooccurrence": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ribca_knn_compositions": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ribca_region_gram_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_region_gram": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_region_project": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ribca_kmeans_trials_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_kmeans_trials": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_kmeans_assign": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ribca_kmeans_update_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
@@ -45,9 +47,12 @@ SIGNATURES = {
     "ribca_kmeans_relocate": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "ribca_knn_dense": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "ribca_umap_fuzzy_weights": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ribca_umap_optimize_ws_bytes": (c_int64, [c_int32, c_int32, c_int64]),
     "ribca_umap_optimize": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
                                       c_double, c_int32, c_uint64, c_void_p, c_int64, c_void_p]),
+    "ribca_core_distance_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_core_distance": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_mreach_mst_ws_bytes": (c_int64, [c_int32]),
     "ribca_mreach_mst": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_spectral_spmm": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_double, c_double, c_double,
                                       c_void_p, c_void_p, c_void_p]),

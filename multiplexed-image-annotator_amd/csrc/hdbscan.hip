@@ -35,6 +35,7 @@
 
 #include "../../include/ribca_hip.h"
 #include "ribca_common.h"
+#include "ribca_scratch.h"
 #include "ribca_status.h"
 
 // every sum and product rounds on its own: the distances are the ones a plain numpy restatement computes
@@ -180,24 +181,19 @@ struct MstWs {
   float* ew;
 };
 
-inline int64_t hd_al(int64_t v) { return (v + 255) & ~(int64_t)255; }
-inline int64_t mst_ws_bytes(int n) { return hd_al(HD_CTRL_WORDS * 4) + 9 * hd_al(4 * (int64_t)n) + hd_al(8 * (int64_t)n); }
-
-MstWs carve_mst_ws(void* ws, int n) {
-  char* p = static_cast<char*>(ws);
+MstWs carve_mst_ws(Carver& c, int n) {
   MstWs w;
-  auto take = [&](int64_t bytes) { char* r = p; p += hd_al(bytes); return r; };
-  w.ctrl = reinterpret_cast<unsigned*>(take(HD_CTRL_WORDS * 4));
-  w.key1 = reinterpret_cast<unsigned long long*>(take(8 * (int64_t)n));
-  w.comp = reinterpret_cast<int*>(take(4 * (int64_t)n));
-  w.bw = reinterpret_cast<unsigned*>(take(4 * (int64_t)n));
-  w.bj = reinterpret_cast<int*>(take(4 * (int64_t)n));
-  w.key2 = reinterpret_cast<unsigned*>(take(4 * (int64_t)n));
-  w.pa = reinterpret_cast<int*>(take(4 * (int64_t)n));
-  w.pb = reinterpret_cast<int*>(take(4 * (int64_t)n));
-  w.eu = reinterpret_cast<int*>(take(4 * (int64_t)n));
-  w.ev = reinterpret_cast<int*>(take(4 * (int64_t)n));
-  w.ew = reinterpret_cast<float*>(take(4 * (int64_t)n));
+  w.ctrl = c.take<unsigned>(HD_CTRL_WORDS);
+  w.key1 = c.take<unsigned long long>(n);
+  w.comp = c.take<int>(n);
+  w.bw = c.take<unsigned>(n);
+  w.bj = c.take<int>(n);
+  w.key2 = c.take<unsigned>(n);
+  w.pa = c.take<int>(n);
+  w.pb = c.take<int>(n);
+  w.eu = c.take<int>(n);
+  w.ev = c.take<int>(n);
+  w.ew = c.take<float>(n);
   return w;
 }
 
@@ -336,12 +332,17 @@ using namespace ribca;
 
 extern "C" {
 
+int64_t ribca_core_distance_ws_bytes(int32_t n, int32_t dim, int32_t min_samples) {      // the control words
+  if (n < 2 || dim < 1 || dim > HD_DMAX || min_samples < 1 || min_samples > n) return 0;
+  return HD_CTRL_WORDS * 4;
+}
+
 int ribca_core_distance(const float* x, int32_t n, int32_t dim, int32_t min_samples, float* core2, void* ws, int64_t ws_bytes, void* stream) {
   if (!x || !core2 || !ws) return fail("ribca_core_distance: NULL buffer");
   if (n < 2) return fail("ribca_core_distance: needs n >= 2");
   if (dim < 1 || dim > HD_DMAX) return fail("ribca_core_distance: needs 1 <= dim <= 64");
   if (min_samples < 1 || min_samples > n) return fail("ribca_core_distance: needs 1 <= min_samples <= n");
-  if (ws_bytes < HD_CTRL_WORDS * 4) return fail("ribca_core_distance: workspace too small (256 bytes)");
+  if (ws_bytes < ribca_core_distance_ws_bytes(n, dim, min_samples)) return fail("ribca_core_distance: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   unsigned* ctrl = static_cast<unsigned*>(ws);
   HIP_TRY(hipMemsetAsync(ctrl, 0, HD_CTRL_WORDS * 4, s));
@@ -357,14 +358,22 @@ int ribca_core_distance(const float* x, int32_t n, int32_t dim, int32_t min_samp
   return 0;
 }
 
+int64_t ribca_mreach_mst_ws_bytes(int32_t n) {
+  if (n < 2) return 0;
+  Carver c(nullptr);
+  carve_mst_ws(c, n);
+  return (int64_t)c.off;
+}
+
 int ribca_mreach_mst(const float* x, int32_t n, int32_t dim, const float* core2, int32_t* edges_u, int32_t* edges_v, float* edges_w, void* ws,
                      int64_t ws_bytes, void* stream) {
   if (!x || !core2 || !edges_u || !edges_v || !edges_w || !ws) return fail("ribca_mreach_mst: NULL buffer");
   if (n < 2) return fail("ribca_mreach_mst: needs n >= 2");
   if (dim < 1 || dim > HD_DMAX) return fail("ribca_mreach_mst: needs 1 <= dim <= 64");
-  if (ws_bytes < mst_ws_bytes(n)) return fail("ribca_mreach_mst: workspace too small");
+  if (ws_bytes < ribca_mreach_mst_ws_bytes(n)) return fail("ribca_mreach_mst: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const MstWs w = carve_mst_ws(ws, n);
+  Carver c(ws);
+  const MstWs w = carve_mst_ws(c, n);
   const dim3 g((n + 255) / 256), b(256);
   HIP_TRY(hipMemsetAsync(w.ctrl, 0, HD_CTRL_WORDS * 4, s));
   hipLaunchKernelGGL(mst_init_kernel, g, b, 0, s, core2, n, w);

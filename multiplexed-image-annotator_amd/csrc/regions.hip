@@ -26,6 +26,7 @@
 
 #include "../../include/ribca_hip.h"
 #include "ribca_common.h"
+#include "ribca_scratch.h"
 #include "ribca_status.h"
 
 // every sum and product rounds on its own: the projections and distances are the ones a plain numpy restatement computes
@@ -34,7 +35,6 @@
 namespace ribca {
 namespace {
 
-constexpr int RG_CHUNK = 1024;        // rows per workgroup of the integer kernels, and the chunk of every fixed-order fp64 sum
 constexpr int RG_TILE = 64;           // Gram tile edge
 constexpr int RG_SUB = 64;            // rows staged in LDS at a time
 constexpr int RG_FMAX = 2032;         // 8 neighbourhood sizes x 254 cell types
@@ -46,16 +46,14 @@ constexpr int KM_THREADS = 128;
 constexpr int KM_ACC_DOUBLES = 4096;  // 32 KiB of per-chunk centre sums in LDS
 
 int fail(const char* msg) { return api_fail(msg); }
-inline int64_t rg_al(int64_t v) { return (v + 255) & ~(int64_t)255; }
-inline int rg_chunks(int n) { return (n + RG_CHUNK - 1) / RG_CHUNK; }
 
 // ------------------------------------------------------------------------------------------------------------------------------ PCA
 __global__ __launch_bounds__(256) void region_colsum_kernel(const int16_t* __restrict__ counts, int n, int F, long long* __restrict__ colsum,
                                                             unsigned* __restrict__ flag) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= F) return;
-  const int r0 = blockIdx.y * RG_CHUNK;
-  const int r1 = r0 + RG_CHUNK < n ? r0 + RG_CHUNK : n;
+  const int r0 = blockIdx.y * kSumChunk;
+  const int r1 = r0 + kSumChunk < n ? r0 + kSumChunk : n;
   int s = 0;
   bool bad = false;
   for (int r = r0; r < r1; ++r) {
@@ -76,8 +74,8 @@ __global__ __launch_bounds__(256) void region_gram_kernel(const int16_t* __restr
   while (rest >= tiles - ta) { rest -= tiles - ta; ++ta; }
   const int tb = ta + rest;
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-  const int r0 = blockIdx.y * RG_CHUNK;
-  const int r1 = r0 + RG_CHUNK < n ? r0 + RG_CHUNK : n;
+  const int r0 = blockIdx.y * kSumChunk;
+  const int r1 = r0 + kSumChunk < n ? r0 + kSumChunk : n;
   int acc[4][4];
 #pragma unroll
   for (int u = 0; u < 4; ++u)
@@ -208,24 +206,16 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_trials_kernel(const double*
     if (c < L) cand_d2[(size_t)c * n + q] = s[c] < cl ? s[c] : cl;      // numpy.minimum on finite values
 }
 
-// part[t * chunks + ch] = rows of chunk ch of candidate t added in ascending order
+// part[ch * L + t] = rows of chunk ch of candidate t added in ascending order
 __global__ __launch_bounds__(64) void kmeans_pot_chunk_kernel(const double* __restrict__ cand_d2, int n, int L, int chunks, double* __restrict__ part) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= L * chunks) return;
   const int t = i / chunks, ch = i % chunks;
-  const int r0 = ch * RG_CHUNK;
-  const int r1 = r0 + RG_CHUNK < n ? r0 + RG_CHUNK : n;
+  const int r0 = ch * kSumChunk;
+  const int r1 = r0 + kSumChunk < n ? r0 + kSumChunk : n;
   double s = 0.0;
   for (int r = r0; r < r1; ++r) s = s + cand_d2[(size_t)t * n + r];
-  part[i] = s;
-}
-
-__global__ __launch_bounds__(64) void kmeans_pot_total_kernel(const double* __restrict__ part, int L, int chunks, double* __restrict__ pot) {
-  const int t = threadIdx.x;
-  if (t >= L) return;
-  double s = 0.0;
-  for (int ch = 0; ch < chunks; ++ch) s = s + part[t * chunks + ch];
-  pot[t] = s;
+  part[ch * L + t] = s;
 }
 
 __global__ __launch_bounds__(KM_THREADS) void kmeans_assign_kernel(const double* __restrict__ y, int n, int d, const double* __restrict__ centres, int k,
@@ -262,8 +252,8 @@ __global__ __launch_bounds__(256) void kmeans_partial_kernel(const double* __res
   const int DT = blockDim.x, t = threadIdx.x;
   const int f = blockIdx.y * DT + t;
   const int ch = blockIdx.x;
-  const int r0 = ch * RG_CHUNK;
-  const int r1 = r0 + RG_CHUNK < n ? r0 + RG_CHUNK : n;
+  const int r0 = ch * kSumChunk;
+  const int r1 = r0 + kSumChunk < n ? r0 + kSumChunk : n;
   for (int c = 0; c < k; ++c) acc[c * DT + t] = 0.0;
   const bool counter = blockIdx.y == 0 && t == 0;
   if (counter)
@@ -279,21 +269,6 @@ __global__ __launch_bounds__(256) void kmeans_partial_kernel(const double* __res
   }
   if (counter)
     for (int c = 0; c < k; ++c) pcnt[(size_t)ch * k + c] = cnt[c];
-}
-
-__global__ __launch_bounds__(256) void kmeans_reduce_kernel(const double* __restrict__ psum, const int32_t* __restrict__ pcnt, int chunks, int k, int d,
-                                                            double* __restrict__ sums, int32_t* __restrict__ counts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < k * d) {
-    double s = 0.0;
-    for (int ch = 0; ch < chunks; ++ch) s = s + psum[(size_t)ch * k * d + i];
-    sums[i] = s;
-  }
-  if (i < k) {
-    int c = 0;
-    for (int ch = 0; ch < chunks; ++ch) c += pcnt[(size_t)ch * k + i];
-    counts[i] = c;
-  }
 }
 
 // one workgroup per centre.  stat: [0] labels changed, [1 .. k] counts, [1 + k .. 1 + 2 k) squared shift of every centre (all as fp64)
@@ -371,6 +346,20 @@ int km_fail(const char* name, const char* why) {
   return api_fail(buf);
 }
 
+// the workspace of ribca_kmeans_update: the per-chunk centre sums and counts of kmeans_partial_kernel
+struct KmUpdateWs {
+  double* psum;       // [chunks][k][d]
+  int32_t* pcnt;      // [chunks][k]
+};
+
+KmUpdateWs carve_kmeans_update(Carver& c, int n, int d, int k) {
+  const size_t chunks = chunks_of(n);
+  KmUpdateWs w;
+  w.psum = c.take<double>(chunks * k * d);
+  w.pcnt = c.take<int32_t>(chunks * k);
+  return w;
+}
+
 }  // namespace
 }  // namespace ribca
 
@@ -378,17 +367,19 @@ using namespace ribca;
 
 extern "C" {
 
+int64_t ribca_region_gram_ws_bytes(int32_t n, int32_t F) { return (n < 1 || F < 1 || F > RG_FMAX) ? 0 : 256; }      // the range flag
+
 int ribca_region_gram(const int16_t* counts, int32_t n, int32_t F, int64_t* colsum, int64_t* gram, void* ws, int64_t ws_bytes, void* stream) {
   if (!counts || !colsum || !gram || !ws) return fail("ribca_region_gram: NULL buffer");
   if (n < 1) return fail("ribca_region_gram: needs n >= 1");
   if (F < 1 || F > RG_FMAX) return fail("ribca_region_gram: needs 1 <= F <= 2032");
-  if (ws_bytes < 256) return fail("ribca_region_gram: workspace too small (256 bytes)");
+  if (ws_bytes < ribca_region_gram_ws_bytes(n, F)) return fail("ribca_region_gram: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   unsigned* flag = static_cast<unsigned*>(ws);
   HIP_TRY(hipMemsetAsync(flag, 0, 256, s));
   HIP_TRY(hipMemsetAsync(colsum, 0, sizeof(int64_t) * (size_t)F, s));
   HIP_TRY(hipMemsetAsync(gram, 0, sizeof(int64_t) * (size_t)F * F, s));
-  const int chunks = rg_chunks(n), tiles = (F + RG_TILE - 1) / RG_TILE;
+  const int chunks = chunks_of(n), tiles = (F + RG_TILE - 1) / RG_TILE;
   hipLaunchKernelGGL(region_colsum_kernel, dim3((F + 255) / 256, chunks), dim3(256), 0, s, counts, n, F, reinterpret_cast<long long*>(colsum), flag);
   hipLaunchKernelGGL(region_gram_kernel, dim3(tiles * (tiles + 1) / 2, chunks), dim3(256), 0, s, counts, n, F, tiles,
                      reinterpret_cast<long long*>(gram));
@@ -412,18 +403,23 @@ int ribca_region_project(const int16_t* counts, int32_t n, int32_t F, const doub
   return 0;
 }
 
+int64_t ribca_kmeans_trials_ws_bytes(int32_t n, int32_t n_cand) {      // one fp64 partial potential per (chunk, candidate)
+  if (n < 1 || n_cand < 1 || n_cand > KM_CT) return 0;
+  return (int64_t)sizeof(double) * n_cand * chunks_of(n);
+}
+
 int ribca_kmeans_trials(const double* y, int32_t n, int32_t d, const int32_t* cand, int32_t n_cand, const double* closest, double* cand_d2,
                         double* pot, void* ws, int64_t ws_bytes, void* stream) {
   if (!y || !cand || !cand_d2 || !pot || !ws) return fail("ribca_kmeans_trials: NULL buffer");
   if (const char* why = km_range(n, d, 1)) return km_fail("ribca_kmeans_trials", why);
   if (n_cand < 1 || n_cand > KM_CT) return fail("ribca_kmeans_trials: needs 1 <= n_cand <= 8");
-  const int chunks = rg_chunks(n);
-  if (ws_bytes < (int64_t)sizeof(double) * n_cand * chunks) return fail("ribca_kmeans_trials: workspace too small");
+  if (ws_bytes < ribca_kmeans_trials_ws_bytes(n, n_cand)) return fail("ribca_kmeans_trials: workspace too small");
+  const int chunks = chunks_of(n);
   hipStream_t s = (hipStream_t)stream;
   double* part = static_cast<double*>(ws);
   hipLaunchKernelGGL(kmeans_trials_kernel, dim3((n + KM_THREADS - 1) / KM_THREADS), dim3(KM_THREADS), 0, s, y, n, d, cand, n_cand, closest, cand_d2);
   hipLaunchKernelGGL(kmeans_pot_chunk_kernel, dim3((n_cand * chunks + 63) / 64), dim3(64), 0, s, cand_d2, n, n_cand, chunks, part);
-  hipLaunchKernelGGL(kmeans_pot_total_kernel, dim3(1), dim3(64), 0, s, part, n_cand, chunks, pot);
+  launch_chunk_total(part, chunks, n_cand, pot, s);
   RIBCA_FINISH();
   return 0;
 }
@@ -441,8 +437,9 @@ int ribca_kmeans_assign(const double* y, int32_t n, int32_t d, const double* cen
 
 int64_t ribca_kmeans_update_ws_bytes(int32_t n, int32_t d, int32_t k) {
   if (km_range(n, d, k)) return 0;
-  const int64_t chunks = rg_chunks(n);
-  return rg_al(8 * chunks * k * d) + rg_al(4 * chunks * k);
+  Carver c(nullptr);
+  carve_kmeans_update(c, n, d, k);
+  return (int64_t)c.off;
 }
 
 int ribca_kmeans_finalize(const double* sums, const int32_t* counts, int32_t k, int32_t d, const double* centres_old, double* centres_new,
@@ -460,12 +457,12 @@ int ribca_kmeans_update(const double* y, int32_t n, int32_t d, const int32_t* la
   if (const char* why = km_range(n, d, k)) return km_fail("ribca_kmeans_update", why);
   if (ws_bytes < ribca_kmeans_update_ws_bytes(n, d, k)) return fail("ribca_kmeans_update: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int chunks = rg_chunks(n);
-  double* psum = static_cast<double*>(ws);
-  int32_t* pcnt = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + rg_al(8 * (int64_t)chunks * k * d));
+  const int chunks = chunks_of(n);
+  Carver c(ws);
+  const KmUpdateWs w = carve_kmeans_update(c, n, d, k);
   const int dt = km_partial_threads(k);
-  hipLaunchKernelGGL(kmeans_partial_kernel, dim3(chunks, (d + dt - 1) / dt), dim3(dt), 0, s, y, n, d, labels, k, psum, pcnt);
-  hipLaunchKernelGGL(kmeans_reduce_kernel, dim3((k * d + 255) / 256), dim3(256), 0, s, psum, pcnt, chunks, k, d, sums, counts);
+  hipLaunchKernelGGL(kmeans_partial_kernel, dim3(chunks, (d + dt - 1) / dt), dim3(dt), 0, s, y, n, d, labels, k, w.psum, w.pcnt);
+  launch_chunk_total(w.psum, chunks, k * d, sums, s, w.pcnt, k, counts);
   RIBCA_FINISH();
   return ribca_kmeans_finalize(sums, counts, k, d, centres_old, centres_new, changed, stat, stream);
 }

@@ -14,6 +14,7 @@
 #include "ribca_common.h"
 #include "ribca_internal.h"
 #include "ribca_kernels.h"
+#include "ribca_scratch.h"
 #include "ribca_status.h"
 
 using namespace ribca;
@@ -25,7 +26,6 @@ int fail(const std::string& msg) { return api_fail(msg.c_str()); }
 int hip_fail(hipError_t e, const char* what) { return api_hip_fail(e, what); }
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ----------------------------------------------------------------------------------------------- profiling
 enum ProfClass { P_QKV = 0, P_PROJ, P_FC1, P_FC2, P_EMBED, P_ATTN, P_LN, P_CELL, P_HEAD, P_OTHER, P_COUNT };
@@ -159,16 +159,6 @@ struct ribca_mae {
 namespace {
 
 constexpr int kEncD = 768, kEncH = 12, kDecD = 512, kDecH = 8, kTokPix = 1600;
-
-struct Carver {
-  char* base; size_t off = 0;
-  explicit Carver(char* b) : base(b) {}
-  template <class T> T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off = align256(off + count * sizeof(T));
-    return p;
-  }
-};
 
 void layout_block(Carver& c, BlockW& L, int D, bool fold = false) {
   const int Dp = round_up(D, 32), H4 = 4 * D;
@@ -972,6 +962,8 @@ int ribca_umap_fuzzy_weights(const int32_t* idx, const float* dist, int32_t n, i
   return 0;
 }
 
+int64_t ribca_umap_optimize_ws_bytes(int32_t n, int32_t dim, int64_t nnz) { return umap_optimize_ws_bytes(n, dim, nnz); }
+
 int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
                         double a, double b, double gamma, double alpha0, double neg_rate, int32_t n_epochs, uint64_t seed, void* ws,
                         int64_t ws_bytes, void* stream) {
@@ -981,7 +973,7 @@ int ribca_umap_optimize(float* emb, int32_t n, int32_t dim, const int64_t* indpt
   HIP_TRY(hipMemcpyAsync(&nnz, indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   if (nnz < 0) return fail("ribca_umap_optimize: indptr[n] is negative");
-  if (ws_bytes < umap_optimize_ws_bytes(n, dim, nnz)) return fail("ribca_umap_optimize: workspace too small");
+  if (ws_bytes < ribca_umap_optimize_ws_bytes(n, dim, nnz)) return fail("ribca_umap_optimize: workspace too small");
   if (launch_umap_optimize(emb, n, dim, indptr, indices, rev, eps, nnz, a, b, gamma, alpha0, neg_rate, n_epochs, seed, ws, (hipStream_t)stream))
     return fail("ribca_umap_optimize: bad arguments (neg_rate must be positive)");
   RIBCA_FINISH();

@@ -177,7 +177,7 @@ int launch_knn_compositions(const double* x, const double* y, const int32_t* typ
 int launch_knn_dense(const float* x, int n, int dim, int k, int32_t* idx, float* dist, hipStream_t s);
 // umap smooth_knn_dist + compute_membership_strengths over a k-NN table; 2 <= k <= 64
 int launch_umap_fuzzy_weights(const int32_t* idx, const float* dist, int n, int k, float* sigma, float* rho, float* w, hipStream_t s);
-// bytes of workspace launch_umap_optimize carves (sampling state per edge, positions after the epoch)
+// bytes of workspace launch_umap_optimize carves (sampling state per edge, positions after the epoch); 0 for sizes it refuses
 int64_t umap_optimize_ws_bytes(int n, int dim, int64_t nnz);
 // n_epochs Jacobi epochs of umap's layout SGD (move_other) on a symmetric CSR graph; dim <= 8
 int launch_umap_optimize(float* emb, int n, int dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,

@@ -9,6 +9,7 @@
 
 #include "../../include/ribca_hip.h"
 #include "ribca_common.h"
+#include "ribca_scratch.h"
 #include "ribca_status.h"
 
 #pragma clang fp contract(off)
@@ -20,7 +21,19 @@ constexpr int SC_RMAX = 16;
 constexpr int SC_DIM_MAX = 16384;
 
 int fail(const char* msg) { return api_fail(msg); }
-inline int64_t sc_al(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+// the workspace of ribca_scatter_raster; all of it is zeroed before the kernels run
+struct ScatterWs {
+  unsigned* count;      // points skipped
+  int* index;           // (height, width): 1 + the highest point index that covers the pixel
+};
+
+ScatterWs carve_scatter(Carver& c, int height, int width) {
+  ScatterWs w;
+  w.count = c.take<unsigned>(1);
+  w.index = c.take<int>((size_t)height * width);
+  return w;
+}
 
 __global__ __launch_bounds__(256) void scatter_mark_kernel(const float* __restrict__ pts, int n, float ax, float bx, float ay, float by, int H, int W, int r,
                                                            int* __restrict__ index, unsigned* __restrict__ skipped) {
@@ -65,7 +78,9 @@ extern "C" {
 
 int64_t ribca_scatter_raster_ws_bytes(int32_t height, int32_t width) {
   if (height < 1 || height > SC_DIM_MAX || width < 1 || width > SC_DIM_MAX) return 0;
-  return 256 + sc_al((int64_t)sizeof(int32_t) * height * width);
+  Carver c(nullptr);
+  carve_scatter(c, height, width);
+  return (int64_t)c.off;
 }
 
 int ribca_scatter_raster(const float* points, const uint8_t* rgb, int32_t n, double ax, double bx, double ay, double by, int32_t height, int32_t width,
@@ -76,17 +91,17 @@ int ribca_scatter_raster(const float* points, const uint8_t* rgb, int32_t n, dou
   if (radius < 0 || radius > SC_RMAX) return fail("ribca_scatter_raster: needs 0 <= radius <= 16");
   if (ws_bytes < ribca_scatter_raster_ws_bytes(height, width)) return fail("ribca_scatter_raster: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  unsigned* count = static_cast<unsigned*>(ws);
-  int* index = reinterpret_cast<int*>(static_cast<char*>(ws) + 256);
+  Carver c(ws);
+  const ScatterWs w = carve_scatter(c, height, width);
   const long long pixels = (long long)height * width;
-  HIP_TRY(hipMemsetAsync(ws, 0, (size_t)ribca_scatter_raster_ws_bytes(height, width), s));
+  HIP_TRY(hipMemsetAsync(ws, 0, c.off, s));
   if (n > 0)
     hipLaunchKernelGGL(scatter_mark_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, s, points, n, (float)ax, (float)bx, (float)ay, (float)by, height, width,
-                       radius, index, count);
-  hipLaunchKernelGGL(scatter_paint_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, index, pixels, rgb, n, out);
+                       radius, w.index, w.count);
+  hipLaunchKernelGGL(scatter_paint_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, w.index, pixels, rgb, n, out);
   RIBCA_FINISH();
   unsigned host = 0;
-  HIP_TRY(hipMemcpyAsync(&host, count, sizeof(host), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&host, w.count, sizeof(host), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   *skipped = (int64_t)host;
   return 0;

@@ -16,6 +16,7 @@
 
 #include "../../include/ribca_hip.h"
 #include "ribca_common.h"
+#include "ribca_scratch.h"
 #include "ribca_status.h"
 
 #pragma clang fp contract(off)
@@ -23,14 +24,12 @@
 namespace ribca {
 namespace {
 
-constexpr int SP_CHUNK = 1024;      // rows per chunk of the fixed-order sums
 constexpr int SP_SUB = 16;          // rows staged in LDS at a time
 constexpr int SP_PMAX = 48;         // widest block of the Gram / combine kernels
 constexpr int SP_MMAX = 16;         // widest block of the SpMM
 constexpr int SP_OUT = (SP_PMAX * SP_PMAX + 255) / 256;      // Gram outputs per thread
 
 int fail(const char* msg) { return api_fail(msg); }
-inline int sp_chunks(int n) { return (n + SP_CHUNK - 1) / SP_CHUNK; }
 
 __global__ __launch_bounds__(256) void spectral_spmm_kernel(const long long* __restrict__ indptr, const int* __restrict__ indices,
                                                             const float* __restrict__ w, long long nnz, const double* __restrict__ dinv, int n, int m,
@@ -61,8 +60,8 @@ __global__ __launch_bounds__(256) void spectral_gram_chunk_kernel(const double* 
   __shared__ double us[SP_SUB * SP_PMAX];
   __shared__ double vs[SP_SUB * SP_PMAX];
   const int tid = threadIdx.x, pq = p * q;
-  const int r0 = blockIdx.x * SP_CHUNK;
-  const int r1 = r0 + SP_CHUNK < n ? r0 + SP_CHUNK : n;
+  const int r0 = blockIdx.x * kSumChunk;
+  const int r1 = r0 + kSumChunk < n ? r0 + kSumChunk : n;
   int ia[SP_OUT], ib[SP_OUT];
   double acc[SP_OUT];
 #pragma unroll
@@ -87,14 +86,6 @@ __global__ __launch_bounds__(256) void spectral_gram_chunk_kernel(const double* 
 #pragma unroll
   for (int k = 0; k < SP_OUT; ++k)
     if (tid + 256 * k < pq) part[(size_t)blockIdx.x * pq + tid + 256 * k] = acc[k];
-}
-
-__global__ __launch_bounds__(256) void spectral_gram_total_kernel(const double* __restrict__ part, int chunks, int pq, double* __restrict__ g) {
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= pq) return;
-  double s = 0.0;
-  for (int ch = 0; ch < chunks; ++ch) s = s + part[(size_t)ch * pq + o];
-  g[o] = s;
 }
 
 __global__ __launch_bounds__(256) void spectral_combine_kernel(const double* __restrict__ u, int n, int p, const double* __restrict__ cmat, int m, int add,
@@ -134,7 +125,7 @@ int ribca_spectral_spmm(const int64_t* indptr, const int32_t* indices, const flo
 
 int64_t ribca_spectral_gram_ws_bytes(int32_t n, int32_t p, int32_t q) {
   if (n < 1 || p < 1 || p > SP_PMAX || q < 1 || q > SP_PMAX) return 0;
-  return (int64_t)sizeof(double) * sp_chunks(n) * p * q;
+  return (int64_t)sizeof(double) * chunks_of(n) * p * q;
 }
 
 int ribca_spectral_gram(const double* u, const double* v, int32_t n, int32_t p, int32_t q, double* g, void* ws, int64_t ws_bytes, void* stream) {
@@ -143,10 +134,10 @@ int ribca_spectral_gram(const double* u, const double* v, int32_t n, int32_t p, 
   if (p < 1 || p > SP_PMAX || q < 1 || q > SP_PMAX) return fail("ribca_spectral_gram: needs 1 <= p, q <= 48");
   if (ws_bytes < ribca_spectral_gram_ws_bytes(n, p, q)) return fail("ribca_spectral_gram: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int chunks = sp_chunks(n), pq = p * q;
+  const int chunks = chunks_of(n), pq = p * q;
   double* part = static_cast<double*>(ws);
   hipLaunchKernelGGL(spectral_gram_chunk_kernel, dim3(chunks), dim3(256), 0, s, u, v, n, p, q, part);
-  hipLaunchKernelGGL(spectral_gram_total_kernel, dim3((pq + 255) / 256), dim3(256), 0, s, part, chunks, pq, g);
+  launch_chunk_total(part, chunks, pq, g, s);
   RIBCA_FINISH();
   return 0;
 }

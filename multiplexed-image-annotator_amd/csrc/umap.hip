@@ -15,6 +15,7 @@
 
 #include "ribca_common.h"
 #include "ribca_kernels.h"
+#include "ribca_scratch.h"
 
 // every sum and product below rounds on its own (HIP contracts a * b + c into an fma by default): the distances and forces are the ones
 // a plain numpy restatement computes
@@ -376,23 +377,37 @@ __global__ void umap_init_state_kernel(const double* __restrict__ eps, int64_t n
   next_neg[e] = eps[e] / neg_rate;
 }
 
+// the workspace of launch_umap_optimize: the scratch members of UmapArgs
+struct UmapWs {
+  double *next_sample, *next_neg;
+  float* new_emb;
+};
+
+UmapWs carve_umap_ws(Carver& c, int n, int dim, int64_t nnz) {
+  UmapWs w;
+  w.next_sample = c.take<double>(nnz);
+  w.next_neg = c.take<double>(nnz);
+  w.new_emb = c.take<float>((size_t)n * dim);
+  return w;
+}
+
 int64_t umap_optimize_ws_bytes(int n, int dim, int64_t nnz) {
-  auto al = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-  return 2 * al(nnz * (int64_t)sizeof(double)) + al((int64_t)n * dim * (int64_t)sizeof(float));
+  if (n < 1 || dim < 1 || dim > UMAP_DMAX || nnz < 0) return 0;
+  Carver c(nullptr);
+  carve_umap_ws(c, n, dim, nnz);
+  return (int64_t)c.off;
 }
 
 int launch_umap_optimize(float* emb, int n, int dim, const int64_t* indptr, const int32_t* indices, const int64_t* rev, const double* eps,
                          int64_t nnz, double a, double b, double gamma, double alpha0, double neg_rate, int n_epochs, uint64_t seed, void* ws,
                          hipStream_t s) {
   if (n < 1 || dim < 1 || dim > UMAP_DMAX || n_epochs < 0 || nnz < 0 || !(neg_rate > 0.0)) return 1;
-  auto al = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-  char* p = static_cast<char*>(ws);
+  Carver c(ws);
+  const UmapWs w = carve_umap_ws(c, n, dim, nnz);
   UmapArgs u;
+  u.next_sample = w.next_sample; u.next_neg = w.next_neg; u.new_emb = w.new_emb;
   u.emb = emb; u.n = n; u.dim = dim; u.indptr = indptr; u.indices = indices; u.rev = rev; u.eps = eps;
   u.a = a; u.b = b; u.gamma = gamma; u.neg_rate = neg_rate;
-  u.next_sample = reinterpret_cast<double*>(p);
-  u.next_neg = reinterpret_cast<double*>(p + al(nnz * (int64_t)sizeof(double)));
-  u.new_emb = reinterpret_cast<float*>(p + 2 * al(nnz * (int64_t)sizeof(double)));
   // host mirror of splitmix64 for the seed key
   uint64_t z = seed + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

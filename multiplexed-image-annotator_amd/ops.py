@@ -39,15 +39,7 @@ def gaussian_taps() -> np.ndarray:
     """27 fp64 weights for sigma = 1, 2, 3 (truncate 4.0), computed exactly as scipy.ndimage's
     ``_gaussian_kernel1d`` does (reference utils.py:265 -> skimage.filters.gaussian -> scipy): entry k of each
     segment is the normalised weight at distance k."""
-    out = []
-    for sigma in (1, 2, 3):
-        sd = float(sigma)
-        radius = int(4.0 * sd + 0.5)
-        x = np.arange(-radius, radius + 1)
-        phi = np.exp(-0.5 / (sd * sd) * x ** 2)
-        phi = phi / phi.sum()
-        out.append(phi[radius:])
-    taps = np.concatenate(out)
+    taps = np.concatenate([_gauss_weights(sigma) for sigma in (1, 2, 3)])
     assert taps.shape == (27,)
     return taps
 
@@ -75,6 +67,12 @@ def workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
     return cur
 
 
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    """The ``ws is None`` default of a wrapper: what the library's own ``*_ws_bytes`` query asks for.  Never empty, so that arguments the
+    library refuses (query = 0) reach its range message and not its NULL check."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
 # ------------------------------------------------------------------------------------------- pre-processing
 def mask_minmax(mask: torch.Tensor) -> Tuple[int, int]:
     assert mask.dtype == torch.int32 and mask.is_cuda
@@ -84,27 +82,39 @@ def mask_minmax(mask: torch.Tensor) -> Tuple[int, int]:
     return mx, mn
 
 
+def _label_tables(mask: torch.Tensor) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+    """The per-label reduction of an (H, W) int32 device mask, left on the device: ti (5, L) int32 = rmin, rmax, cmin, cmax, count and tu (2, L)
+    int64 = sum_r, sum_c for the labels 0 .. L - 1; None for a mask without a cell.  Negative labels are an error."""
+    assert mask.dtype == torch.int32 and mask.is_cuda and mask.dim() == 2
+    h, w = mask.shape
+    if mask.numel() == 0:
+        return None
+    mx, mn = mask_minmax(mask)
+    if mn < 0:
+        raise ValueError("segmentation mask holds negative labels; cell ids must be 1..N with 0 = background")
+    if mx <= 0:
+        return None
+    L = mx + 1
+    ti = torch.empty((5, L), dtype=torch.int32, device=mask.device)
+    tu = torch.empty((2, L), dtype=torch.int64, device=mask.device)
+    check(lib().ribca_label_table(ptr(mask), h, w, L, ptr(ti), ptr(tu), stream_ptr()), "ribca_label_table")
+    return ti, tu
+
+
+def _no_cells(device) -> Tuple[torch.Tensor, torch.Tensor]:
+    return torch.zeros(0, dtype=torch.int32, device=device), torch.zeros((0, 4), dtype=torch.int32, device=device)
+
+
 def label_table(mask: torch.Tensor, with_device: bool = False):
     """(H, W) int32 device mask -> (ids ascending int64 [n], table int64 [n, 7]: rmin, rmax, cmin, cmax, sum_r, sum_c,
     count) on the host.  The per-label reduction runs on the GPU; the host only drops absent labels.  ``with_device``: additionally the
     device-resident (ids int32 [n], bbox int32 [n, 4]) the crop consumes, so that a caller that needs the host table anyway (CSV
     centroids) does not send the id list back up."""
-    assert mask.dtype == torch.int32 and mask.is_cuda and mask.dim() == 2
-    h, w = mask.shape
-    def none():
+    tables = _label_tables(mask)
+    if tables is None:
         e = (np.zeros(0, np.int64), np.zeros((0, 7), np.int64))
-        return e + (torch.zeros(0, dtype=torch.int32, device=mask.device), torch.zeros((0, 4), dtype=torch.int32, device=mask.device)) if with_device else e
-    if mask.numel() == 0:
-        return none()
-    mx, mn = mask_minmax(mask)
-    if mn < 0:
-        raise ValueError("segmentation mask holds negative labels; cell ids must be 1..N with 0 = background")
-    if mx <= 0:
-        return none()
-    L = mx + 1
-    ti = torch.empty((5, L), dtype=torch.int32, device=mask.device)
-    tu = torch.empty((2, L), dtype=torch.int64, device=mask.device)
-    check(lib().ribca_label_table(ptr(mask), h, w, L, ptr(ti), ptr(tu), stream_ptr()), "ribca_label_table")
+        return e + _no_cells(mask.device) if with_device else e
+    ti, tu = tables
     ti_h = ti.cpu().numpy().astype(np.int64)
     tu_h = tu.cpu().numpy()
     ids = np.flatnonzero(ti_h[4] > 0)
@@ -120,20 +130,10 @@ def label_table_device(mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     what ``extract_patches`` consumes.  Only the label range (two scalars) and the cell count cross PCIe; the sharded path uses it so
     that no rank bounces the id list through numpy between the label table and the crop (reference preprocess.py:159-211 builds the
     whole dict on the host)."""
-    assert mask.dtype == torch.int32 and mask.is_cuda and mask.dim() == 2
-    h, w = mask.shape
-    empty = (torch.zeros(0, dtype=torch.int32, device=mask.device), torch.zeros((0, 4), dtype=torch.int32, device=mask.device))
-    if mask.numel() == 0:
-        return empty
-    mx, mn = mask_minmax(mask)
-    if mn < 0:
-        raise ValueError("segmentation mask holds negative labels; cell ids must be 1..N with 0 = background")
-    if mx <= 0:
-        return empty
-    L = mx + 1
-    ti = torch.empty((5, L), dtype=torch.int32, device=mask.device)
-    tu = torch.empty((2, L), dtype=torch.int64, device=mask.device)
-    check(lib().ribca_label_table(ptr(mask), h, w, L, ptr(ti), ptr(tu), stream_ptr()), "ribca_label_table")
+    tables = _label_tables(mask)
+    if tables is None:
+        return _no_cells(mask.device)
+    ti = tables[0]
     ids = torch.nonzero(ti[4] > 0).flatten()                       # ascending; the one host sync (its length)
     bbox = ti[:4].index_select(1, ids).t().contiguous()
     return ids.to(torch.int32), bbox
@@ -281,6 +281,10 @@ def knn_compositions(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
 
 
 # ------------------------------------------------------------------------------------------- tissue regions (PCA + k-means, csrc/regions.hip)
+def region_gram_ws_bytes(n: int, f: int) -> int:
+    return int(lib().ribca_region_gram_ws_bytes(n, f))
+
+
 def region_gram(counts: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Column sums (F) and Gram matrix (F, F) of the (n, F) int16 device count table, exact int64."""
     counts = counts.contiguous()
@@ -288,7 +292,7 @@ def region_gram(counts: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tupl
     colsum = torch.empty(f, dtype=torch.int64, device=counts.device)
     gram = torch.empty((f, f), dtype=torch.int64, device=counts.device)
     if ws is None:
-        ws = torch.empty(256, dtype=torch.uint8, device=counts.device)
+        ws = _scratch(region_gram_ws_bytes(n, f), counts.device)
     check(lib().ribca_region_gram(ptr(counts), n, f, ptr(colsum), ptr(gram), ptr(ws), ws.numel(), stream_ptr()), "ribca_region_gram")
     return colsum, gram
 
@@ -304,6 +308,10 @@ def region_project(counts: torch.Tensor, size_col: torch.Tensor, mean: torch.Ten
     return y
 
 
+def kmeans_trials_ws_bytes(n: int, n_cand: int) -> int:
+    return int(lib().ribca_kmeans_trials_ws_bytes(n, n_cand))
+
+
 def kmeans_trials(y: torch.Tensor, cand: torch.Tensor, closest: Optional[torch.Tensor],
                   ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One k-means++ step on y (n, d) fp64: (L, n) min(closest, d2 to candidate row cand[t]) and (L) potentials (fixed-order sums)."""
@@ -312,7 +320,7 @@ def kmeans_trials(y: torch.Tensor, cand: torch.Tensor, closest: Optional[torch.T
     cand_d2 = torch.empty((m, n), dtype=torch.float64, device=y.device)
     pot = torch.empty(m, dtype=torch.float64, device=y.device)
     if ws is None:
-        ws = torch.empty(max(8 * m * ((n + 1023) // 1024), 8), dtype=torch.uint8, device=y.device)
+        ws = _scratch(kmeans_trials_ws_bytes(n, m), y.device)
     check(lib().ribca_kmeans_trials(ptr(y), n, d, ptr(cand), m, ptr(closest), ptr(cand_d2), ptr(pot), ptr(ws), ws.numel(), stream_ptr()),
           "ribca_kmeans_trials")
     return cand_d2, pot
@@ -377,9 +385,7 @@ def umap_fuzzy_weights(idx: torch.Tensor, dist: torch.Tensor) -> Tuple[torch.Ten
 
 def umap_optimize_ws_bytes(n: int, dim: int, nnz: int) -> int:
     """workspace of umap_optimize (include/ribca_hip.h): the sampling state of every edge and the positions after an epoch"""
-    def al(v):
-        return (v + 255) // 256 * 256
-    return 2 * al(8 * nnz) + al(4 * n * dim)
+    return int(lib().ribca_umap_optimize_ws_bytes(n, dim, nnz))
 
 
 def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, rev: torch.Tensor, eps: torch.Tensor, a: float, b: float,
@@ -389,7 +395,7 @@ def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor
     n, dim = emb.shape
     nnz = int(indices.numel())
     if ws is None:
-        ws = torch.empty(umap_optimize_ws_bytes(n, dim, nnz), dtype=torch.uint8, device=emb.device)
+        ws = _scratch(umap_optimize_ws_bytes(n, dim, nnz), emb.device)
     check(lib().ribca_umap_optimize(ptr(emb), n, dim, ptr(indptr), ptr(indices), ptr(rev), ptr(eps), float(a), float(b), float(gamma),
                                     float(alpha0), float(neg_rate), int(n_epochs), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ws), ws.numel(),
                                     stream_ptr()), "ribca_umap_optimize")
@@ -438,7 +444,7 @@ def spectral_gram(u: torch.Tensor, v: torch.Tensor, ws: Optional[torch.Tensor] =
     q = v.shape[1]
     g = torch.empty((p, q), dtype=torch.float64, device=u.device)
     if ws is None:
-        ws = torch.empty(max(spectral_gram_ws_bytes(n, p, q), 8), dtype=torch.uint8, device=u.device)
+        ws = _scratch(spectral_gram_ws_bytes(n, p, q), u.device)
     check(lib().ribca_spectral_gram(ptr(u), ptr(v), n, p, q, ptr(g), ptr(ws), ws.numel(), stream_ptr()), "ribca_spectral_gram")
     return g
 
@@ -489,7 +495,7 @@ def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: 
     ax, bx, ay, by = (float(v) for v in affine)
     out = torch.empty((int(height), int(width), 3), dtype=torch.uint8, device=points.device)
     if ws is None:
-        ws = torch.empty(max(int(lib().ribca_scatter_raster_ws_bytes(int(height), int(width))), 256), dtype=torch.uint8, device=points.device)
+        ws = _scratch(lib().ribca_scatter_raster_ws_bytes(int(height), int(width)), points.device)
     skipped = ctypes.c_int64(0)
     n = points.shape[0]
     check(lib().ribca_scatter_raster(ptr(points) if n else None, ptr(rgb) if n else None, n, ax, bx, ay, by, int(height), int(width), int(radius),
@@ -498,6 +504,10 @@ def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: 
 
 
 # ------------------------------------------------------------------------------------------- HDBSCAN (extra cell types)
+def core_distance_ws_bytes(n: int, dim: int, min_samples: int) -> int:
+    return int(lib().ribca_core_distance_ws_bytes(n, dim, min_samples))
+
+
 def core_distance(x: torch.Tensor, min_samples: int, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """core2 (n) fp32: the min_samples-th smallest squared distance of every row of the (n, dim <= 64) fp32 device matrix x, the row itself
     counted (include/ribca_hip.h: fp32 sums of squared differences in dimension order)."""
@@ -505,16 +515,14 @@ def core_distance(x: torch.Tensor, min_samples: int, ws: Optional[torch.Tensor] 
     n, dim = x.shape
     core2 = torch.empty(n, dtype=torch.float32, device=x.device)
     if ws is None:
-        ws = torch.empty(256, dtype=torch.uint8, device=x.device)
+        ws = _scratch(core_distance_ws_bytes(n, dim, int(min_samples)), x.device)
     check(lib().ribca_core_distance(ptr(x), n, dim, int(min_samples), ptr(core2), ptr(ws), ws.numel(), stream_ptr()), "ribca_core_distance")
     return core2
 
 
 def mreach_mst_ws_bytes(n: int) -> int:
     """workspace of mreach_mst (include/ribca_hip.h): the control words and ten per-point / per-label arrays"""
-    def al(v):
-        return (v + 255) // 256 * 256
-    return 256 + al(8 * n) + 9 * al(4 * n)
+    return int(lib().ribca_mreach_mst_ws_bytes(n))
 
 
 def mreach_mst(x: torch.Tensor, core2: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -527,7 +535,7 @@ def mreach_mst(x: torch.Tensor, core2: torch.Tensor, ws: Optional[torch.Tensor] 
     v = torch.empty(m, dtype=torch.int32, device=x.device)
     w = torch.empty(m, dtype=torch.float32, device=x.device)
     if ws is None:
-        ws = torch.empty(mreach_mst_ws_bytes(n), dtype=torch.uint8, device=x.device)
+        ws = _scratch(mreach_mst_ws_bytes(n), x.device)
     check(lib().ribca_mreach_mst(ptr(x), n, dim, ptr(core2.contiguous()), ptr(u), ptr(v), ptr(w), ptr(ws), ws.numel(), stream_ptr()),
           "ribca_mreach_mst")
     return u, v, w

@@ -255,7 +255,7 @@ def _case_region_gram(dev, n, f):
         check(lib().ribca_region_gram(ptr(cd), n, f, ptr(colsum), ptr(gram), ptr(ws), ws.numel(), stream_ptr()), "ribca_region_gram")
         return {"colsum": colsum, "gram": gram}
 
-    return 256, direct, lambda ws: dict(zip(("colsum", "gram"), ops.region_gram(c, ws=ws)))
+    return ops.region_gram_ws_bytes(n, f), direct, lambda ws: dict(zip(("colsum", "gram"), ops.region_gram(c, ws=ws)))
 
 
 def _case_kmeans_trials(dev, n, d, n_cand, with_closest):
@@ -272,7 +272,7 @@ def _case_kmeans_trials(dev, n, d, n_cand, with_closest):
         check(lib().ribca_kmeans_trials(ptr(yd), n, d, ptr(cd), n_cand, ptr(cl), ptr(d2), ptr(pot), ptr(ws), ws.numel(), stream_ptr()), "ribca_kmeans_trials")
         return {"cand_d2": d2, "pot": pot}
 
-    return 8 * n_cand * ((n + 1023) // 1024), direct, lambda ws: dict(zip(("cand_d2", "pot"), ops.kmeans_trials(y, cand, closest, ws=ws)))
+    return ops.kmeans_trials_ws_bytes(n, n_cand), direct, lambda ws: dict(zip(("cand_d2", "pot"), ops.kmeans_trials(y, cand, closest, ws=ws)))
 
 
 def _case_kmeans_update(dev, n, d, k):
@@ -310,7 +310,7 @@ def _case_core_distance(dev, n, dim, ms):
         check(lib().ribca_core_distance(ptr(xd), n, dim, ms, ptr(core2), ptr(ws), ws.numel(), stream_ptr()), "ribca_core_distance")
         return {"core2": core2}
 
-    return 256, direct, lambda ws: {"core2": ops.core_distance(x, ms, ws=ws)}
+    return ops.core_distance_ws_bytes(n, dim, ms), direct, lambda ws: {"core2": ops.core_distance(x, ms, ws=ws)}
 
 
 def _case_mreach_mst(dev, n, dim, ms):

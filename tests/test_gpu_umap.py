@@ -124,6 +124,21 @@ def test_sgd_is_deterministic_and_seeded():
     assert not np.array_equal(r1, r3)
 
 
+def test_sgd_refuses_one_byte_less_than_its_query():
+    """the workspace check of ribca_umap_optimize is its query; it needs indptr[n] from the device, so unlike the other four it cannot be
+    asked without one.  Refused before any launch: emb keeps its bytes."""
+    dev = _lib.require_gpu()
+    n, dim, nnz = 400, 2, 1000
+    indptr = torch.linspace(0, nnz, n + 1, device=dev).to(torch.int64)
+    indices, rev = torch.zeros(nnz, dtype=torch.int32, device=dev), torch.zeros(nnz, dtype=torch.int64, device=dev)
+    eps, emb = torch.ones(nnz, dtype=torch.float64, device=dev), torch.full((n, dim), 3.0, dtype=torch.float32, device=dev)
+    need = ops.umap_optimize_ws_bytes(n, dim, nnz)
+    assert need == 2 * 8192 + 3328 and int(indptr[n]) == nnz
+    with pytest.raises(_lib.RibcaError, match="ribca_umap_optimize.*workspace"):
+        ops.umap_optimize(emb, indptr, indices, rev, eps, 1.5, 0.9, 3, 7, ws=torch.empty(need - 1, dtype=torch.uint8, device=dev))
+    assert bool((emb == 3.0).all())
+
+
 def test_umap_embed_quality_on_planted_blobs():
     from sklearn.cluster import HDBSCAN
     from sklearn.manifold import trustworthiness

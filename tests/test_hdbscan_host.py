@@ -136,8 +136,13 @@ def test_hdbscan_entry_points_refuse_bad_arguments_with_a_status():
     refused(lib.ribca_core_distance(p, 10, 3, 0, p, p, 256, None), "ribca_core_distance", "min_samples")
     refused(lib.ribca_core_distance(p, 10, 3, 11, p, p, 256, None), "ribca_core_distance", "min_samples")
     refused(lib.ribca_core_distance(p, 10, 65, 2, p, p, 256, None), "ribca_core_distance", "dim")
-    refused(lib.ribca_core_distance(p, 10, 3, 2, p, p, 255, None), "ribca_core_distance", "workspace")
+    assert lib.ribca_core_distance_ws_bytes(10, 3, 2) == 256 and lib.ribca_core_distance_ws_bytes(1025, 15, 65) == 256
+    assert lib.ribca_core_distance_ws_bytes(1, 3, 1) == 0 and lib.ribca_core_distance_ws_bytes(10, 65, 2) == 0 and lib.ribca_core_distance_ws_bytes(10, 3, 11) == 0
+    refused(lib.ribca_core_distance(p, 10, 3, 2, p, p, lib.ribca_core_distance_ws_bytes(10, 3, 2) - 1, None), "ribca_core_distance", "workspace")
     refused(lib.ribca_mreach_mst(None, 10, 3, None, None, None, None, None, 0, None), "ribca_mreach_mst", "NULL")
     refused(lib.ribca_mreach_mst(p, 1, 3, p, p, p, p, p, 4096, None), "ribca_mreach_mst", "n >= 2")
     refused(lib.ribca_mreach_mst(p, 10, 65, p, p, p, p, p, 4096, None), "ribca_mreach_mst", "dim")
-    refused(lib.ribca_mreach_mst(p, 10, 3, p, p, p, p, p, ops.mreach_mst_ws_bytes(10) - 1, None), "ribca_mreach_mst", "workspace")
+    # 256 + al(8 n) + 9 al(4 n)
+    assert lib.ribca_mreach_mst_ws_bytes(10) == 256 + 256 + 9 * 256 and lib.ribca_mreach_mst_ws_bytes(1025) == 256 + 8448 + 9 * 4352
+    assert lib.ribca_mreach_mst_ws_bytes(1) == 0 and ops.mreach_mst_ws_bytes(10) == lib.ribca_mreach_mst_ws_bytes(10)
+    refused(lib.ribca_mreach_mst(p, 10, 3, p, p, p, p, p, lib.ribca_mreach_mst_ws_bytes(10) - 1, None), "ribca_mreach_mst", "workspace")

@@ -154,3 +154,22 @@ def test_entry_points_refuse_out_of_range_requests_with_a_status():
     refused(lib.ribca_kmeans_relocate(1, 10, 4, 3, 1, 1, 1, 3, 1, 1, None), "ribca_kmeans_relocate")
     refused(lib.ribca_kmeans_finalize(None, None, 3, 4, None, None, None, None, None), "ribca_kmeans_finalize")
     assert lib.ribca_kmeans_update_ws_bytes(10, 4, 300) == 0 and lib.ribca_kmeans_update_ws_bytes(100000, 43, 5) > 0
+    # the sizes the library asks for, pinned: a layout or a chunk that moves shows here, without a GPU
+    assert lib.ribca_kmeans_update_ws_bytes(1025, 5, 7) == 768 + 256 and lib.ribca_kmeans_update_ws_bytes(10, 4, 3) == 256 + 256      # al(8 c k d) + al(4 c k)
+    assert lib.ribca_region_gram_ws_bytes(10, 8) == 256 and lib.ribca_region_gram_ws_bytes(10, 2033) == 0 and lib.ribca_region_gram_ws_bytes(0, 8) == 0
+    assert lib.ribca_kmeans_trials_ws_bytes(1025, 3) == 48 and lib.ribca_kmeans_trials_ws_bytes(1024, 8) == 64      # 8 n_cand ceil(n / 1024), not rounded
+    assert lib.ribca_kmeans_trials_ws_bytes(10, 9) == 0 and lib.ribca_kmeans_trials_ws_bytes(0, 3) == 0
+
+
+def test_one_byte_less_than_the_query_is_refused():
+    """every entry point's own check is its query: query - 1 bytes come back as "workspace too small" before any launch"""
+    from multiplexed_image_annotator_amd import _lib
+    lib = _lib.lib()
+
+    def short(status, name):
+        msg = lib.ribca_last_error()
+        assert status != 0 and name.encode() in msg and b"workspace" in msg, (name, msg)
+
+    short(lib.ribca_region_gram(1, 10, 8, 1, 1, 1, lib.ribca_region_gram_ws_bytes(10, 8) - 1, None), "ribca_region_gram")
+    short(lib.ribca_kmeans_trials(1, 1025, 4, 1, 3, None, 1, 1, 1, lib.ribca_kmeans_trials_ws_bytes(1025, 3) - 1, None), "ribca_kmeans_trials")
+    short(lib.ribca_kmeans_update(1, 1025, 5, 1, 7, 1, 1, 1, 1, None, 1, 1, lib.ribca_kmeans_update_ws_bytes(1025, 5, 7) - 1, None), "ribca_kmeans_update")

@@ -250,3 +250,7 @@ def test_new_entry_points_refuse_bad_arguments_without_a_gpu():
         assert status != 0 and text in lib.ribca_last_error(), (text, lib.ribca_last_error())
     assert lib.ribca_spectral_gram_ws_bytes(1025, 3, 5) == 8 * 2 * 15 and lib.ribca_spectral_gram_ws_bytes(10, 49, 1) == 0
     assert lib.ribca_scatter_raster_ws_bytes(9, 12) == 256 + 512 and lib.ribca_scatter_raster_ws_bytes(0, 12) == 0
+    # 2 al(8 nnz) + al(4 n dim); the refusal of one byte less needs indptr[n] from the device: tests/test_gpu_umap.py
+    assert lib.ribca_umap_optimize_ws_bytes(400, 2, 1000) == 2 * 8192 + 3328 and lib.ribca_umap_optimize_ws_bytes(1025, 5, 0) == 20736
+    assert lib.ribca_umap_optimize_ws_bytes(400, 9, 1000) == 0 and lib.ribca_umap_optimize_ws_bytes(0, 2, 1000) == 0
+    assert lib.ribca_umap_optimize_ws_bytes(400, 2, -1) == 0

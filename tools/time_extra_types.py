@@ -41,7 +41,9 @@ def main():
         t0 = time.perf_counter()
         emb = manifold.umap_embed(x, n_components=5, seed=0, timings=t)
         t["umap_total"] = (time.perf_counter() - t0) * 1e3
-        rec = {"n": len(x), "dim": args.dim, **{k + "_ms": round(v, 2) for k, v in t.items()}}
+        rec = {"n": len(x), "dim": args.dim}
+        for k, v in t.items():      # stage milliseconds; the spectral backend's name and its counts under their own names
+            rec.update({k + "_ms": round(v, 2)} if isinstance(v, float) else {k: v})
         if not args.no_hdbscan:
             from sklearn.metrics import adjusted_rand_score
             runs = []
