@@ -138,6 +138,12 @@ double ribca_vit_flops_per_cell(const ribca_vit_t* m);
 int64_t ribca_mae_blob_len(int32_t L, int32_t enc_depth, int32_t dec_depth);
 int ribca_mae_create(const float* blob, int64_t blob_len, int32_t L, int32_t enc_depth, int32_t dec_depth, void* stream,
                      ribca_mae_t** out);
+/* The same with the block path as an argument instead of the environment.  fold = 1: folded blocks (LayerNorm folded into qkv / fc1,
+ * packed-split residual stream, MX products where the width allows); fold = 0: fp32 residual stream, LayerNorm kernels, every product
+ * as three fp16 passes (the yardstick of the load-time probe and the fallback for weights it refuses).  Any other value is refused.
+ * ribca_mae_create = this with fold = 0 where RIBCA_MAE_FOLD=0 is set in the environment at that call, else 1. */
+int ribca_mae_create_path(const float* blob, int64_t blob_len, int32_t L, int32_t enc_depth, int32_t dec_depth, int32_t fold, void* stream,
+                          ribca_mae_t** out);
 void ribca_mae_destroy(ribca_mae_t* m);
 int64_t ribca_mae_workspace_bytes(const ribca_mae_t* m, int32_t chunk_cells, int32_t n_present);
 /* Replaces MarkerImputer.impute (markerImputer.py:294-329): patches (n_cells, L, 40, 40) fp32 in place -- every channel

@@ -77,6 +77,7 @@ SIGNATURES = {
     "ribca_vit_flops_per_cell": (c_double, [c_void_p]),
     "ribca_mae_blob_len": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_mae_create": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, POINTER(c_void_p)]),
+    "ribca_mae_create_path": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, POINTER(c_void_p)]),
     "ribca_mae_destroy": (None, [c_void_p]),
     "ribca_mae_workspace_bytes": (c_int64, [c_void_p, c_int32, c_int32]),
     "ribca_mae_impute": (c_int32, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p]),
@@ -159,8 +160,8 @@ class _Library:
 
 def _bind(handle, table):
     for name, (res, args) in table.items():
-        if name == "ribca_internal_table" and os.environ.get("RIBCA_LIB") and not hasattr(handle, name):
-            continue      # an A/B build of a revision older than the table (tools/build_ab_lib.py old <rev>): the package itself never calls it
+        if os.environ.get("RIBCA_LIB") and not hasattr(handle, name):
+            continue      # an A/B build of a revision older than this entry point (tools/build_ab_lib.py old <rev>): calling it raises AttributeError
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

@@ -115,27 +115,46 @@ struct BlockW {
   // the MX3 format and fc2 runs as fp16 hi * hi + two block-scaled corrections
   const uint16_t* fc2mxh = nullptr; const unsigned char* fc2mxx = nullptr;
   // attn.qkv / mlp.fc1 (gamma o W) in the MX weight image, K padded to a multiple of 128, where the residual rows are kept in MX3 as well
-  // (mx_z_on): proj and fc2 then write the new rows twice -- packed-split for the residual tile of the next proj / fc2, MX3 for these
+  // (BlockPath::mx_z): proj and fc2 then write the new rows twice -- packed-split for the residual tile of the next proj / fc2, MX3 for these
   const uint16_t *qkvmxh = nullptr, *fc1mxh = nullptr; const unsigned char *qkvmxx = nullptr, *fc1mxx = nullptr;
 };
 
-// RIBCA_MX=0: the fp16x3 kernels everywhere (A/B).  The choice depends on the model's width alone, never on the chunk: a cell's bits must
-// not depend on the size of the chunk it was computed in.
-bool mx_on(int D) {
-  static const bool on = !(getenv("RIBCA_MX") && atoi(getenv("RIBCA_MX")) == 0);
-  return on && (4 * D) % 128 == 0 && gemm_mx_supported(D, 4 * D);
+// The process switches (A/B), read from the environment once per process.  RIBCA_MX=0: the fp16x3 kernels everywhere.  RIBCA_MXZ=0: qkv / fc1
+// stay on the fp16x3 kernels.  RIBCA_CELL_ATTN=0: the unfused qkv GEMM + attention pair in place of the per-cell kernel.
+bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
+struct Switches { bool mx, mxz, cell_attn; };
+const Switches& switches() {
+  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN")};
+  return sw;
 }
+// The choice depends on the model's width alone, never on the chunk: a cell's bits must not depend on the size of the chunk it was computed in.
+bool mx_on(int D) { return switches().mx && (4 * D) % 128 == 0 && gemm_mx_supported(D, 4 * D); }
+// D % 192 == 0: proj / fc2 emit the MX3 copy from 128 x 192 tiles only, and the 32-column scale blocks need D % 96 == 0 (gemm_epi.h
+// mx3_emit_wave48); 3 D and 4 D are then multiples of 192 as well.
+bool mx_z_on(int D) { return switches().mxz && mx_on(D) && D % 192 == 0; }
 
-// RIBCA_MXZ=0: qkv / fc1 stay on the fp16x3 kernels (A/B).  D % 192 == 0: proj / fc2 emit the MX3 copy from 128 x 192 tiles only, and the
-// 32-column scale blocks need D % 96 == 0 (gemm_epi.h mx3_emit_wave48); 3 D and 4 D are then multiples of 192 as well.
-bool mx_z_on(int D) {
-  static const bool on = !(getenv("RIBCA_MXZ") && atoi(getenv("RIBCA_MXZ")) == 0);
-  return on && mx_on(D) && D % 192 == 0;
+// What a run of transformer blocks executes: computed once at create, stored in the handle, and read by the arena layout, the workspace
+// layout and the launch sequence alike -- none of them decides anything for itself.
+//   fold       LayerNorm folded into the qkv / fc1 GEMMs, packed-split residual stream (run_block_fold); else fp32 residual stream (run_block)
+//   mx_fc2     fc1 writes its GELU output in MX3 and fc2 runs on the MX kernel
+//   mx_z       the residual rows are kept in MX3 as well: qkv (where it is a GEMM of its own) and fc1 run on the MX kernel.  Implies mx_fc2
+//   cell_attn  norm1 -> qkv -> attention of a whole block in ONE per-cell kernel (cell_attention.hip; D = 144, 288, 384):
+//              13.9 -> 14.4 k cells/s in a same-box A/B (profiles/r3/ab_cell_attention.txt)
+struct BlockPath {
+  bool fold, mx_fc2, mx_z, cell_attn;
+  // ribca_vit_forward_precise: no MX product.  The fused per-cell kernel is fp16x3 and stays.  Layouts always take the handle's own path, so
+  // that both entry points share one arena and one workspace size.
+  BlockPath precise() const { return {fold, false, false, cell_attn}; }
+  // a whole block's qkv product reads the MX3 copy of the residual rows (so whatever wrote those rows must have left one)
+  bool qkv_mx3() const { return mx_z && !cell_attn; }
+};
+BlockPath block_path(const AttnGeom& a, bool fold) {
+  return {fold, fold && mx_on(a.D), fold && mx_z_on(a.D), fold && switches().cell_attn && cell_attention_supported(a.D, a.H, a.T)};
 }
 
 struct ribca_vit {
-  int D, C, K, depth, hd, hdp, hdv, Dp, H4;
-  bool fold = true;        // LayerNorm folded into the qkv / fc1 GEMMs, residual stream packed-split (RIBCA_LN_FOLD=0 at create: round-2 path)
+  int D, C, K, depth, Dp;
+  BlockPath path;
   char* arena = nullptr;
   size_t arena_bytes = 0;
   const float *cls, *pos, *pe_b, *norm_w, *norm_b, *head_w, *head_b;
@@ -147,8 +166,11 @@ struct ribca_vit {
 struct ribca_mae {
   int L, enc_depth, dec_depth;
   // round 5: the blocks run on the classifiers' folded path (LayerNorm folded into qkv / fc1, packed-split residual stream, residual tile
-  // through the operand ring; the 768-wide encoder on the MX kernel as well).  RIBCA_MAE_FOLD=0 at create: the round-2 path (A/B)
-  bool fold = true;
+  // through the operand ring; the 768-wide encoder on the MX kernel as well).  fold = 0 at create: the round-2 path (fp32 residual stream,
+  // LayerNorm kernel, fp16x3) -- the yardstick of the load-time probe and the fallback for weights it refuses.
+  // cell_attention_supported is false for the widths 768 and 512 at any token count, so neither path depends on n_present: both are fixed
+  // at create and not recomputed per call.
+  BlockPath enc_path, dec_path;
   char* arena = nullptr;
   size_t arena_bytes = 0;
   const float *cls, *pos, *pe_b, *norm_w, *norm_b, *de_b, *mask_tok, *dpos, *dnorm_w, *dnorm_b, *pred_b;
@@ -160,9 +182,9 @@ namespace {
 
 constexpr int kEncD = 768, kEncH = 12, kDecD = 512, kDecH = 8, kTokPix = 1600;
 
-void layout_block(Carver& c, BlockW& L, int D, bool fold = false) {
+void layout_block(Carver& c, BlockW& L, int D, const BlockPath& p) {
   const int Dp = round_up(D, 32), H4 = 4 * D;
-  if (fold) {
+  if (p.fold) {
     L.qkvc = c.take<float>(3 * D); L.qkvb2 = c.take<float>(3 * D);
     L.fc1c = c.take<float>(4 * D); L.fc1b2 = c.take<float>(4 * D);
   }
@@ -171,18 +193,18 @@ void layout_block(Carver& c, BlockW& L, int D, bool fold = false) {
   L.ln2w = c.take<float>(D); L.ln2b = c.take<float>(D);
   L.fc1b = c.take<float>(4 * D); L.fc2b = c.take<float>(D);
   L.qkvw = c.take<uint16_t>((size_t)gemm_padded_n(3 * D) * 2 * Dp);
-  if (fold) L.qkvwf = c.take<uint16_t>((size_t)gemm_padded_n(3 * D) * 2 * Dp);
+  if (p.fold) L.qkvwf = c.take<uint16_t>((size_t)gemm_padded_n(3 * D) * 2 * Dp);
   L.projw = c.take<uint16_t>((size_t)gemm_padded_n(D) * 2 * Dp);
-  if (fold) L.projwf = c.take<uint16_t>((size_t)gemm_padded_n(D) * 2 * Dp);
+  if (p.fold) L.projwf = c.take<uint16_t>((size_t)gemm_padded_n(D) * 2 * Dp);
   L.fc1w = c.take<uint16_t>((size_t)gemm_padded_n(4 * D) * 2 * Dp);
   L.fc1wf = c.take<uint16_t>((size_t)gemm_padded_n(4 * D) * 2 * Dp);
   L.fc2w = c.take<uint16_t>((size_t)gemm_padded_n(D) * 2 * H4);
-  if (fold) L.fc2wf = c.take<uint16_t>((size_t)gemm_padded_n(D) * 2 * H4);
-  if (fold && mx_on(D)) {
+  if (p.fold) L.fc2wf = c.take<uint16_t>((size_t)gemm_padded_n(D) * 2 * H4);
+  if (p.mx_fc2) {
     L.fc2mxh = c.take<uint16_t>(mx_wh_bytes(round_up(D, 16), H4) / 2);
     L.fc2mxx = c.take<unsigned char>(mx_wx_bytes(round_up(D, 16), H4));
   }
-  if (fold && mx_z_on(D)) {
+  if (p.mx_z) {
     const int Kz = round_up(D, 128);
     L.qkvmxh = c.take<uint16_t>(mx_wh_bytes(3 * D, Kz) / 2); L.qkvmxx = c.take<unsigned char>(mx_wx_bytes(3 * D, Kz));
     L.fc1mxh = c.take<uint16_t>(mx_wh_bytes(4 * D, Kz) / 2); L.fc1mxx = c.take<unsigned char>(mx_wx_bytes(4 * D, Kz));
@@ -198,7 +220,7 @@ size_t layout(ribca_vit* m, char* base) {
   m->pe_b = c.take<float>(D);
   m->pe_w = c.take<float>((size_t)D * 16 * m->C);
   m->layers.resize(m->depth);
-  for (auto& L : m->layers) layout_block(c, L, D, m->fold);
+  for (auto& L : m->layers) layout_block(c, L, D, m->path);
   m->norm_w = c.take<float>(D); m->norm_b = c.take<float>(D);
   m->head_w = c.take<float>((size_t)m->K * D); m->head_b = c.take<float>(m->K);
   return c.off;
@@ -211,14 +233,14 @@ size_t layout_mae(ribca_mae* m, char* base) {
   m->pe_w = c.take<uint16_t>((size_t)gemm_padded_n(kEncD) * 2 * kTokPix);
   m->pe_b = c.take<float>(kEncD);
   m->enc.resize(m->enc_depth);
-  for (auto& L : m->enc) layout_block(c, L, kEncD, m->fold);
+  for (auto& L : m->enc) layout_block(c, L, kEncD, m->enc_path);
   m->norm_w = c.take<float>(kEncD); m->norm_b = c.take<float>(kEncD);
   m->de_w = c.take<uint16_t>((size_t)gemm_padded_n(kDecD) * 2 * kEncD);
   m->de_b = c.take<float>(kDecD);
   m->mask_tok = c.take<float>(kDecD);
   m->dpos = c.take<float>((size_t)(m->L + 1) * kDecD);
   m->dec.resize(m->dec_depth);
-  for (auto& L : m->dec) layout_block(c, L, kDecD, m->fold);
+  for (auto& L : m->dec) layout_block(c, L, kDecD, m->dec_path);
   m->dnorm_w = c.take<float>(kDecD); m->dnorm_b = c.take<float>(kDecD);
   m->pred_w = c.take<uint16_t>((size_t)gemm_padded_n(kTokPix) * 2 * kDecD);
   m->pred_b = c.take<float>(kTokPix);
@@ -243,25 +265,25 @@ struct BlobReader {
                             const_cast<float*>(bias2), s);
     p += (size_t)N * K;
   }
-  void block(const BlockW& L, int D, bool fold = false) {
+  void block(const BlockW& L, int D, const BlockPath& path) {
     const int Dp = round_up(D, 32);
     copy(L.ln1w, D); copy(L.ln1b, D);
-    if (fold) {
+    if (path.fold) {
       pack_fold(L.qkvw, 3 * D, D, Dp, L.ln1w, L.ln1b, L.qkvc, L.qkvb2);
       launch_pack_wf(L.qkvw, 2 * Dp, gemm_padded_n(3 * D), Dp, const_cast<uint16_t*>(L.qkvwf), s);
     } else pack(L.qkvw, 3 * D, D, Dp);
     copy(L.qkvb, 3 * D);
     pack(L.projw, D, D, Dp); copy(L.projb, D);
-    if (fold) launch_pack_wf(L.projw, 2 * Dp, gemm_padded_n(D), Dp, const_cast<uint16_t*>(L.projwf), s);
+    if (path.fold) launch_pack_wf(L.projw, 2 * Dp, gemm_padded_n(D), Dp, const_cast<uint16_t*>(L.projwf), s);
     copy(L.ln2w, D); copy(L.ln2b, D);
-    if (fold) pack_fold(L.fc1w, 4 * D, D, Dp, L.ln2w, L.ln2b, L.fc1c, L.fc1b2);
+    if (path.fold) pack_fold(L.fc1w, 4 * D, D, Dp, L.ln2w, L.ln2b, L.fc1c, L.fc1b2);
     else pack(L.fc1w, 4 * D, D, Dp);
     copy(L.fc1b, 4 * D);
     launch_pack_wf(L.fc1w, 2 * Dp, gemm_padded_n(4 * D), Dp, const_cast<uint16_t*>(L.fc1wf), s);
     pack(L.fc2w, D, 4 * D, 4 * D); copy(L.fc2b, D);
-    if (fold) launch_pack_wf(L.fc2w, 2 * 4 * D, gemm_padded_n(D), 4 * D, const_cast<uint16_t*>(L.fc2wf), s);
-    if (L.fc2mxh) launch_mx_pack_w(L.fc2w, 2 * 4 * D, round_up(D, 16), 4 * D, 4 * D, const_cast<uint16_t*>(L.fc2mxh), const_cast<unsigned char*>(L.fc2mxx), s);
-    if (L.qkvmxh) {
+    if (path.fold) launch_pack_wf(L.fc2w, 2 * 4 * D, gemm_padded_n(D), 4 * D, const_cast<uint16_t*>(L.fc2wf), s);
+    if (path.mx_fc2) launch_mx_pack_w(L.fc2w, 2 * 4 * D, round_up(D, 16), 4 * D, 4 * D, const_cast<uint16_t*>(L.fc2mxh), const_cast<unsigned char*>(L.fc2mxx), s);
+    if (path.mx_z) {
       const int Kz = round_up(D, 128);
       launch_mx_pack_w(L.qkvw, 2 * Dp, 3 * D, Dp, Kz, const_cast<uint16_t*>(L.qkvmxh), const_cast<unsigned char*>(L.qkvmxx), s);
       launch_mx_pack_w(L.fc1w, 2 * Dp, 4 * D, Dp, Kz, const_cast<uint16_t*>(L.fc1mxh), const_cast<unsigned char*>(L.fc1mxx), s);
@@ -277,20 +299,20 @@ struct BlockWs {
   // folded-LayerNorm blocks: residual stream packed-split [rows][2 * Dp], per-tile row statistics of the last residual GEMM and
   // the (rstd, -mean rstd) pairs the next qkv / fc1 epilogue reads
   uint16_t* zps = nullptr; float2* part = nullptr; float2* rs = nullptr;
-  // the residual rows again in MX3 (mx_z_on; Kp = D rounded up to 128, M set per chunk by the caller) and the bytes of its planes
+  // the residual rows again in MX3 (BlockPath::mx_z; Kp = D rounded up to 128, M set per chunk by the caller) and the bytes of its planes
   MxAct zmx = MxAct{nullptr, nullptr, nullptr, 0, 0};
   size_t zmx_rows = 0;
 };
-BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, bool fold = false) {
+BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, const BlockPath& p) {
   BlockWs w;
   const size_t Mc = (size_t)cells * a.T;
   const int Dp = round_up(a.D, 32);
-  if (fold) {
+  if (p.fold) {
     w.z = nullptr;
     w.zps = c.take<uint16_t>(Mc * 2 * Dp);
     w.part = c.take<float2>(Mc * gemm_resid_part_rows(a.D));
     w.rs = c.take<float2>(Mc);
-    if (mx_z_on(a.D)) {
+    if (p.mx_z) {
       const int Kz = round_up(a.D, 128);
       w.zmx.hi = c.take<uint16_t>(Mc * Kz);
       w.zmx.l8 = c.take<unsigned char>(Mc * Kz);
@@ -320,20 +342,21 @@ BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, bool fold = false)
 //     vt of a one-tile attention (imputer)  pad keys T .. KP - 1, read under P = 0;     zmx  columns D .. Kz of the three planes
 //   don't-care: the pad token rows T .. TP - 1 of q, k and row-major vt (never fetched, or masked), every row beyond the chunk's bc * T rows
 //     of every buffer, and all of part, rs, h, enc_zf / dec_zf, tok_ps, tables (written before they are read): none of them is touched here
-int zero_pads(const BlockWs& w, hipStream_t s) {
+int zero_pads(const BlockWs& w, const BlockPath& p, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(w.xa, 0, w.xa_bytes, s));
-  if (w.zps) HIP_TRY(hipMemsetAsync(w.zps, 0, w.xa_bytes, s));     // same shape as xa: the K pad of the next GEMM must read as zeros
+  if (p.fold) HIP_TRY(hipMemsetAsync(w.zps, 0, w.xa_bytes, s));     // same shape as xa: the K pad of the next GEMM must read as zeros
   HIP_TRY(hipMemsetAsync(w.q, 0, w.qk_bytes, s));
   HIP_TRY(hipMemsetAsync(w.k, 0, w.qk_bytes, s));
   HIP_TRY(hipMemsetAsync(w.vt, 0, w.vt_bytes, s));
-  if (w.zmx.hi) {      // the K pad of the MX3 residual rows (D = 576: columns 576 .. 639) is never written either; scale byte 0 = 2^-127
+  if (p.mx_z) {      // the K pad of the MX3 residual rows (D = 576: columns 576 .. 639) is never written either; scale byte 0 = 2^-127
     HIP_TRY(hipMemsetAsync(w.zmx.hi, 0, w.zmx_rows * w.zmx.Kp * 2, s));
     HIP_TRY(hipMemsetAsync(w.zmx.l8, 0, w.zmx_rows * w.zmx.Kp, s));
     HIP_TRY(hipMemsetAsync(w.zmx.sc, 0, w.zmx_rows * (w.zmx.Kp / 32), s));
   }
   return 0;
 }
-// one pre-LN block on z (cells*T rows): z += proj(attn(LN1 z)); z += fc2(gelu(fc1(LN2 z)))
+// one pre-LN block on z (cells*T rows): z += proj(attn(LN1 z)); z += fc2(gelu(fc1(LN2 z))).  The unfolded runner (!BlockPath::fold): fp32
+// residual stream, LayerNorm kernels, fp16x3 GEMMs.  Only the imputer's fallback path runs it.
 void run_block(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, hipStream_t s) {
   const int D = a.D, Dp = round_up(D, 32), ld_x = 2 * Dp, ld_h = 2 * 4 * D, Mc = cells * a.T;
   const float scale = 1.0f / sqrtf((float)a.hd);
@@ -362,38 +385,6 @@ void run_block(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, 
   }
 }
 
-// Last block of a classifier: only the CLS row reaches the head (reference model.py:61-62 takes x[:, 0] after the final norm),
-// so after the attention (which still needs every token's K and V) the projection, the MLP and both residual updates run
-// on the CLS rows only: they are addressed in place with a row stride of T rows (M = cells).  Same values as the full block
-// on those rows; the other 100 rows of the last block are never read again.
-void run_last_block_cls(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, hipStream_t s) {
-  const int D = a.D, Dp = round_up(D, 32), ld_x = 2 * Dp, ld_h = 2 * 4 * D, Mc = cells * a.T;
-  const float scale = 1.0f / sqrtf((float)a.hd);
-  { ProfScope ps(P_LN, s); launch_layernorm_ps(w.z, D, L.ln1w, L.ln1b, w.xa, ld_x, Mc, D, s); }
-  {
-    ProfScope ps(P_QKV, s);
-    GemmArgs g{w.xa, ld_x, L.qkvw, ld_x, Mc, 3 * D, Dp, L.qkvb};
-    launch_gemm_qkv(g, w.q, w.k, w.vt, a, scale, s);
-  }
-  { ProfScope ps(P_ATTN, s); launch_attention(w.q, w.k, w.vt, w.xa, ld_x, cells, a, s, 1); }
-  {
-    ProfScope ps(P_PROJ, s);
-    GemmArgs g{w.xa, a.T * ld_x, L.projw, ld_x, cells, D, Dp, L.projb};
-    launch_gemm_resid(g, w.z, a.T * D, s);
-  }
-  { ProfScope ps(P_LN, s); launch_layernorm_ps(w.z, a.T * D, L.ln2w, L.ln2b, w.xa, a.T * ld_x, cells, D, s); }
-  {
-    ProfScope ps(P_FC1, s);
-    GemmArgs g{w.xa, a.T * ld_x, L.fc1w, ld_x, cells, 4 * D, Dp, L.fc1b};
-    launch_gemm_gelu(g, w.h, ld_h, s);
-  }
-  {
-    ProfScope ps(P_FC2, s);
-    GemmArgs g{w.h, ld_h, L.fc2w, ld_h, cells, D, 4 * D, L.fc2b};
-    launch_gemm_resid(g, w.z, a.T * D, s);
-  }
-}
-
 // ---- the classifiers' blocks with LayerNorm folded into the GEMM behind it (gemm_epi.h).  Five launches + two finalisers per block
 // instead of seven + no LayerNorm pass over the rows: qkv and fc1 read the packed-split residual stream itself, the residual GEMMs
 // (proj, fc2) update it in place and leave the row statistics of the NEW rows behind.
@@ -403,28 +394,21 @@ void resid_ps_and_stats(const GemmArgs& g, const BlockWs& w, int ldz_rows, int D
   const ResidStatGeom sg = launch_gemm_resid_ps(g, w.zps, ldz_rows, want_stats ? w.part : nullptr, w.rs, prev_stride, s);
   if (want_stats) launch_ln_finalize(w.part, sg.tiles, g.M, sg.bn, D, w.rs, s);
 }
-// norm1 -> qkv -> attention of a whole block in ONE per-cell kernel (cell_attention.hip) where the geometry allows (D = 144, 288, 384):
-// 13.9 -> 14.4 k cells/s in a same-box A/B (profiles/r3/ab_cell_attention.txt).  RIBCA_CELL_ATTN=0: the unfused pair, for A/B.
-bool cell_attn_on(const AttnGeom& a) {
-  static const int v = getenv("RIBCA_CELL_ATTN") ? atoi(getenv("RIBCA_CELL_ATTN")) : 1;
-  return v != 0 && cell_attention_supported(a.D, a.H, a.T);
-}
-// next_full: the block after this one is a full block too (its qkv reads what this block's fc2 writes)
-void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, hipStream_t s, bool precise = false, bool next_full = true) {
+// One whole block on path p (the handle's, or its precise() form).  next_mx3: the block after this one is a whole block whose qkv product reads
+// the MX3 copy of the rows this block's fc2 writes (p.qkv_mx3() and not in front of the last block) -- the one thing p cannot know.
+void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, const BlockPath& p, bool next_mx3, hipStream_t s) {
   const int D = a.D, Dp = round_up(D, 32), ld_x = 2 * Dp, ld_h = 2 * 4 * D, Mc = cells * a.T;
   const float scale = 1.0f / sqrtf((float)a.hd);
   // the residual rows in MX3 beside the packed-split ones: qkv (where it is a GEMM of its own) and fc1 run on the MX kernel
-  const bool mz = w.zmx.hi != nullptr && L.fc1mxh != nullptr && !precise;
   MxAct zmx = w.zmx;
   zmx.M = Mc;
-  const bool fused_attn = cell_attn_on(a);
-  if (fused_attn) {
+  if (p.cell_attn) {
     ProfScope ps(P_CELL, s);
     launch_cell_qkv_attention(w.zps, ld_x, L.qkvw, ld_x, L.qkvb2, L.qkvc, w.rs, w.xa, ld_x, cells, D, scale, s);
   } else {
     {
       ProfScope ps(P_QKV, s);
-      if (mz) {
+      if (p.mx_z) {
         launch_gemm_mx_qkv_ln(zmx, MxWeight{L.qkvmxh, L.qkvmxx}, Mc, 3 * D, L.qkvb2, w.rs, L.qkvc, w.q, w.k, w.vt, a, scale, s);
       } else {
         GemmArgs g{w.zps, ld_x, L.qkvw, ld_x, Mc, 3 * D, Dp, L.qkvb2, L.qkvwf};
@@ -436,21 +420,21 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
   {
     ProfScope ps(P_PROJ, s);
     GemmArgs g{w.xa, ld_x, L.projw, ld_x, Mc, D, Dp, L.projb, L.projwf};
-    if (mz) {
+    if (p.mx_z) {
       const ResidStatGeom sg = launch_gemm_resid_ps(g, w.zps, ld_x, w.part, w.rs, 1, s, false, &zmx);
       launch_ln_finalize(w.part, sg.tiles, Mc, sg.bn, D, w.rs, s);
     } else {
       resid_ps_and_stats(g, w, ld_x, D, true, 1, s);
     }
   }
-  if (L.fc2mxh != nullptr && !precise) {
+  if (p.mx_fc2) {
     // the MX pair: fc1's GELU epilogue emits the three-plane operand (3 bytes per element, carved out of the h buffer), fc2 multiplies it
     // as fp16 hi * hi + two block-scaled corrections (gemm_mx.hip)
     const size_t hn = (size_t)Mc * 4 * D;
     const MxAct hmx{w.h, reinterpret_cast<unsigned char*>(w.h + hn), reinterpret_cast<unsigned char*>(w.h + hn) + hn, 4 * D, Mc};
     {
       ProfScope ps(P_FC1, s);
-      if (mz) {
+      if (p.mx_z) {
         launch_gemm_mx_gelu(zmx, MxWeight{L.fc1mxh, L.fc1mxx}, Mc, 4 * D, L.fc1b2, w.rs, L.fc1c, hmx, s);
       } else {
         GemmArgs g{w.zps, ld_x, L.fc1w, ld_x, Mc, 4 * D, Dp, L.fc1b2, L.fc1wf};
@@ -461,8 +445,7 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
       ProfScope ps(P_FC2, s);
       // (the MX3 copy of the new rows is read by the next block's qkv GEMM: not wanted where that runs inside the fused per-cell kernel, which
       // reads the packed-split rows, nor in front of the last block)
-      const bool emit = mz && !fused_attn && next_full;
-      const ResidStatGeom sg = launch_gemm_mx_resid(hmx, MxWeight{L.fc2mxh, L.fc2mxx}, Mc, D, L.fc2b, w.zps, ld_x, w.part, w.rs, 1, s, emit ? &zmx : nullptr);
+      const ResidStatGeom sg = launch_gemm_mx_resid(hmx, MxWeight{L.fc2mxh, L.fc2mxx}, Mc, D, L.fc2b, w.zps, ld_x, w.part, w.rs, 1, s, next_mx3 ? &zmx : nullptr);
       launch_ln_finalize(w.part, sg.tiles, Mc, sg.bn, D, w.rs, s);
     }
     return;
@@ -478,8 +461,12 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
     resid_ps_and_stats(g, w, ld_x, D, true, 1, s);
   }
 }
-// last block, CLS rows only behind the attention (see run_last_block_cls): GEMM row m = cell, addressed with a row stride of T rows;
-// the statistics of norm2 are indexed by GEMM row too.  Nothing reads statistics after the last fc2 (the head normalises itself).
+// Last block of a classifier: only the CLS row reaches the head (reference model.py:61-62 takes x[:, 0] after the final norm),
+// so after the attention (which still needs every token's K and V) the projection, the MLP and both residual updates run
+// on the CLS rows only: GEMM row m = cell, addressed in place with a row stride of T rows; the statistics of norm2 are indexed by GEMM
+// row too.  Same values as the full block on those rows; the other 100 rows of the last block are never read again.  Nothing reads
+// statistics after the last fc2 (the head normalises itself).
+// It has no MX form and takes no path: it is identical under ribca_vit_forward and ribca_vit_forward_precise.
 void run_last_block_cls_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, hipStream_t s) {
   const int D = a.D, Dp = round_up(D, 32), ld_x = 2 * Dp, ld_h = 2 * 4 * D, Mc = cells * a.T;
   const float scale = 1.0f / sqrtf((float)a.hd);
@@ -515,7 +502,7 @@ void run_last_block_cls_fold(const BlockW& L, const BlockWs& w, int cells, const
 
 extern "C" {
 
-int ribca_version(void) { return 100; }
+int ribca_version(void) { return 101; }
 const char* ribca_last_error(void) { return api_last_error(); }
 
 // the launcher table of libribca_hip_test.so (csrc/ribca_internal.h): the only way into the library besides the C entry points
@@ -536,8 +523,7 @@ int32_t ribca_mxz_enabled(int32_t D) { return mx_z_on(D) ? 1 : 0; }
 
 int64_t ribca_vit_blob_len(int32_t D, int32_t C, int32_t K, int32_t depth) {
   const int64_t d = D;
-  return d + (int64_t)kTokens * d + d * C * 16 + d + (int64_t)depth * (2 * d + 3 * d * d + 3 * d + d * d + d + 2 * d + 4 * d * d + 4 * d + 4 * d * d + d) +
-         2 * d + (int64_t)K * d + K;
+  return d + (int64_t)kTokens * d + d * C * 16 + d + (int64_t)depth * block_params(d) + 2 * d + (int64_t)K * d + K;
 }
 
 int ribca_vit_create(const float* blob, int64_t blob_len, int32_t D, int32_t C, int32_t K, int32_t depth, void* stream, ribca_vit_t** out) {
@@ -550,12 +536,8 @@ int ribca_vit_create(const float* blob, int64_t blob_len, int32_t D, int32_t C, 
   hipStream_t s = (hipStream_t)stream;
   ribca_vit* m = new ribca_vit();
   m->D = D; m->C = C; m->K = K; m->depth = depth;
-  m->hd = D / kHeads;
-  m->hdp = round_up(m->hd, 32);
-  m->hdv = round_up(m->hd, 16);
   m->Dp = round_up(D, 32);
-  m->H4 = 4 * D;  // multiple of 32 because D % 8 == 0
-  m->fold = !(getenv("RIBCA_LN_FOLD") && atoi(getenv("RIBCA_LN_FOLD")) == 0);
+  m->path = block_path(make_attn_geom(D, kHeads, kTokens), true);
   m->arena_bytes = layout(m, nullptr);
   hipError_t e = hipMalloc((void**)&m->arena, m->arena_bytes);
   if (e != hipSuccess) { delete m; return hip_fail(e, "hipMalloc(weights)"); }
@@ -565,7 +547,7 @@ int ribca_vit_create(const float* blob, int64_t blob_len, int32_t D, int32_t C, 
   r.copy(m->pos, (size_t)kTokens * D);
   r.copy(m->pe_w, (size_t)D * 16 * C);
   r.copy(m->pe_b, D);
-  for (auto& L : m->layers) r.block(L, D, m->fold);
+  for (auto& L : m->layers) r.block(L, D, m->path);
   r.copy(m->norm_w, D); r.copy(m->norm_b, D);
   r.copy(m->head_w, (size_t)K * D); r.copy(m->head_b, K);
   e = r.err != hipSuccess ? r.err : hipGetLastError();
@@ -590,23 +572,13 @@ double ribca_vit_flops_per_cell(const ribca_vit_t* m) {
 int64_t ribca_vit_workspace_bytes(const ribca_vit_t* m, int32_t chunk_cells) {
   if (!m || chunk_cells <= 0) return 0;
   Carver c(nullptr);
-  carve_blocks(c, chunk_cells, make_attn_geom(m->D, kHeads, kTokens), m->fold);
+  carve_blocks(c, chunk_cells, make_attn_geom(m->D, kHeads, kTokens), m->path);
   return (int64_t)c.off;
 }
 
-static int vit_forward_impl(const ribca_vit_t* m, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells, float* probs,
-                            void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream, bool precise);
-int ribca_vit_forward(const ribca_vit_t* m, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells, float* probs,
-                      void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream) {
-  return vit_forward_impl(m, patches, c_img, src_chan, n_cells, probs, workspace, workspace_bytes, chunk_cells, stream, false);
-}
-int ribca_vit_forward_precise(const ribca_vit_t* m, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells, float* probs,
-                              void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream) {
-  return vit_forward_impl(m, patches, c_img, src_chan, n_cells, probs, workspace, workspace_bytes, chunk_cells, stream, true);
-}
-static int vit_forward_impl(const ribca_vit_t* m, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells, float* probs,
-                            void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream, bool precise) {
-  if (!m) return fail("ribca_vit_forward: model is NULL");
+// path: the handle's own, or its precise() form -- the workspace is laid out for the handle's path under both
+static int vit_forward_impl(const ribca_vit_t* m, const BlockPath& path, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells,
+                            float* probs, void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream) {
   if (n_cells < 0 || chunk_cells <= 0) return fail("ribca_vit_forward: bad cell counts");
   if (n_cells == 0) return 0;
   if (!patches || !src_chan || !probs || !workspace) return fail("ribca_vit_forward: NULL buffer");
@@ -614,58 +586,51 @@ static int vit_forward_impl(const ribca_vit_t* m, const float* patches, int32_t 
   if (((uintptr_t)workspace & 255) != 0) return fail("ribca_vit_forward: workspace must be 256-byte aligned");
   const AttnGeom geom = make_attn_geom(m->D, kHeads, kTokens);
   Carver c((char*)workspace);
-  const BlockWs w = carve_blocks(c, chunk_cells, geom, m->fold);
+  const BlockWs w = carve_blocks(c, chunk_cells, geom, m->path);
   if ((int64_t)c.off > workspace_bytes) return fail("ribca_vit_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int D = m->D;
+  const int D = m->D, ld_z = 2 * m->Dp;
+  const size_t n_whole = m->layers.size() - 1;      // whole blocks in front of the CLS-only last one
   {
     ProfScope ps(P_OTHER, s);
-    if (zero_pads(w, s)) return 1;
+    if (zero_pads(w, m->path, s)) return 1;
   }
   for (int c0 = 0; c0 < n_cells; c0 += chunk_cells) {
     const int bc = n_cells - c0 < chunk_cells ? n_cells - c0 : chunk_cells;
-    if (m->fold) {
-      const int ld_z = 2 * m->Dp;
-      {
-        ProfScope ps(P_EMBED, s);
-        launch_embed_ps(patches + (size_t)c0 * c_img * 1600, c_img, src_chan, m->C, m->pe_w, m->pe_b, m->pos, w.zps, ld_z, D, bc, s);
-      }
-      {
-        ProfScope ps(P_OTHER, s);
-        launch_cls_rows_ps(w.zps, ld_z, m->cls, m->pos, D, bc, kTokens, s);
-      }
-      { ProfScope ps(P_LN, s); launch_row_stats_ps(w.zps, ld_z, bc * kTokens, D, w.rs, true, s); }
-      if (w.zmx.hi != nullptr && !precise && !cell_attn_on(geom) && m->layers.size() > 1) {      // the first block's qkv operand
-        ProfScope ps(P_OTHER, s);
-        MxAct zmx = w.zmx;
-        zmx.M = bc * kTokens;
-        launch_mx_pack_act(w.zps, ld_z, bc * kTokens, m->Dp, zmx, s);
-      }
-      for (size_t li = 0; li + 1 < m->layers.size(); ++li) run_block_fold(m->layers[li], w, bc, geom, s, precise, li + 2 < m->layers.size());
-      run_last_block_cls_fold(m->layers.back(), w, bc, geom, s);
-      {
-        ProfScope ps(P_HEAD, s);
-        launch_head_softmax_ps(w.zps, ld_z, m->norm_w, m->norm_b, m->head_w, m->head_b, probs + (size_t)c0 * m->K, D, m->K, bc, s);
-      }
-      continue;
-    }
     {
       ProfScope ps(P_EMBED, s);
-      launch_embed_f32(patches + (size_t)c0 * c_img * 1600, c_img, src_chan, m->C, m->pe_w, m->pe_b, m->pos, w.z, D, D, bc, s);
+      launch_embed_ps(patches + (size_t)c0 * c_img * 1600, c_img, src_chan, m->C, m->pe_w, m->pe_b, m->pos, w.zps, ld_z, D, bc, s);
     }
     {
       ProfScope ps(P_OTHER, s);
-      launch_cls_rows(w.z, D, m->cls, m->pos, D, bc, kTokens, s);
+      launch_cls_rows_ps(w.zps, ld_z, m->cls, m->pos, D, bc, kTokens, s);
     }
-    for (size_t li = 0; li + 1 < m->layers.size(); ++li) run_block(m->layers[li], w, bc, geom, s);
-    run_last_block_cls(m->layers.back(), w, bc, geom, s);
+    { ProfScope ps(P_LN, s); launch_row_stats_ps(w.zps, ld_z, bc * kTokens, D, w.rs, true, s); }
+    if (path.qkv_mx3() && n_whole > 0) {      // the first block's qkv operand
+      ProfScope ps(P_OTHER, s);
+      MxAct zmx = w.zmx;
+      zmx.M = bc * kTokens;
+      launch_mx_pack_act(w.zps, ld_z, bc * kTokens, m->Dp, zmx, s);
+    }
+    for (size_t li = 0; li < n_whole; ++li) run_block_fold(m->layers[li], w, bc, geom, path, path.qkv_mx3() && li + 1 < n_whole, s);
+    run_last_block_cls_fold(m->layers.back(), w, bc, geom, s);
     {
       ProfScope ps(P_HEAD, s);
-      launch_head_softmax(w.z, D, m->norm_w, m->norm_b, m->head_w, m->head_b, probs + (size_t)c0 * m->K, D, m->K, bc, s);
+      launch_head_softmax_ps(w.zps, ld_z, m->norm_w, m->norm_b, m->head_w, m->head_b, probs + (size_t)c0 * m->K, D, m->K, bc, s);
     }
   }
   RIBCA_FINISH();
   return 0;
+}
+int ribca_vit_forward(const ribca_vit_t* m, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells, float* probs,
+                      void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream) {
+  if (!m) return fail("ribca_vit_forward: model is NULL");
+  return vit_forward_impl(m, m->path, patches, c_img, src_chan, n_cells, probs, workspace, workspace_bytes, chunk_cells, stream);
+}
+int ribca_vit_forward_precise(const ribca_vit_t* m, const float* patches, int32_t c_img, const int32_t* src_chan, int32_t n_cells, float* probs,
+                              void* workspace, int64_t workspace_bytes, int32_t chunk_cells, void* stream) {
+  if (!m) return fail("ribca_vit_forward: model is NULL");
+  return vit_forward_impl(m, m->path.precise(), patches, c_img, src_chan, n_cells, probs, workspace, workspace_bytes, chunk_cells, stream);
 }
 
 // ------------------------------------------------------------------------------------------- marker imputer
@@ -675,15 +640,18 @@ int64_t ribca_mae_blob_len(int32_t L, int32_t enc_depth, int32_t dec_depth) {
          dec_depth * block_params(d) + 2 * d + (int64_t)kTokPix * d + kTokPix;
 }
 
-int ribca_mae_create(const float* blob, int64_t blob_len, int32_t L, int32_t enc_depth, int32_t dec_depth, void* stream, ribca_mae_t** out) {
-  if (!out) return fail("ribca_mae_create: out is NULL");
+int ribca_mae_create_path(const float* blob, int64_t blob_len, int32_t L, int32_t enc_depth, int32_t dec_depth, int32_t fold, void* stream,
+                          ribca_mae_t** out) {
+  if (!out) return fail("ribca_mae_create_path: out is NULL");
   *out = nullptr;
+  if (fold != 0 && fold != 1) return fail("ribca_mae_create_path: fold must be 0 (fp32 residual stream, fp16x3) or 1 (folded blocks)");
   if (L < 2 || L > 15 || enc_depth <= 0 || dec_depth <= 0) return fail("ribca_mae_create: L must be in [2, 15] (tokens incl. CLS <= 16)");
   if (blob_len != ribca_mae_blob_len(L, enc_depth, dec_depth)) return fail("ribca_mae_create: blob length does not match (L, depths)");
   hipStream_t s = (hipStream_t)stream;
   ribca_mae* m = new ribca_mae();
   m->L = L; m->enc_depth = enc_depth; m->dec_depth = dec_depth;
-  m->fold = !(getenv("RIBCA_MAE_FOLD") && atoi(getenv("RIBCA_MAE_FOLD")) == 0);
+  m->enc_path = block_path(make_attn_geom(kEncD, kEncH, L + 1), fold != 0);
+  m->dec_path = block_path(make_attn_geom(kDecD, kDecH, L + 1), fold != 0);
   m->arena_bytes = layout_mae(m, nullptr);
   hipError_t e = hipMalloc((void**)&m->arena, m->arena_bytes);
   if (e != hipSuccess) { delete m; return hip_fail(e, "hipMalloc(imputer weights)"); }
@@ -693,13 +661,13 @@ int ribca_mae_create(const float* blob, int64_t blob_len, int32_t L, int32_t enc
   r.copy(m->pos, (size_t)(L + 1) * kEncD);
   r.pack(m->pe_w, kEncD, kTokPix, kTokPix);
   r.copy(m->pe_b, kEncD);
-  for (auto& B : m->enc) r.block(B, kEncD, m->fold);
+  for (auto& B : m->enc) r.block(B, kEncD, m->enc_path);
   r.copy(m->norm_w, kEncD); r.copy(m->norm_b, kEncD);
   r.pack(m->de_w, kDecD, kEncD, kEncD);
   r.copy(m->de_b, kDecD);
   r.copy(m->mask_tok, kDecD);
   r.copy(m->dpos, (size_t)(L + 1) * kDecD);
-  for (auto& B : m->dec) r.block(B, kDecD, m->fold);
+  for (auto& B : m->dec) r.block(B, kDecD, m->dec_path);
   r.copy(m->dnorm_w, kDecD); r.copy(m->dnorm_b, kDecD);
   r.pack(m->pred_w, kTokPix, kDecD, kDecD);
   r.copy(m->pred_b, kTokPix);
@@ -708,6 +676,12 @@ int ribca_mae_create(const float* blob, int64_t blob_len, int32_t L, int32_t enc
   if (api_finish() != 0) { ribca_mae_destroy(m); return 1; }
   *out = m;
   return 0;
+}
+
+// RIBCA_MAE_FOLD=0 in the environment at THIS create (read at every create, unlike the process switches): the round-2 path, for A/B
+int ribca_mae_create(const float* blob, int64_t blob_len, int32_t L, int32_t enc_depth, int32_t dec_depth, void* stream, ribca_mae_t** out) {
+  if (!out) return fail("ribca_mae_create: out is NULL");
+  return ribca_mae_create_path(blob, blob_len, L, enc_depth, dec_depth, env_on("RIBCA_MAE_FOLD") ? 1 : 0, stream, out);
 }
 
 void ribca_mae_destroy(ribca_mae_t* m) {
@@ -730,9 +704,9 @@ constexpr int kMaeTables = 7;
 MaeWs carve_mae(const ribca_mae* m, int chunk, int P, char* base) {
   Carver c(base);
   MaeWs w;
-  w.enc = carve_blocks(c, chunk, make_attn_geom(kEncD, kEncH, P + 1), m->fold);
-  w.dec = carve_blocks(c, chunk, make_attn_geom(kDecD, kDecH, m->L + 1), m->fold);
-  if (m->fold) {
+  w.enc = carve_blocks(c, chunk, make_attn_geom(kEncD, kEncH, P + 1), m->enc_path);
+  w.dec = carve_blocks(c, chunk, make_attn_geom(kDecD, kDecH, m->L + 1), m->dec_path);
+  if (m->enc_path.fold) {
     w.enc_zf = c.take<float>((size_t)chunk * (P + 1) * kEncD);
     w.dec_zf = c.take<float>((size_t)chunk * (m->L + 1) * kDecD);
   }
@@ -778,15 +752,15 @@ int ribca_mae_impute(const ribca_mae_t* m, float* patches, const int32_t* presen
   const int *t_present = w.tables, *t_missing = w.tables + 16, *t_eslot = w.tables + 32, *t_epos = w.tables + 48, *t_dslot = w.tables + 64,
             *t_dmask = w.tables + 80, *t_all = w.tables + 96;
   const AttnGeom ge = make_attn_geom(kEncD, kEncH, P + 1), gd = make_attn_geom(kDecD, kDecH, L + 1);
-  if (zero_pads(w.enc, s) || zero_pads(w.dec, s)) return 1;
-  const bool fold = m->fold;
+  if (zero_pads(w.enc, m->enc_path, s) || zero_pads(w.dec, m->dec_path, s)) return 1;
+  const bool fold = m->enc_path.fold;      // (both runs of blocks fold, or neither)
   // fp32 token rows -> the packed-split residual stream of a run of folded blocks + the statistics its first LayerNorm reads (+ the MX3
   // copy where that width's qkv runs on the MX kernel): what vit_forward_impl does behind the patch embedding
-  auto enter_fold = [&](const float* zf, const BlockWs& bw, int cells, const AttnGeom& a, size_t depth) {
+  auto enter_fold = [&](const float* zf, const BlockWs& bw, int cells, const AttnGeom& a, const BlockPath& p) {
     const int D = a.D, ld = 2 * round_up(D, 32), Mc = cells * a.T;
     launch_rows_to_ps(zf, D, bw.zps, ld, round_up(D, 32), cells, a.T, a.T, t_all, s);
     launch_row_stats_ps(bw.zps, ld, Mc, D, bw.rs, true, s);
-    if (bw.zmx.hi != nullptr && !cell_attn_on(a) && depth > 0) {
+    if (p.qkv_mx3()) {
       MxAct zmx = bw.zmx;
       zmx.M = Mc;
       launch_mx_pack_act(bw.zps, ld, Mc, round_up(D, 32), zmx, s);
@@ -805,8 +779,8 @@ int ribca_mae_impute(const ribca_mae_t* m, float* patches, const int32_t* presen
     }
     launch_cls_rows(ez, kEncD, m->cls, m->pos, kEncD, bc, P + 1, s);
     if (fold) {
-      enter_fold(ez, w.enc, bc, ge, m->enc.size());
-      for (size_t li = 0; li < m->enc.size(); ++li) run_block_fold(m->enc[li], w.enc, bc, ge, s, false, li + 1 < m->enc.size());
+      enter_fold(ez, w.enc, bc, ge, m->enc_path);
+      for (size_t li = 0; li < m->enc.size(); ++li) run_block_fold(m->enc[li], w.enc, bc, ge, m->enc_path, m->enc_path.qkv_mx3() && li + 1 < m->enc.size(), s);
       // decoder input (markerImputer.py:208-219): final encoder norm (its own statistics from the packed-split rows), project latents
       launch_layernorm_gather_ps_from_ps(w.enc.zps, 2 * kEncD, m->norm_w, m->norm_b, w.enc.xa, 2 * kEncD, bc, P + 1, P + 1, t_all, kEncD, s);
     } else {
@@ -821,8 +795,8 @@ int ribca_mae_impute(const ribca_mae_t* m, float* patches, const int32_t* presen
     launch_fill_rows(dz, kDecD, m->mask_tok, m->dpos, kDecD, bc, L + 1, Mi, t_dmask, s);
     // predict only the missing channels and write them into the patch tensor (blend, markerImputer.py:312-326)
     if (fold) {
-      enter_fold(dz, w.dec, bc, gd, m->dec.size());
-      for (size_t li = 0; li < m->dec.size(); ++li) run_block_fold(m->dec[li], w.dec, bc, gd, s, false, li + 1 < m->dec.size());
+      enter_fold(dz, w.dec, bc, gd, m->dec_path);
+      for (size_t li = 0; li < m->dec.size(); ++li) run_block_fold(m->dec[li], w.dec, bc, gd, m->dec_path, m->dec_path.qkv_mx3() && li + 1 < m->dec.size(), s);
       launch_layernorm_gather_ps_from_ps(w.dec.zps, 2 * kDecD, m->dnorm_w, m->dnorm_b, w.tok_ps, 2 * kDecD, bc, L + 1, Mi, t_dmask, kDecD, s);
     } else {
       for (const auto& B : m->dec) run_block(B, w.dec, bc, gd, s);

@@ -60,8 +60,6 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 
 constexpr int kTokens = 101;   // 10x10 patches + CLS (reference model.py:66-88 with img_size=40, patch 4)
 constexpr int kHeads = 12;
-constexpr int kTokPad = 112;   // tokens padded to 7 MFMA tiles of 16 for attention operands
-constexpr int kKeyPad = 128;   // keys padded to 4 MFMA K-steps of 32 for the P*V product
 
 constexpr float kF16Max = 65504.0f;
 __device__ __forceinline__ float clamp_f16_range(float x) { return __builtin_amdgcn_fmed3f(x, -kF16Max, kF16Max); }

@@ -108,8 +108,6 @@ void launch_cell_qkv_attention(const uint16_t* z, int ldz, const uint16_t* W, in
 // ----- small ViT kernels (vit_misc.hip) ----------------------------------------------------------------------
 void launch_layernorm_ps(const float* z, int ldz, const float* gamma, const float* beta, uint16_t* out, int ldo, int M, int D,
                          hipStream_t s);
-void launch_embed_f32(const float* patches, int c_img, const int* src_chan, int C, const float* w, const float* bias, const float* pos,
-                      float* z, int ldz, int D, int cells, hipStream_t s);
 void launch_cls_rows(float* z, int ldz, const float* cls, const float* pos, int D, int cells, int tokens_per_cell, hipStream_t s);
 // out_ps row (cell*S + j) = LayerNorm(z row (cell*T + sel[j])): the rows a following GEMM actually needs
 void launch_layernorm_gather_ps(const float* z, int ldz, const float* gamma, const float* beta, uint16_t* out, int ldo, int cells, int T,
@@ -121,8 +119,6 @@ void launch_layernorm_gather_ps_from_ps(const uint16_t* z_ps, int ldz, const flo
 void launch_rows_to_ps(const float* src, int K, uint16_t* out, int ldo, int Kp, int cells, int T, int S, const int* sel, hipStream_t s);
 // z row (cell*T + sel[j]) = a[:] + table[sel[j]][:]   (mask tokens + positional embedding)
 void launch_fill_rows(float* z, int ldz, const float* a, const float* table, int D, int cells, int T, int S, const int* sel, hipStream_t s);
-void launch_head_softmax(const float* z, int ldz, const float* gamma, const float* beta, const float* hw, const float* hb,
-                         float* probs, int D, int K, int cells, hipStream_t s);
 void launch_pack_weight(const float* w, int N, int K, uint16_t* out, int Np, int Kp, hipStream_t s);
 // packed-split residual stream of the classifiers
 void launch_embed_ps(const float* patches, int c_img, const int* src_chan, int C, const float* w, const float* bias, const float* pos,

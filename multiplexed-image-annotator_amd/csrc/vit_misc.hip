@@ -63,11 +63,10 @@ void launch_layernorm_ps(const float* z, int ldz, const float* gamma, const floa
 // cancellation of O(1) terms, and LayerNorm rescales that row to unit variance, so a 2^-16-relative product error
 // (split 16-bit operands) is amplified ~50x there.  fp32 FMA keeps this stage at the reference's own precision.
 // Classic 64x64 LDS-tiled SGEMM, one input channel (16 taps) per K step, im2col done on the fly from the fp32 patches.
-// PS = true: z is the packed-split residual stream of the classifiers (uint16 [rows][ldz], fp16 hi + lo), else fp32.
-template <bool PS>
+// z is the packed-split residual stream of the classifiers (uint16 [rows][ldz], fp16 hi + lo).
 __global__ __launch_bounds__(256) void embed_f32_kernel(const float* __restrict__ patches, int c_img, const int* __restrict__ src_chan,
                                                         int C, const float* __restrict__ w /*[D][C*16]*/, const float* __restrict__ bias,
-                                                        const float* __restrict__ pos, void* __restrict__ zv, int ldz, int D, int M) {
+                                                        const float* __restrict__ pos, uint16_t* __restrict__ z, int ldz, int D, int M) {
   __shared__ float As[16][64 + 4];  // [k][row]
   __shared__ float Ws[16][64 + 4];  // [k][col]
   const int tid = threadIdx.x;
@@ -121,28 +120,16 @@ __global__ __launch_bounds__(256) void embed_f32_kernel(const float* __restrict_
     float4 o;
     o.x = acc[i][0] + bv.x + pe.x; o.y = acc[i][1] + bv.y + pe.y; o.z = acc[i][2] + bv.z + pe.z; o.w = acc[i][3] + bv.w + pe.w;
     const size_t zrow = ((size_t)cl * kTokens + 1 + tt) * ldz;
-    if constexpr (PS) {
-      const float v4[4] = {o.x, o.y, o.z, o.w};
-      ps_store4(static_cast<uint16_t*>(zv) + zrow, n, v4);
-    } else {
-      *reinterpret_cast<float4*>(static_cast<float*>(zv) + zrow + n) = o;
-    }
+    const float v4[4] = {o.x, o.y, o.z, o.w};
+    ps_store4(z + zrow, n, v4);
   }
 }
 
-void launch_embed_f32(const float* patches, int c_img, const int* src_chan, int C, const float* w, const float* bias, const float* pos,
-                      float* z, int ldz, int D, int cells, hipStream_t s) {
-  const int M = cells * 100;
-  if (M <= 0) return;
-  hipLaunchKernelGGL(embed_f32_kernel<false>, dim3((M + 63) / 64, (D + 63) / 64), dim3(256), 0, s, patches, c_img, src_chan, C, w, bias, pos,
-                     (void*)z, ldz, D, M);
-}
 void launch_embed_ps(const float* patches, int c_img, const int* src_chan, int C, const float* w, const float* bias, const float* pos,
                      uint16_t* z, int ldz, int D, int cells, hipStream_t s) {
   const int M = cells * 100;
   if (M <= 0) return;
-  hipLaunchKernelGGL(embed_f32_kernel<true>, dim3((M + 63) / 64, (D + 63) / 64), dim3(256), 0, s, patches, c_img, src_chan, C, w, bias, pos,
-                     (void*)z, ldz, D, M);
+  hipLaunchKernelGGL(embed_f32_kernel, dim3((M + 63) / 64, (D + 63) / 64), dim3(256), 0, s, patches, c_img, src_chan, C, w, bias, pos, z, ldz, D, M);
 }
 
 // packed-split residual stream: CLS rows (model.py:49-51), one thread per 4 columns
@@ -384,27 +371,21 @@ void launch_fill_rows(float* z, int ldz, const float* a, const float* table, int
   hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, z, ldz, a, table, D, total, T, S, sel);
 }
 
-// final LayerNorm of the CLS row -> Linear(D, K) -> softmax(dim=1), all fp32.  One wave per cell, K <= 16.
-template <bool PS>
-__global__ __launch_bounds__(256) void head_softmax_kernel(const void* __restrict__ zv, int ldz, const float* __restrict__ gamma,
+// final LayerNorm of the CLS row (packed-split residual stream) -> Linear(D, K) -> softmax(dim=1), all fp32.  One wave per cell, K <= 16.
+__global__ __launch_bounds__(256) void head_softmax_kernel(const uint16_t* __restrict__ z, int ldz, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ hw,
                                                            const float* __restrict__ hb, float* __restrict__ probs, int D, int K,
                                                            int cells) {
   const int lane = threadIdx.x & 63;
   const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (cell >= cells) return;
+  const uint16_t* zr = z + (size_t)cell * kTokens * ldz;
   float x[12];
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < 12; ++i) {
     const int d = lane + 64 * i;
-    if constexpr (PS) {
-      const uint16_t* zr = static_cast<const uint16_t*>(zv) + (size_t)cell * kTokens * ldz;
-      x[i] = d < D ? f16_to_f32(zr[ps_off(d)]) + f16_to_f32(zr[ps_off(d) + 8]) : 0.f;
-    } else {
-      const float* zr = static_cast<const float*>(zv) + (size_t)cell * kTokens * ldz;
-      x[i] = d < D ? zr[d] : 0.f;
-    }
+    x[i] = d < D ? f16_to_f32(zr[ps_off(d)]) + f16_to_f32(zr[ps_off(d) + 8]) : 0.f;
     sum += x[i];
   }
   const float mean = wave_sum(sum) / (float)D;
@@ -439,15 +420,10 @@ __global__ __launch_bounds__(256) void head_softmax_kernel(const void* __restric
     for (int k = 0; k < K; ++k) probs[(size_t)cell * K + k] = logit[k] / den;
 }
 
-void launch_head_softmax(const float* z, int ldz, const float* gamma, const float* beta, const float* hw, const float* hb, float* probs,
-                         int D, int K, int cells, hipStream_t s) {
-  if (cells <= 0) return;
-  hipLaunchKernelGGL(head_softmax_kernel<false>, dim3((cells + 3) / 4), dim3(256), 0, s, (const void*)z, ldz, gamma, beta, hw, hb, probs, D, K, cells);
-}
 void launch_head_softmax_ps(const uint16_t* z, int ldz, const float* gamma, const float* beta, const float* hw, const float* hb, float* probs,
                             int D, int K, int cells, hipStream_t s) {
   if (cells <= 0) return;
-  hipLaunchKernelGGL(head_softmax_kernel<true>, dim3((cells + 3) / 4), dim3(256), 0, s, (const void*)z, ldz, gamma, beta, hw, hb, probs, D, K, cells);
+  hipLaunchKernelGGL(head_softmax_kernel, dim3((cells + 3) / 4), dim3(256), 0, s, z, ldz, gamma, beta, hw, hb, probs, D, K, cells);
 }
 
 // fp32 nn.Linear weight [N][K] -> packed-split fp16 [Np][2*Kp], zero padded.  One thread per 4 consecutive k.

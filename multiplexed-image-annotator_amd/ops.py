@@ -24,15 +24,19 @@ VOTE_ORDER: List[str] = ["CD4 T cell", "CD8 T cell", "Dendritic cell", "B cell",
                          "Nerve cell"]
 GLOBAL_NAMES: List[str] = VOTE_ORDER + ["Others"]
 
+_BLOCK_TENSORS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+                  "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
+
+
+def _block_keys(prefix: str, depth: int) -> List[str]:
+    """the 12 tensors of each timm Block, in blob order"""
+    return [f"{prefix}{i}.{t}" for i in range(depth) for t in _BLOCK_TENSORS]
+
+
 #: state-dict key order of the flat parameter blob (include/ribca_hip.h, ribca_vit_blob_len)
 def blob_keys(depth: int) -> List[str]:
-    keys = ["cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"]
-    for i in range(depth):
-        p = f"blocks.{i}."
-        keys += [p + "norm1.weight", p + "norm1.bias", p + "attn.qkv.weight", p + "attn.qkv.bias", p + "attn.proj.weight",
-                 p + "attn.proj.bias", p + "norm2.weight", p + "norm2.bias", p + "mlp.fc1.weight", p + "mlp.fc1.bias",
-                 p + "mlp.fc2.weight", p + "mlp.fc2.bias"]
-    return keys + ["norm.weight", "norm.bias", "head.weight", "head.bias"]
+    return (["cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"] + _block_keys("blocks.", depth)
+            + ["norm.weight", "norm.bias", "head.weight", "head.bias"])
 
 
 def gaussian_taps() -> np.ndarray:
@@ -927,17 +931,9 @@ def _side_streams(device, n: int):
 
 
 def mae_blob_keys(enc_depth: int, dec_depth: int) -> List[str]:
-    def blk(prefix, depth):
-        out = []
-        for i in range(depth):
-            p = f"{prefix}{i}."
-            out += [p + "norm1.weight", p + "norm1.bias", p + "attn.qkv.weight", p + "attn.qkv.bias", p + "attn.proj.weight",
-                    p + "attn.proj.bias", p + "norm2.weight", p + "norm2.bias", p + "mlp.fc1.weight", p + "mlp.fc1.bias",
-                    p + "mlp.fc2.weight", p + "mlp.fc2.bias"]
-        return out
-    return (["cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"] + blk("blocks.", enc_depth)
+    return (["cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"] + _block_keys("blocks.", enc_depth)
             + ["norm.weight", "norm.bias", "decoder_embed.weight", "decoder_embed.bias", "mask_token", "decoder_pos_embed"]
-            + blk("decoder_blocks.", dec_depth) + ["decoder_norm.weight", "decoder_norm.bias", "decoder_pred.weight", "decoder_pred.bias"])
+            + _block_keys("decoder_blocks.", dec_depth) + ["decoder_norm.weight", "decoder_norm.bias", "decoder_pred.weight", "decoder_pred.bias"])
 
 
 class MaeModel:
@@ -968,10 +964,15 @@ class MaeModel:
         if os.environ.get("RIBCA_MARGIN_PROBE", "1") != "0" and os.environ.get("RIBCA_MAE_FOLD") is None:
             self._probe(blob, enc, dec)
 
-    def _create(self, blob, enc, dec):
+    def _create(self, blob, enc, dec, fold: Optional[int] = None):
+        """``fold`` None: the library's choice (RIBCA_MAE_FOLD in the environment at this call); 1 / 0: the folded / the fp16x3 path"""
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            check(lib().ribca_mae_create(ptr(blob), blob.numel(), self.L, enc, dec, stream_ptr(), ctypes.byref(handle)), "ribca_mae_create")
+            if fold is None:
+                check(lib().ribca_mae_create(ptr(blob), blob.numel(), self.L, enc, dec, stream_ptr(), ctypes.byref(handle)), "ribca_mae_create")
+            else:
+                check(lib().ribca_mae_create_path(ptr(blob), blob.numel(), self.L, enc, dec, int(fold), stream_ptr(), ctypes.byref(handle)),
+                      "ribca_mae_create_path")
             torch.cuda.current_stream().synchronize()
         return handle
 
@@ -981,26 +982,23 @@ class MaeModel:
     PROBE_CELLS = 64
 
     def _probe(self, blob, enc, dec) -> None:
-        os.environ["RIBCA_MAE_FOLD"] = "0"          # read by the library at create
+        drop = self._create(blob, enc, dec, fold=0)      # the yardstick; whichever handle `drop` names when the probe ends (or fails) goes
         try:
-            slow = self._create(blob, enc, dec)
+            g = torch.Generator().manual_seed(0x5249424342)
+            u = torch.rand((self.PROBE_CELLS, self.L, PATCH, PATCH), generator=g, dtype=torch.float32) * 2.0 - 1.0
+            x = torch.where(u > 0.1, u, torch.full_like(u, -1.0))
+            x[:, self.L - 1] = -1.0                      # the last marker missing, as in BASELINE config 5
+            present = list(range(self.L - 1))
+            a, b = x.to(self.device).contiguous(), x.to(self.device).contiguous()
+            with torch.cuda.device(self.device):
+                self._impute_with(self._h, a, present, self.PROBE_CELLS)
+                self._impute_with(drop, b, present, self.PROBE_CELLS)
+                self.probe_plane_delta = float((a[:, self.L - 1] - b[:, self.L - 1]).abs().max().item())
+            self.fast_ok = self.probe_plane_delta <= self.PROBE_LIMIT
+            if not self.fast_ok:      # these weights do not tolerate the MX products: every product at three fp16 passes
+                self._h, drop = drop, self._h
         finally:
-            del os.environ["RIBCA_MAE_FOLD"]
-        g = torch.Generator().manual_seed(0x5249424342)
-        u = torch.rand((self.PROBE_CELLS, self.L, PATCH, PATCH), generator=g, dtype=torch.float32) * 2.0 - 1.0
-        x = torch.where(u > 0.1, u, torch.full_like(u, -1.0))
-        x[:, self.L - 1] = -1.0                      # the last marker missing, as in BASELINE config 5
-        present = list(range(self.L - 1))
-        a, b = x.to(self.device).contiguous(), x.to(self.device).contiguous()
-        with torch.cuda.device(self.device):
-            self._impute_with(self._h, a, present, self.PROBE_CELLS)
-            self._impute_with(slow, b, present, self.PROBE_CELLS)
-            self.probe_plane_delta = float((a[:, self.L - 1] - b[:, self.L - 1]).abs().max().item())
-        self.fast_ok = self.probe_plane_delta <= self.PROBE_LIMIT
-        drop = slow if self.fast_ok else self._h
-        if not self.fast_ok:
-            self._h = slow                           # these weights do not tolerate the MX products: every product at three fp16 passes
-        lib().ribca_mae_destroy(drop)
+            lib().ribca_mae_destroy(drop)
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -140,3 +140,26 @@ def test_entry_points_refuse_bad_arguments_with_a_status():
     lib.ribca_vit_destroy(None)
     lib.ribca_mae_destroy(None)
     assert lib.ribca_vote(None, 3, None, None, 0, None, None, 0.3, 0, None, None, None) == 0      # n = 0: nothing to do, nothing touched
+
+
+def test_mae_create_path_refuses_an_unknown_path():
+    """fold is 0 or 1; anything else is refused with a status naming the entry point before any HIP call, and the handle stays NULL"""
+    from multiplexed_image_annotator_amd import _lib
+    lib = _lib.lib()
+    handle = ctypes.c_void_p()
+    assert lib.ribca_mae_create_path(None, 0, 7, 1, 1, 2, None, ctypes.byref(handle)) != 0
+    assert b"ribca_mae_create_path" in lib.ribca_last_error()
+    assert not handle.value
+
+
+def test_mx_width_table_under_the_default_environment():
+    """which widths run mlp.fc2 (4 D % 128 == 0, D % 48 == 0) and the residual rows (D % 192 == 0 on top) on the MX kernels.  The switches are
+    read once per process, so the table is read in a child whose environment names none of them."""
+    import subprocess
+    import sys
+    from multiplexed_image_annotator_amd import _lib
+    env = {k: v for k, v in os.environ.items() if k not in ("RIBCA_MX", "RIBCA_MXZ", "RIBCA_CELL_ATTN")}
+    code = ("import ctypes, sys; h = ctypes.CDLL(sys.argv[1]); w = (144, 288, 384, 512, 576, 768); "
+            "print([h.ribca_mx_enabled(d) for d in w], [h.ribca_mxz_enabled(d) for d in w])")
+    out = subprocess.run([sys.executable, "-c", code, _lib.LIB_PATH], env=env, capture_output=True, text=True, check=True).stdout
+    assert out.strip() == "[0, 1, 1, 0, 1, 1] [0, 0, 1, 0, 1, 1]"

@@ -401,6 +401,46 @@ def test_imputer_load_time_probe():
     assert (a[:, 3] - b[:, 3]).abs().max().item() < 1e-3
 
 
+def test_imputer_path_is_an_argument(monkeypatch):
+    """ribca_mae_create_path(fold) builds what ribca_mae_create builds under the matching RIBCA_MAE_FOLD, bit for bit, and ops.MaeModel picks
+    the probe's yardstick through it: loading a model (probe included) neither writes nor deletes an environment variable."""
+    from multiplexed_image_annotator_amd import _lib, ops
+    dev = _lib.require_gpu()
+    sd = synth.make_mae_state_dict("immune_base", synth.SEED_BASE + 6, enc_depth=1, dec_depth=1)
+    monkeypatch.delenv("RIBCA_MAE_FOLD", raising=False)      # the default environment: the probe runs
+    monkeypatch.delenv("RIBCA_MARGIN_PROBE", raising=False)
+    writes = []
+    env_type = type(os.environ)
+    set_item, del_item = env_type.__setitem__, env_type.__delitem__
+    with monkeypatch.context() as mp:
+        mp.setattr(env_type, "__setitem__", lambda self, k, v: (writes.append(k), set_item(self, k, v))[1])
+        mp.setattr(env_type, "__delitem__", lambda self, k: (writes.append(k), del_item(self, k))[1])
+        before = dict(os.environ)
+        m = ops.MaeModel(sd, dev)
+        assert dict(os.environ) == before and list(os.environ) == list(before) and writes == []
+    assert m.probe_plane_delta > 0.0          # the probe ran
+    present = [0, 1, 2, 4, 5, 6]
+    g = torch.Generator().manual_seed(4)
+    x = (torch.rand((5, 7, 40, 40), generator=g) * 2 - 1).to(dev)
+    blob = torch.cat([sd[k].detach().to(torch.float32).reshape(-1) for k in ops.mae_blob_keys(1, 1)]).to(dev)
+
+    def imputed(fold, env):
+        with monkeypatch.context() as mp:
+            if env is not None:
+                mp.setenv("RIBCA_MAE_FOLD", env)
+            h = m._create(blob, 1, 1, fold)
+        try:
+            return m._impute_with(h, x.clone(), present, 4)
+        finally:
+            _lib.lib().ribca_mae_destroy(h)
+
+    slow_arg, slow_env = imputed(0, None), imputed(None, "0")
+    fast_arg, fast_env = imputed(1, None), imputed(None, None)
+    assert torch.equal(slow_arg, slow_env) and torch.equal(fast_arg, fast_env)
+    assert not torch.equal(slow_arg[:, 3], fast_arg[:, 3])      # (two different paths were compared, not one twice)
+    assert torch.equal(slow_arg[:, present], x[:, present])
+
+
 def _tile_rank_worker(rank, world, port, root, seed):
     """One rank of a tile-per-rank run: a batch CSV of three images over two ranks (both on cuda:0 here; gloo for the control plane)."""
     import torch.distributed as tdist
