@@ -298,6 +298,40 @@ int64_t ribca_scatter_raster_ws_bytes(int32_t height, int32_t width);
 int ribca_scatter_raster(const float* points, const uint8_t* rgb, int32_t n, double ax, double bx, double ay, double by, int32_t height, int32_t width,
                          int32_t radius, uint8_t* out, int64_t* skipped, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- per-cell-type statistics and their plots (Annotator.generate_heatmap, model.py:700-741; Annotator.cell_type_composition,
+ * model.py:861-912; csrc/celltype_stats.hip) -------------------------------------------------------------------------------------------------
+ * ribca_group_sums: x (n, c) fp64 row-major, group (n) int32 -> sums (groups, c) fp64, counts (groups) int64 (device), *skipped (HOST) = the rows
+ * whose id lies outside [0, groups): they are ignored, which is how a caller masks rows.  Sums and counts, not means: partial results of several
+ * images or ranks combine exactly in the counts and in an order the caller fixes in the sums.  1 <= c <= 1024, 1 <= groups <= 256,
+ * 0 <= n < 2^31 - 1; n = 0 gives zeros.  sums is a pure function of x and group -- no floating-point atomic; it does not depend on the launch
+ * geometry, the device, the workspace or the stream -- with THE summation tree, every addition rounded on its own (no fma), R = 1024:
+ *     chunk k = the rows [k R, min(n, (k + 1) R));  part[k][g][j] = (((+0.0 + x[r0][j]) + x[r1][j]) + ...) over the rows r0 < r1 < ... of chunk k
+ *     whose id is g (+0.0 when there is none);  sums[g][j] = (((+0.0 + part[0][g][j]) + part[1][g][j]) + ...) over ALL chunks in ascending k.
+ * In numpy:  part = np.zeros((chunks, groups, c));  for r in range(n): part[r // 1024, group[r]] += x[r]  (ids in range only);
+ *            sums = np.zeros((groups, c));  for k in range(chunks): sums += part[k].
+ * ws: ribca_group_sums_ws_bytes(n, c, groups) bytes (0 for arguments the entry point refuses).  Synchronises the stream once. */
+int64_t ribca_group_sums_ws_bytes(int32_t n, int32_t c, int32_t groups);
+int ribca_group_sums(const double* x, const int32_t* group, int32_t n, int32_t c, int32_t groups, double* sums, int64_t* counts, int64_t* skipped,
+                     void* ws, int64_t ws_bytes, void* stream);
+/* ribca_heatmap_raster: sums (rows, cols) fp64, counts (rows) int64, lut (256, 3) uint8 -> out (rows cell, cols cell, 3) uint8 and *vmin, *vmax
+ * (HOST).  mean = sums[t][j] / (double) counts[t], NaN where counts[t] <= 0; vmin / vmax = the smallest / largest mean that is not NaN (NaN when
+ * there is none: numpy's nanmin / nanmax, seaborn's default).  The pixel (y, x) belongs to the table cell (y / cell, x / cell); it is white
+ * (255) when y % cell or x % cell lies outside [gap, cell - gap), silver (192) when the mean is NaN, and otherwise lut[i] with i = 0 when
+ * vmax == vmin, else q = floor(((mean - vmin) / (vmax - vmin)) * 256.0), every operation rounded on its own, i = 255 when q >= 255, (int) q when
+ * 0 <= q < 255, 0 otherwise.  1 <= rows <= 256, 1 <= cols <= 1024, 1 <= cell <= 64, 0 <= 2 gap < cell.
+ * ws: ribca_heatmap_raster_ws_bytes(rows, cols, cell, gap) bytes.  Synchronises the stream once. */
+int64_t ribca_heatmap_raster_ws_bytes(int32_t rows, int32_t cols, int32_t cell, int32_t gap);
+int ribca_heatmap_raster(const double* sums, const int64_t* counts, int32_t rows, int32_t cols, const uint8_t* lut, int32_t cell, int32_t gap, uint8_t* out,
+                         double* vmin, double* vmax, void* ws, int64_t ws_bytes, void* stream);
+/* ribca_pie_raster: rays (m, 2) fp64 = (cos, sin) of the m interior wedge boundaries in ascending angle, rgb (m + 1, 3) uint8 -> out (size, size, 3)
+ * uint8.  The centre is the pixel (size / 2, size / 2); a pixel at the integer offset v = (dx to the right, dy UPWARDS) with
+ * dx^2 + dy^2 <= radius^2 gets rgb[w], w = the number of rays a for which NOT (v < a); every other pixel is white.  The order of directions is that
+ * of their angles in [0, 2 pi) from 3 o'clock, counter-clockwise on screen (matplotlib's ax.pie), decided without a transcendental:
+ *     half(u) = 0 if (u.y > 0 or (u.y == 0 and u.x > 0)) else 1;   u < a  iff  half(u) < half(a), or half(u) == half(a) and u.x * a.y - u.y * a.x > 0
+ * (fp64, the two products and the difference rounded on their own).  The centre pixel gets rgb[0].  m = 0: a disc of rgb[0].
+ * 0 <= m <= 256, 1 <= size <= 16384, 0 <= radius <= size.  No workspace; does not synchronise. */
+int ribca_pie_raster(const double* rays, int32_t m, const uint8_t* rgb, int32_t size, int32_t radius, uint8_t* out, void* stream);
+
 /* ---- vote (Annotator.merge_by_voting, model.py:481-633) ------------------------------------------------------ */
 /* Global class ids: 0..16 = key order of utils.get_void_vote (utils.py:143-146), 17 = "Others".
  * p_a (n, k_a) and optional p_b (n, k_b) are softmax outputs; map_* (k) int8 give each class's global id;

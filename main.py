@@ -2,8 +2,8 @@
 """CLI with the reference's argument surface (reference main.py:56-112) on the MI355X hot path.
 
 Runs marker parsing -> preprocess -> predict -> export_annotations -> tissue_region_analysis -> neighborhood_analysis ->
-colorize, as the reference does (main.py:19-28); its plotting steps (heat-maps, pie charts, legends) are CPU work downstream
-of the CSV and are not part of this accelerated path.  ``--min-cells N`` (N > 0) re-clusters the cells the vote left as "Others" into
+colorize, as the reference does (main.py:19-28), its two plotting steps included: the integrated cell-type heat map and the cell-type
+composition pies are reduced and rasterised on the GPU and written with a CSV beside each PNG.  ``--min-cells N`` (N > 0) re-clusters the cells the vote left as "Others" into
 "Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
@@ -58,7 +58,8 @@ def _pipeline(annotator, bs, n_regions):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
-    calls (generate_heatmap, cell_type_composition) are outside the accelerated path: this Annotator logs and skips them."""
+    calls (generate_heatmap(integrate=True), cell_type_composition()) draw on the GPU; the batch-wide pie is written beside the
+    reference's per-image ones, as the heat map and the neighbourhood matrix of this sequence are the integrated ones."""
     p = annotator.channel_parser
     if not p.immune_base and not p.immune_extended and not p.immune_full and not p.struct and not p.nerve:
         raise ValueError("No panels are applied. Please check the marker list.")
@@ -75,6 +76,7 @@ def _pipeline(annotator, bs, n_regions):
         annotator.neighborhood_analysis(integrate=True, normalize=True)
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
+    annotator.cell_type_composition(integrate=True)
     annotator.clear_tmp()
 
 

@@ -62,6 +62,12 @@ SIGNATURES = {
     "ribca_scatter_raster_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_scatter_raster": (c_int32, [c_void_p, c_void_p, c_int32, c_double, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_void_p,
                                        POINTER(c_int64), c_void_p, c_int64, c_void_p]),
+    "ribca_group_sums_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ribca_group_sums": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_int64, c_void_p]),
+    "ribca_heatmap_raster_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ribca_heatmap_raster": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, POINTER(c_double), POINTER(c_double),
+                                       c_void_p, c_int64, c_void_p]),
+    "ribca_pie_raster": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ribca_u16_to_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_gauss1d": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "ribca_bg_subtract": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),

@@ -1,9 +1,9 @@
 """``Annotator``: drop-in for the reference orchestrator on its hot path (cell_type_annotation/model.py:90-919):
 same constructor, ``preprocess()``, ``predict(batch_size)``, ``export_annotations()``, ``clear_tmp()``,
 ``get_cell_type_names()`` and the attributes downstream code reads (``annotations``, ``confidence``, ``annotations_all``,
-``cell_types``, ``channel_parser``, ``preprocessor``, ``*_pred``).  Compute runs in the HIP library; the heat-map and pie-chart methods of
-the reference are outside the accelerated path: they log and return, so the reference's own call sequence
-(main.py:19-28) completes against this class; ``umap_visualization()`` embeds and draws on the GPU.
+``cell_types``, ``channel_parser``, ``preprocessor``, ``*_pred``).  Compute runs in the HIP library, the plots included:
+``generate_heatmap()`` and ``cell_type_composition()`` reduce and rasterise on the GPU and write a CSV beside every PNG, and
+``umap_visualization()`` embeds and draws there, so the reference's own call sequence (main.py:19-28) runs in full against this class.
 """
 from __future__ import annotations
 
@@ -706,19 +706,166 @@ class Annotator(object):
                             "k-means {:.1f} ms (gpu, seed {}).".format(i, stats["n"], stats["F"], stats["d"], n, stats["iterations"], pca_ms,
                                                                        kmeans_ms, seed))
 
-    # ---- outside the accelerated path ------------------------------------------------------------------------------
-    def _skip(self, what: str):
-        msg = f"{what}: skipped (plotting downstream of the CSV, outside the accelerated hot path)"
-        self.logger.log(msg)
-        return None
+    # ---- per-cell-type plots (model.py:700-741, 861-912) ------------------------------------------------------------------------------
+    HEATMAP_CELL = 24       # pixels per table cell of {batch_id}_*heatmap*.png
+    HEATMAP_GAP = 1         # white pixels around every cell (the reference's linewidth=.5)
+    PIE_CANVAS = 480        # side of the square the disc of {batch_id}_*cell-type_composition*.png is drawn in
+    PIE_RADIUS = 200
+
+    def _check_annotated(self, message: str) -> None:
+        """the reference's ValueError before predict(); a rank of a tile-per-rank run that owns no image has nothing of its own and goes on"""
+        if len(self.annotations) == 0 and not (self.tile_mode and self.preprocessor._n_images > 0):
+            raise ValueError(message)
+
+    def _type_sums(self, columns: bool, batch_wide: bool):
+        """One ops.group_sums call per image over the groups ``self.cell_types`` (the batch-wide list on every rank): sums (I, T, C) and counts
+        (I, T) as host arrays, the image number of each, the rows skipped per image (a name outside cell_types) and the milliseconds.  ``columns``
+        False: one zero column (only the counts are wanted).  ``batch_wide`` in tile-per-rank mode: I covers every image of the batch -- one
+        all-reduce in which each image's rows come from the rank that owns it and are +0.0 elsewhere, so they arrive as computed."""
+        import time
+        t0 = time.perf_counter()
+        types = {str(t): k for k, t in enumerate(self.cell_types)}
+        n_types = len(types)
+        full = self.preprocessor.intensity_full
+        width = 1
+        if columns:
+            width = next((a.shape[1] for a in full[:len(self.annotations)] if a is not None), len(self.channel_parser.markers))
+        sums = np.zeros((len(self.annotations), n_types, width), dtype=np.float64)
+        counts = np.zeros((len(self.annotations), n_types), dtype=np.int64)
+        skipped = np.zeros(len(self.annotations), dtype=np.int64)
+        dev = _lib.require_gpu()
+        for i, names in enumerate(self.annotations):
+            if len(names) == 0:
+                continue
+            ids = np.fromiter((types.get(name, -1) for name in names), dtype=np.int32, count=len(names))
+            x = np.ascontiguousarray(full[i], dtype=np.float64) if columns else np.zeros((len(names), 1), dtype=np.float64)
+            if x.shape != (len(names), width):
+                raise ValueError(f"image {i}: {x.shape[0]} intensity rows of {x.shape[1]} channels for {len(names)} annotations of {width} channels")
+            s, c, k = ops.group_sums(torch.from_numpy(x).to(dev), torch.from_numpy(ids).to(dev), n_types)
+            sums[i], counts[i], skipped[i] = s.cpu().numpy(), c.cpu().numpy(), k
+        numbers = [self._image_number(i) for i in range(len(self.annotations))]
+        if batch_wide and self.tile_mode:
+            n_batch = self.preprocessor._n_images
+            buf = np.zeros((n_batch, n_types * (width + 1) + 1), dtype=np.float64)      # counts and skipped rows are exact in fp64 (< 2^53)
+            for i, num in enumerate(numbers):
+                buf[num, :n_types * width] = sums[i].reshape(-1)
+                buf[num, n_types * width:-1] = counts[i]
+                buf[num, -1] = skipped[i]
+            buf = dist.all_reduce_sum(torch.from_numpy(buf)).numpy()
+            sums = buf[:, :n_types * width].reshape(n_batch, n_types, width)
+            counts = buf[:, n_types * width:-1].astype(np.int64)
+            skipped = buf[:, -1].astype(np.int64)
+            numbers = list(range(n_batch))
+        return sums, counts, numbers, skipped, (time.perf_counter() - t0) * 1e3
+
+    @staticmethod
+    def _add_in_order(tables: np.ndarray) -> np.ndarray:
+        """the (T, C) tables of the images added from +0.0 in ascending image order"""
+        total = np.zeros(tables.shape[1:], dtype=tables.dtype)
+        for t in tables:
+            total = total + t
+        return total
 
     def generate_heatmap(self, integrate=False):
-        """model.py:697-766 (seaborn heat-maps of the intensity table): not drawn; ``preprocessor.intensity_full`` holds the data."""
-        return self._skip("generate_heatmap")
+        """model.py:700-741: the mean intensity of every image channel (columns, labelled ``channel_parser.markers``) over the cells of every
+        cell type present (rows: np.unique of the annotation names, of the batch with ``integrate`` or per image), as
+        ``{batch_id}_Integrated_heatmap.png`` / ``{batch_id}_heatmap_{i}.png`` and, beside each, the table as ``.csv`` (cell_type, one
+        column per marker, cells; 17 significant digits).  The means are ordered fp64 sums of ``preprocessor.intensity_full`` (ops.group_sums,
+        one call per image; the images' sums added in image order) divided by the counts; ops.heatmap_raster paints the table, the labels and
+        the colour bar are drawn on the host (plots.heatmap_figure).  Colours: colors.diverging_table (RdBu_r, not seaborn's vlag); any
+        number of cell types draws (the reference's figsize is 0 inches high for fewer than four).  Returns None and records
+        ``heatmap_stats``, one record per figure written by this rank.  Cell-sharded multi-rank runs: rank 0 computes and writes.
+        Tile-per-rank: every rank writes its own images' figures; the integrated one is rank 0's, from one all-reduce every rank enters."""
+        self._check_annotated("No annotations to generate heatmap")
+        self.heatmap_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        sums, counts, numbers, skipped, sums_ms = self._type_sums(columns=True, batch_wide=bool(integrate))
+        if integrate:
+            if self.rank == 0:
+                self._write_heatmap(f"{self.batch_id}_Integrated_heatmap", self._add_in_order(sums), counts.sum(axis=0), int(skipped.sum()), sums_ms)
+        else:
+            for i, num in enumerate(numbers):
+                self._write_heatmap(f"{self.batch_id}_heatmap_{num}", sums[i], counts[i], int(skipped[i]), sums_ms)
+        return None
 
-    def cell_type_composition(self, reduction=True):
-        """model.py:860-913 (pie charts): not drawn; the CSVs hold the labels."""
-        return self._skip("cell_type_composition")
+    def _write_heatmap(self, stem: str, sums: np.ndarray, counts: np.ndarray, skipped: int, sums_ms: float) -> None:
+        import time
+        from . import plots
+        present = np.nonzero(counts > 0)[0]
+        if len(present) == 0:
+            self.logger.log(f"Heat map {stem}: no cells, nothing drawn")
+            return
+        present = present[np.argsort(np.array([str(self.cell_types[k]) for k in present]), kind="stable")]      # np.unique's order
+        names = [str(self.cell_types[k]) for k in present]
+        sums, counts = np.ascontiguousarray(sums[present]), np.ascontiguousarray(counts[present])
+        width = sums.shape[1]
+        markers = [str(m) for m in self.channel_parser.markers]
+        markers = (markers + [f"channel {j}" for j in range(len(markers), width)])[:width]
+        dev = _lib.require_gpu()
+        lut = colors.diverging_table()
+        t0 = time.perf_counter()
+        rect, vmin, vmax = ops.heatmap_raster(torch.from_numpy(sums).to(dev), torch.from_numpy(counts).to(dev), torch.from_numpy(lut).to(dev),
+                                              self.HEATMAP_CELL, self.HEATMAP_GAP)
+        rect = rect.cpu().numpy()
+        raster_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        fig, lay = plots.heatmap_figure(rect, lut, vmin, vmax, names, markers, self.HEATMAP_CELL)
+        fig.save(os.path.join(self.result_dir, stem + ".png"))
+        with open(os.path.join(self.result_dir, stem + ".csv"), "w") as f:
+            f.write(plots.heatmap_csv(names, markers, sums / counts[:, None].astype(np.float64), counts))
+        draw_ms = (time.perf_counter() - t0) * 1e3
+        stats = {"file": stem + ".png", "rows": len(names), "columns": width, "cells": int(counts.sum()), "skipped": int(skipped), "vmin": vmin,
+                 "vmax": vmax, "rect": (lay["top"], lay["left"]), "sums_ms": sums_ms, "raster_ms": raster_ms, "draw_ms": draw_ms}
+        self.heatmap_stats.append(stats)
+        self.logger.log("Heat map {}: {} cell types x {} markers over {} cells ({} skipped), colour scale {:.4g} .. {:.4g}; sums {:.1f}, raster {:.1f}, "
+                        "drawing {:.1f} ms.".format(stats["file"], len(names), width, stats["cells"], skipped, vmin, vmax, sums_ms, raster_ms, draw_ms))
+
+    def cell_type_composition(self, reduction=True, integrate=False):
+        """model.py:861-912: the share of every ``self.cell_types`` entry as a pie (wedges in that order and in ``self.colors``, from
+        3 o'clock counter-clockwise as matplotlib's ax.pie; ops.pie_raster) with the reference's legend beside it
+        (plots.legend_texts: with ``reduction=False`` it prints the raw count x 100, as the reference does), as
+        ``{batch_id}_integrated_cell-type_composition.png`` / ``{batch_id}_cell-type_composition_{i}.png`` and a ``.csv`` (cell_type,
+        cells, fraction) beside each.  The counts are those of ops.group_sums.  Returns None and records ``composition_stats``, one record
+        per figure written by this rank; multi-rank runs as generate_heatmap."""
+        self._check_annotated("No annotations to analyze")
+        self.composition_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        _, counts, numbers, skipped, sums_ms = self._type_sums(columns=False, batch_wide=bool(integrate))
+        if integrate:
+            if self.rank == 0:
+                self._write_composition(f"{self.batch_id}_integrated_cell-type_composition", counts.sum(axis=0), reduction, int(skipped.sum()), sums_ms)
+        else:
+            for i, num in enumerate(numbers):
+                self._write_composition(f"{self.batch_id}_cell-type_composition_{num}", counts[i], reduction, int(skipped[i]), sums_ms)
+        return None
+
+    def _write_composition(self, stem: str, counts: np.ndarray, reduction: bool, skipped: int, sums_ms: float) -> None:
+        import time
+        from . import plots
+        names = [str(c) for c in self.cell_types]
+        palette = np.array(self.colors, dtype=np.uint8).reshape(-1, 3)
+        kept, rays = plots.pie_wedges(counts)
+        t0 = time.perf_counter()
+        if len(kept):
+            dev = _lib.require_gpu()
+            disc = ops.pie_raster(torch.from_numpy(rays).to(dev), torch.from_numpy(np.ascontiguousarray(palette[kept])).to(dev), self.PIE_CANVAS,
+                                  self.PIE_RADIUS).cpu().numpy()
+        else:      # no cell: no disc
+            disc = np.full((self.PIE_CANVAS, self.PIE_CANVAS, 3), 255, dtype=np.uint8)
+        raster_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        fig, lay = plots.pie_figure(disc, plots.legend_texts(names, counts, reduction), palette)
+        fig.save(os.path.join(self.result_dir, stem + ".png"))
+        with open(os.path.join(self.result_dir, stem + ".csv"), "w") as f:
+            f.write(plots.composition_csv(names, counts))
+        draw_ms = (time.perf_counter() - t0) * 1e3
+        stats = {"file": stem + ".png", "rows": len(names), "columns": 1, "wedges": int(len(kept)), "cells": int(counts.sum()), "skipped": int(skipped),
+                 "vmin": None, "vmax": None, "rect": (lay["top"], lay["left"]), "sums_ms": sums_ms, "raster_ms": raster_ms, "draw_ms": draw_ms}
+        self.composition_stats.append(stats)
+        self.logger.log("Composition {}: {} cells in {} of {} cell types ({} skipped); counts {:.1f}, raster {:.1f}, drawing {:.1f} ms.".format(
+            stats["file"], stats["cells"], len(kept), len(names), skipped, sums_ms, raster_ms, draw_ms))
 
     UMAP_CANVAS = (1200, 1600)      # rows, columns of {batch_id}_umap.png
     UMAP_RADIUS = 2

@@ -16,6 +16,7 @@ SILVER = (192, 192, 192)
 _GOLDEN = 0.618033988749895
 _LEVELS = (0.7, 0.8, 0.9, 1.0)
 _VIRIDIS = None
+_DIVERGING = None
 
 
 def get_colors(n: int) -> List[Tuple[int, int, int]]:
@@ -39,6 +40,18 @@ def viridis_table() -> np.ndarray:
     if _VIRIDIS is None:
         _VIRIDIS = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "viridis_u8.npy"))
     return _VIRIDIS
+
+
+def diverging_table() -> np.ndarray:
+    """(256, 3) uint8: the look-up table of the cell-type heat maps (Annotator.generate_heatmap): matplotlib's RdBu_r with each component
+    truncated to int(c * 255), in place of seaborn's 'vlag' (model.py:720), which the reference does not carry.  Shipped as data
+    (diverging_u8.csv, 256 lines "r,g,b", generated from matplotlib by tools/make_diverging_table.py)."""
+    global _DIVERGING
+    if _DIVERGING is None:
+        _DIVERGING = np.loadtxt(os.path.join(os.path.dirname(os.path.abspath(__file__)), "diverging_u8.csv"), dtype=np.uint8, delimiter=",")
+        if _DIVERGING.shape != (256, 3):
+            raise ValueError("diverging_u8.csv: expected 256 lines of three components, got an array of shape {}".format(_DIVERGING.shape))
+    return _DIVERGING
 
 
 def confidence_colors(conf: np.ndarray) -> np.ndarray:

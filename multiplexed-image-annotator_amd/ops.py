@@ -507,6 +507,65 @@ def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: 
     return out, int(skipped.value)
 
 
+# ------------------------------------------------------------------------------------------- per-cell-type statistics (csrc/celltype_stats.hip)
+GROUP_SUM_ROWS = 1024      # R of the summation tree (include/ribca_hip.h; kSumChunk of csrc/ribca_scratch.h)
+GROUP_SUM_MAX_COLUMNS = 1024
+GROUP_SUM_MAX_GROUPS = 256
+
+
+def group_sums_ws_bytes(n: int, c: int, groups: int) -> int:
+    return int(lib().ribca_group_sums_ws_bytes(int(n), int(c), int(groups)))
+
+
+def group_sums(x: torch.Tensor, group: torch.Tensor, groups: int, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """sums (groups, c) fp64 and counts (groups) int64 device tensors of the rows of the (n, c) fp64 device matrix x by their (n) int32 group
+    id, and the number of rows whose id lies outside [0, groups) (ignored).  The sums are a pure function of the inputs: include/ribca_hip.h
+    states the summation tree."""
+    if x.dtype != torch.float64 or x.dim() != 2 or group.dtype != torch.int32 or group.shape != (x.shape[0],):
+        raise ValueError("group_sums takes an (n, c) float64 matrix and (n) int32 group ids")
+    x, group = x.contiguous(), group.contiguous()
+    n, c = x.shape
+    sums = torch.empty((max(int(groups), 0), c), dtype=torch.float64, device=x.device)
+    counts = torch.empty(max(int(groups), 0), dtype=torch.int64, device=x.device)
+    if ws is None:
+        ws = _scratch(group_sums_ws_bytes(n, c, groups), x.device)
+    skipped = ctypes.c_int64(0)
+    check(lib().ribca_group_sums(ptr(x) if n else None, ptr(group) if n else None, n, c, int(groups), ptr(sums), ptr(counts), ctypes.byref(skipped),
+                                 ptr(ws), ws.numel(), stream_ptr()), "ribca_group_sums")
+    return sums, counts, int(skipped.value)
+
+
+def heatmap_raster(sums: torch.Tensor, counts: torch.Tensor, lut: torch.Tensor, cell: int, gap: int,
+                   ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, float, float]:
+    """(T cell, C cell, 3) uint8 device image of the (T, C) table of means sums / counts through the (256, 3) uint8 look-up table, and the
+    vmin, vmax of its colour scale (NaN, NaN when every count is 0).  include/ribca_hip.h states the pixels."""
+    if sums.dtype != torch.float64 or sums.dim() != 2 or counts.dtype != torch.int64 or counts.shape != (sums.shape[0],) or \
+            lut.dtype != torch.uint8 or lut.shape != (256, 3):
+        raise ValueError("heatmap_raster takes (T, C) float64 sums, (T) int64 counts and a (256, 3) uint8 table")
+    sums, counts, lut = sums.contiguous(), counts.contiguous(), lut.contiguous()
+    t, c = sums.shape
+    out = torch.empty((t * max(int(cell), 0), c * max(int(cell), 0), 3), dtype=torch.uint8, device=sums.device)
+    if ws is None:
+        ws = _scratch(lib().ribca_heatmap_raster_ws_bytes(t, c, int(cell), int(gap)), sums.device)
+    vmin, vmax = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    check(lib().ribca_heatmap_raster(ptr(sums), ptr(counts), t, c, ptr(lut), int(cell), int(gap), ptr(out), ctypes.byref(vmin), ctypes.byref(vmax),
+                                     ptr(ws), ws.numel(), stream_ptr()), "ribca_heatmap_raster")
+    return out, float(vmin.value), float(vmax.value)
+
+
+def pie_raster(rays: torch.Tensor, rgb: torch.Tensor, size: int, radius: int) -> torch.Tensor:
+    """(size, size, 3) uint8 device image: a disc of the given radius around the pixel (size // 2, size // 2) cut into m + 1 wedges by the
+    (m, 2) fp64 device rays (cos, sin; ascending angle), wedge w in rgb[w] ((m + 1, 3) uint8), white outside.  include/ribca_hip.h states the
+    pixels."""
+    if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 2 or rgb.dtype != torch.uint8 or rgb.shape != (rays.shape[0] + 1, 3):
+        raise ValueError("pie_raster takes (m, 2) float64 rays and (m + 1, 3) uint8 colours")
+    rays, rgb = rays.contiguous(), rgb.contiguous()
+    m = rays.shape[0]
+    out = torch.empty((max(int(size), 0), max(int(size), 0), 3), dtype=torch.uint8, device=rgb.device)
+    check(lib().ribca_pie_raster(ptr(rays) if m else None, m, ptr(rgb), int(size), int(radius), ptr(out), stream_ptr()), "ribca_pie_raster")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- HDBSCAN (extra cell types)
 def core_distance_ws_bytes(n: int, dim: int, min_samples: int) -> int:
     return int(lib().ribca_core_distance_ws_bytes(n, dim, min_samples))

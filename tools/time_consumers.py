@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Times the post-predict consumers on the GPU at the BASELINE config-3 size (4096 x 4096 mask, ~100 k cells): label painting
 (ribca_colorize), the 25-nearest-neighbour co-occurrence (ribca_knn_cooccurrence), the neighbourhood compositions and the tissue regions
-(PCA + k-means of csrc/regions.hip on the composition counts, 5 regions)."""
+(PCA + k-means of csrc/regions.hip on the composition counts, 5 regions), the per-cell-type table of the heat map (ribca_group_sums over a 15-column
+fp64 intensity table, 12 cell types) with the two rasterisers, and, for the same table, the reference's own Python loop (model.py:708-715) restated
+on the host."""
 import os
 import sys
 import time
@@ -35,3 +37,48 @@ for name, fn in (("colorize", lambda: ops.colorize(mask, ids, pal[tidx], colors.
     out = fn()
     torch.cuda.synchronize()
     print(f"{name}: {1e3 * (time.perf_counter() - t0):.1f} ms for {n} cells, 4096x4096 (host table upload included)")
+
+
+# ---- the cell-type heat map and composition pie (csrc/celltype_stats.hip) --------------------------------------------------------------
+from multiplexed_image_annotator_amd import plots  # noqa: E402
+
+names = np.array([f"type {k:02d}" for k in range(12)])
+intensity = rng.random((n, 15))
+x_dev, g_dev = torch.from_numpy(intensity).to(dev), torch.from_numpy(tidx.astype(np.int32)).to(dev)
+lut = torch.from_numpy(colors.diverging_table()).to(dev)
+
+
+def heatmap_table(upload):
+    xd, gd = (torch.from_numpy(intensity).to(dev), torch.from_numpy(tidx.astype(np.int32)).to(dev)) if upload else (x_dev, g_dev)
+    return ops.group_sums(xd, gd, 12)
+
+
+def pie():
+    kept, rays = plots.pie_wedges(np.bincount(tidx, minlength=12))
+    return ops.pie_raster(torch.from_numpy(rays).to(dev), torch.from_numpy(pal[kept]).to(dev), 480, 200)
+
+
+sums, counts, _ = heatmap_table(False)
+for name, fn in (("heat-map table (group_sums, 12 types x 15 channels), table on the device", lambda: heatmap_table(False)),
+                 ("heat-map table (group_sums), 12 MB host table uploaded", lambda: heatmap_table(True)),
+                 ("heat-map raster (12 x 15 cells of 24 px)", lambda: ops.heatmap_raster(sums, counts, lut, 24, 1)),
+                 ("pie raster (480 px, 12 wedges)", pie)):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    print(f"{name}: {1e3 * (time.perf_counter() - t0):.2f} ms for {n} cells")
+
+# the reference's loop for the same table: one list comprehension over all cells per cell type, np.mean of a list of rows
+annotations = names[tidx].tolist()
+rows = list(intensity)
+t0 = time.perf_counter()
+celltypes = np.unique(annotations)
+table = np.zeros((len(celltypes), 15))
+for j in range(len(celltypes)):
+    indices = [k for k in range(len(annotations)) if annotations[k] == celltypes[j]]
+    table[j] = np.mean([rows[k] for k in indices], axis=0)
+host_ms = 1e3 * (time.perf_counter() - t0)
+err = np.abs(table - (sums / counts[:, None]).cpu().numpy()).max()
+print(f"reference's Python loop for the same table (host, model.py:708-715): {host_ms:.1f} ms for {n} cells; max |difference| to the GPU table {err:.2e}")
