@@ -170,6 +170,27 @@ int ribca_colorize(const int32_t* mask, int64_t n_pixels, const int32_t* label_t
 int ribca_knn_cooccurrence(const double* x, const double* y, const int32_t* cell_type, int32_t n_cells, int32_t n_neighbors, int32_t n_types,
                            uint64_t* matrix, void* stream);
 
+/* The neighbour list of the same search: idx (n, k - 1) int32, idx[i][p - 1] = the cell of rank p = 1 .. k - 1 among the k nearest of cell i
+ * (rank 0, the cell itself -- or the lower index among exact duplicates -- is dropped), by (fp64 dx*dx + dy*dy, index).  Counting
+ * matrix[type[i]][type[idx[i][q]]] over the list gives ribca_knn_cooccurrence's matrix.  2 <= k <= min(n, 32). */
+int ribca_knn_neighbours(const double* x, const double* y, int32_t n, int32_t k, int32_t* idx, void* stream);
+
+/* ---- neighbourhood enrichment: the permutation null of the co-occurrence counts (csrc/enrichment.hip) ----------------
+ * The graph stays, the labels move: for the permutation with the global index p = p0 + j, j = 0 .. P - 1, cell i carries
+ * label_p(i) = cell_type[sigma_p(i)] and counts[j][label_p(i)][label_p(idx[i][q])] += 1 for q = 0 .. m - 1.  idx (n, m) int32 (entries outside
+ * [0, n) are skipped), cell_type (n) int32 (values outside [0, T) are skipped, as either end of a pair), counts (P, T, T) uint64, ACCUMULATED
+ * into (zero it first; call once per image of a group).  Integer atomics only: the result does not depend on the launch geometry.
+ * sigma_p is a keyed bijection of [0, n), a six-round balanced Feistel network with cycle walking, all in uint64:
+ *     s(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *     h = max(1, (bit_length(n - 1) + 1) / 2), mask = 2^h - 1;   K = s(s(s(seed) ^ image) ^ p)
+ *     one pass on v < 4^h: L = v >> h, R = v & mask; for r = 0 .. 5: f = s(K ^ ((r << 32) | R)) >> (64 - h), (L, R) = (R, L ^ f); v = (L << h) | R
+ *     sigma_p(i): v = i; repeat the pass until v < n (at most 4^h - n + 1 passes: the walk stays on the cycle of i).
+ * 1 <= n <= 2^30, 1 <= m <= 31, 1 <= T <= 64, image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31.  ws: ribca_nhood_perm_counts_ws_bytes(n, P) bytes (the
+ * shuffled labels of a batch of permutations, one byte per cell; 0 for arguments the entry point refuses).  Does not synchronise. */
+int64_t ribca_nhood_perm_counts_ws_bytes(int32_t n, int32_t P);
+int ribca_nhood_perm_counts(const int32_t* idx, const int32_t* cell_type, int32_t n, int32_t m, int32_t T, uint64_t seed, int32_t image, int64_t p0,
+                            int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The
@@ -323,6 +344,11 @@ int ribca_group_sums(const double* x, const int32_t* group, int32_t n, int32_t c
 int64_t ribca_heatmap_raster_ws_bytes(int32_t rows, int32_t cols, int32_t cell, int32_t gap);
 int ribca_heatmap_raster(const double* sums, const int64_t* counts, int32_t rows, int32_t cols, const uint8_t* lut, int32_t cell, int32_t gap, uint8_t* out,
                          double* vmin, double* vmax, void* ws, int64_t ws_bytes, void* stream);
+/* ribca_table_raster: values (rows, cols) fp64 -> out (rows cell, cols cell, 3) uint8 on a colour scale the CALLER gives: geometry, gap and index
+ * rule of ribca_heatmap_raster with vmin, vmax as arguments and the value clamped to [vmin, vmax] first; silver where the value is NaN; lut[128]
+ * for every number when vmax == vmin.  vmin <= vmax, both finite; the limits of ribca_heatmap_raster.  No workspace; does not synchronise. */
+int ribca_table_raster(const double* values, int32_t rows, int32_t cols, const uint8_t* lut, int32_t cell, int32_t gap, double vmin, double vmax,
+                       uint8_t* out, void* stream);
 /* ribca_pie_raster: rays (m, 2) fp64 = (cos, sin) of the m interior wedge boundaries in ascending angle, rgb (m + 1, 3) uint8 -> out (size, size, 3)
  * uint8.  The centre is the pixel (size / 2, size / 2); a pixel at the integer offset v = (dx to the right, dy UPWARDS) with
  * dx^2 + dy^2 <= radius^2 gets rgb[w], w = the number of rays a for which NOT (v < a); every other pixel is white.  The order of directions is that

@@ -4,7 +4,8 @@
 Runs marker parsing -> preprocess -> predict -> export_annotations -> tissue_region_analysis -> neighborhood_analysis ->
 colorize, as the reference does (main.py:19-28), its two plotting steps included: the integrated cell-type heat map and the cell-type
 composition pies are reduced and rasterised on the GPU and written with a CSV beside each PNG.  ``--min-cells N`` (N > 0) re-clusters the cells the vote left as "Others" into
-"Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+"Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  ``--enrichment-perms N`` (N > 0) adds the
+permutation z-scores of the neighbourhood matrix (Annotator.neighborhood_enrichment).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -33,6 +34,8 @@ def parse_args(argv=None):
     ap.add_argument('--bs', type=int, default=128)
     ap.add_argument('--cell-size', type=int, default=30)
     ap.add_argument('--n_jobs', type=int, default=0)
+    ap.add_argument('--enrichment-perms', type=int, default=0,
+                    help='label permutations of the neighbourhood-enrichment z-scores written beside the neighbourhood matrix (0 = off)')
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument('--image-path', type=str)
     grp.add_argument('--batch-csv', type=str)
@@ -54,7 +57,7 @@ def _setup():
             dist.init_process_group(os.environ.get("RIBCA_DIST_BACKEND", "nccl"))
 
 
-def _pipeline(annotator, bs, n_regions):
+def _pipeline(annotator, bs, n_regions, enrichment_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -74,6 +77,8 @@ def _pipeline(annotator, bs, n_regions):
             annotator.export_annotations()
     if n_cells >= 25:                               # the reference's kNN (25 neighbours) raises on smaller images
         annotator.neighborhood_analysis(integrate=True, normalize=True)
+        if enrichment_perms > 0:                    # not a step of the reference: the permutation z-scores of the same matrix
+            annotator.neighborhood_enrichment(n_perms=enrichment_perms, integrate=True)
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
     annotator.cell_type_composition(integrate=True)
@@ -81,7 +86,7 @@ def _pipeline(annotator, bs, n_regions):
 
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-        confidence, cell_size, cell_type_confidence, n_jobs):
+        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _setup()
@@ -96,7 +101,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions)
+    _pipeline(annotator, bs, n_regions, enrichment_perms)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -107,13 +112,13 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-              confidence, cell_size, cell_type_confidence, n_jobs=0):
+              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions)
+    _pipeline(annotator, bs, n_regions, enrichment_perms)
 
 
 def main(argv=None):
@@ -121,7 +126,7 @@ def main(argv=None):
     common = dict(marker_list_path=args.marker_list_path, device=args.device, main_dir=args.main_dir, batch_id=args.batch_id, bs=args.bs,
                   strict=args.strict, infer=args.infer, min_cells=args.min_cells, n_regions=args.n_regions, normalize=args.normalize,
                   blur=args.blur, amax=args.amax, confidence=args.confidence, cell_size=args.cell_size,
-                  cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs)
+                  cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

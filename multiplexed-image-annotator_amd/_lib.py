@@ -33,6 +33,10 @@ SIGNATURES = {
                                                c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ribca_colorize": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ribca_knn_cooccurrence": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ribca_knn_neighbours": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "ribca_nhood_perm_counts_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ribca_nhood_perm_counts": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                          c_int64, c_void_p]),
     "ribca_knn_compositions": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "ribca_region_gram_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_region_gram": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -67,6 +71,7 @@ SIGNATURES = {
     "ribca_heatmap_raster_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ribca_heatmap_raster": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, POINTER(c_double), POINTER(c_double),
                                        c_void_p, c_int64, c_void_p]),
+    "ribca_table_raster": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_double, c_double, c_void_p, c_void_p]),
     "ribca_pie_raster": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ribca_u16_to_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_gauss1d": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),

@@ -621,9 +621,12 @@ class Annotator(object):
 
     def neighborhood_analysis(self, n_neighbors=25, integrate=True, normalize=True):
         """Writes the same CSVs as the reference (``{batch_id}_integrated_neighborhood.csv`` or one ``{batch_id}_neighborhood_{i}.csv``
-        per image); the seaborn heat-map PNGs are not drawn."""
+        per image) and, beside each, the reference's heat map of the matrix as ``.png`` (spatial_methods.py:51-55, 110-114: seaborn's default scaling,
+        the matrix min .. max; ops.table_raster, colors.diverging_table, plots.heatmap_figure).  Records ``neighborhood_stats``, one record
+        per figure written by this rank."""
         if len(self.annotations) == 0:
             raise ValueError("No annotations")
+        self.neighborhood_stats = []
         groups = [list(range(self._n_images))] if integrate else [[i] for i in range(self._n_images)]
         for g, idx in enumerate(groups):
             m = self.neighborhood_matrix(idx, n_neighbors)
@@ -640,6 +643,101 @@ class Annotator(object):
                     f.write("cell_type," + "".join(f"{c}," for c in self.cell_types) + "\n")
                     for r, c in enumerate(self.cell_types):
                         f.write(f"{c}," + "".join(f"{m[r][j]:.3f}," for j in range(len(self.cell_types))) + "\n")
+                self.neighborhood_stats.append(self._write_table_figure(name[:-4], m, float(m.min()), float(m.max())))
+
+    def _write_table_figure(self, stem: str, table: np.ndarray, vmin: float, vmax: float) -> dict:
+        """``{stem}.png``: the (T, T) table over ``self.cell_types`` on the colour scale vmin .. vmax -- the rectangle from ops.table_raster, the
+        labels and the colour bar from plots.heatmap_figure.  Returns the record of the figure."""
+        import time
+        from . import plots
+        names = [str(c) for c in self.cell_types]
+        dev = _lib.require_gpu()
+        lut = colors.diverging_table()
+        t0 = time.perf_counter()
+        rect = ops.table_raster(torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(dev), torch.from_numpy(lut).to(dev), self.HEATMAP_CELL,
+                                self.HEATMAP_GAP, vmin, vmax).cpu().numpy()
+        raster_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        fig, lay = plots.heatmap_figure(rect, lut, vmin, vmax, names, names, self.HEATMAP_CELL)
+        fig.save(os.path.join(self.result_dir, stem + ".png"))
+        return {"file": stem + ".png", "rows": len(names), "columns": len(names), "vmin": vmin, "vmax": vmax, "rect": (lay["top"], lay["left"]),
+                "raster_ms": raster_ms, "draw_ms": (time.perf_counter() - t0) * 1e3}
+
+    # ---- neighbourhood enrichment: the permutation z-score beside the co-occurrence matrix (histoCAT, squidpy's nhood_enrichment) -----------------
+    def neighborhood_enrichment(self, n_neighbors=25, n_perms=1000, integrate=True):
+        """z = (observed - mean) / std of every (cell type, neighbour type) count of ``neighborhood_matrix`` against its permutation null: the
+        k-NN graph stays, the cell-type labels are shuffled within each image n_perms times (a keyed bijection per (seed, image number,
+        permutation); seed = RIBCA_ENRICH_SEED, default 0) and recounted on the GPU (ops.knn_neighbours, ops.nhood_perm_counts), the images of a
+        group accumulated into one (n_perms, T, T) tensor.  Per group (the batch with ``integrate``, else every image) it writes
+        ``{stem}_neighborhood_enrichment.csv`` (the layout of the neighbourhood CSV, z with three decimals), ``..._enrichment_table.csv`` (long
+        form: observed, null mean and std, z, and the permutations at or above / at or below the observed count) and ``..._enrichment.png`` (z on
+        the symmetric scale +- max |z|), with stem = ``{batch_id}_integrated`` or ``{batch_id}`` and the image number at the end as
+        neighborhood_analysis names its files.  Records ``enrichment_stats``, one record per group written by this rank (``knn_ms``: the observed
+        counts and the list; ``perm_ms``: the permutations; ``draw_ms``: everything after them on the host -- z-scores, both CSVs, raster and PNG).  Cell-sharded
+        multi-rank runs: rank 0 computes and writes.  Tile-per-rank: every rank does its own images; the integrated tensor takes one all-reduce
+        every rank enters (counts are exact in fp64)."""
+        import time
+        from . import enrichment
+        self._check_annotated("No annotations")
+        t = len(self.cell_types)
+        p = int(n_perms)
+        if p < 1:
+            raise ValueError(f"n_perms must be at least 1, got {n_perms}")
+        if t > ops.NHOOD_MAX_TYPES:
+            raise ValueError(f"neighborhood_enrichment handles at most {ops.NHOOD_MAX_TYPES} cell types, got {t}")
+        self.enrichment_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        seed = enrichment.default_seed()
+        n_local = len(self.annotations)
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        dev = _lib.require_gpu()
+        for g, members in enumerate(groups):
+            obs = torch.zeros((t, t), dtype=torch.int64, device=dev)
+            perm = torch.zeros((p, t, t), dtype=torch.int64, device=dev)
+            cells, knn_ms, perm_ms = 0, 0.0, 0.0
+            for i in members:
+                tab = self.preprocessor.cell_tables[i]
+                x = tab[:, 5].astype(np.float64) / tab[:, 6].astype(np.float64)
+                y = tab[:, 4].astype(np.float64) / tab[:, 6].astype(np.float64)
+                types = self._cell_type_ints(i)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                obs = ops.knn_cooccurrence(x, y, types, t, n_neighbors, out=obs)
+                idx = ops.knn_neighbours(x, y, n_neighbors)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                perm = ops.nhood_perm_counts(idx, types, t, seed, self._image_number(i), 0, p, out=perm)
+                torch.cuda.synchronize()
+                knn_ms += (t1 - t0) * 1e3
+                perm_ms += (time.perf_counter() - t1) * 1e3
+                cells += len(x)
+            both = torch.cat([obs.reshape(-1), perm.reshape(-1)]).cpu()
+            if integrate and self.tile_mode:
+                buf = dist.all_reduce_sum(torch.cat([both.to(torch.float64), torch.tensor([float(cells)], dtype=torch.float64)]))
+                both, cells = buf[:-1].to(torch.int64), int(buf[-1].item())
+            if integrate and self.rank != 0:
+                continue
+            both = both.numpy()
+            observed, null = both[:t * t].reshape(t, t), both[t * t:].reshape(p, t, t)
+            t0 = time.perf_counter()
+            stats = enrichment.z_scores(observed, null)
+            names = [str(c) for c in self.cell_types]
+            stem = f"{self.batch_id}_integrated_neighborhood_enrichment" if integrate else f"{self.batch_id}_neighborhood_enrichment"
+            tail = "" if integrate else f"_{self._image_number(members[0])}"
+            with open(os.path.join(self.result_dir, stem + tail + ".csv"), "w") as f:
+                f.write(enrichment.matrix_csv(names, stats["z"]))
+            with open(os.path.join(self.result_dir, stem + "_table" + tail + ".csv"), "w") as f:
+                f.write(enrichment.table_csv(names, observed, stats))
+            lim = enrichment.colour_limit(stats["z"])
+            fig = self._write_table_figure(stem + tail, stats["z"], -lim, lim)
+            draw_ms = (time.perf_counter() - t0) * 1e3
+            rec = {"file": fig["file"], "n": cells, "T": t, "P": p, "seed": seed, "neighbors": int(n_neighbors), "limit": lim, "rect": fig["rect"],
+                   "knn_ms": knn_ms, "perm_ms": perm_ms, "draw_ms": draw_ms}
+            self.enrichment_stats.append(rec)
+            self.logger.log("Neighbourhood enrichment {}: {} cells, {} cell types, {} permutations (seed {}), |z| up to {:.4g}; kNN {:.1f}, "
+                            "permutations {:.1f}, z-scores and drawing {:.1f} ms.".format(rec["file"], cells, t, p, seed, lim, knn_ms, perm_ms, draw_ms))
+        return None
 
     # ---- tissue regions (model.py:802-804 -> spatial_methods.py:133-198) -------------------------------------------------
     def tissue_region_analysis(self, n, method="kmeans"):

@@ -5,6 +5,7 @@
 //                   adds the chunks in ascending order.  The result is a pure function of the inputs.
 //   heatmap_raster  mean = sum / count per (row, column), min / max over the means that are not NaN, one thread per pixel: colour
 //                   lut[min(255, floor((mean - vmin) / (vmax - vmin) * 256))], silver where the mean is NaN, white in the gap around every cell.
+//   table_raster    the paint rule of heatmap_raster over a table of values with vmin / vmax given by the caller (values clamped to them).
 //   pie_raster      one thread per pixel: the wedge of a pixel of the disc is the number of boundary rays whose angle is <= the pixel's, the angles
 //                   compared by half plane and the sign of a cross product (no transcendental on the device).
 #include <cmath>
@@ -169,6 +170,34 @@ __global__ __launch_bounds__(256) void heatmap_paint_kernel(const double* __rest
   out[3 * p] = r, out[3 * p + 1] = g, out[3 * p + 2] = b;
 }
 
+// the paint rule with the scale given by the caller: the value clamped to [vmin, vmax], the middle entry when the scale is a point
+__global__ __launch_bounds__(256) void table_paint_kernel(const double* __restrict__ values, int rows, int cols, const uint8_t* __restrict__ lut, int cell,
+                                                          int gap, double vmin, double vmax, uint8_t* __restrict__ out) {
+  const long long W = (long long)cols * cell;
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= W * rows * cell) return;
+  const int py = (int)(p / W), px = (int)(p % W);
+  const int ly = py % cell, lx = px % cell;
+  uint8_t r = 255, g = 255, b = 255;
+  if (ly >= gap && ly < cell - gap && lx >= gap && lx < cell - gap) {
+    const double v = values[(size_t)(py / cell) * cols + px / cell];
+    if (v == v) {
+      int idx = 128;
+      if (vmax != vmin) {
+        const double c = v < vmin ? vmin : (v > vmax ? vmax : v);
+        const double d = c - vmin;
+        const double w = vmax - vmin;
+        const double q = floor(d / w * 256.0);      // three roundings: contraction is off
+        idx = q >= 255.0 ? 255 : (q >= 0.0 ? (int)q : 0);
+      }
+      r = lut[3 * idx], g = lut[3 * idx + 1], b = lut[3 * idx + 2];
+    } else {
+      r = g = b = 192;
+    }
+  }
+  out[3 * p] = r, out[3 * p + 1] = g, out[3 * p + 2] = b;
+}
+
 __device__ __forceinline__ int half_of(double vx, double vy) { return (vy > 0.0 || (vy == 0.0 && vx > 0.0)) ? 0 : 1; }
 
 __global__ __launch_bounds__(256) void pie_paint_kernel(const double* __restrict__ rays, int m, const uint8_t* __restrict__ rgb, int size, int radius,
@@ -265,6 +294,19 @@ int ribca_heatmap_raster(const double* sums, const int64_t* counts, int32_t rows
   HIP_TRY(hipStreamSynchronize(s));
   *vmin = host[0];
   *vmax = host[1];
+  return 0;
+}
+
+int ribca_table_raster(const double* values, int32_t rows, int32_t cols, const uint8_t* lut, int32_t cell, int32_t gap, double vmin, double vmax,
+                       uint8_t* out, void* stream) {
+  if (!values || !lut || !out) return fail("ribca_table_raster: NULL buffer");
+  if (rows < 1 || rows > GS_GROUPS_MAX || cols < 1 || cols > GS_C_MAX) return fail("ribca_table_raster: needs 1 <= rows <= 256, 1 <= cols <= 1024");
+  if (cell < 1 || cell > HM_CELL_MAX || gap < 0 || 2 * gap >= cell) return fail("ribca_table_raster: needs 1 <= cell <= 64, 0 <= 2 gap < cell");
+  if (!std::isfinite(vmin) || !std::isfinite(vmax) || vmin > vmax) return fail("ribca_table_raster: needs finite vmin <= vmax");
+  const long long pixels = (long long)rows * cell * cols * cell;
+  hipLaunchKernelGGL(table_paint_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, values, rows, cols, lut, cell, gap,
+                     vmin, vmax, out);
+  RIBCA_FINISH();
   return 0;
 }
 

@@ -1,0 +1,150 @@
+// The permutation null of the neighbourhood co-occurrence counts (Annotator.neighborhood_enrichment; histoCAT / squidpy's nhood_enrichment): the
+// k-NN graph of ribca_knn_neighbours stays fixed, the cell-type labels are shuffled within the image P times and the type pairs recounted.
+//   sigma_p          a keyed bijection of [0, n): six-round balanced Feistel network over 4^h >= n with cycle walking, the round function a
+//                    splitmix64 of (key, round, right half) -- counter-based, so any (permutation, cell) is computed on its own and a numpy loop
+//                    reproduces it (include/ribca_hip.h states it; tests/enrichment_numpy.py restates it).
+//   perm_labels      one thread per (cell, permutation of the batch): row j of the workspace = the n shuffled labels as bytes (255 = a label
+//                    outside [0, T): skipped later).  A row of 1e5 cells is 100 KB and stays in L2 for the gathers that follow.
+//   perm_count       one workgroup per (slab of EN_SLAB cells, permutation): each thread reads its cell's byte, gathers the bytes of its m neighbours
+//                    and counts the pairs into a T x T LDS histogram (<= 16 KiB) with integer atomics; then one 64-bit global atomic per non-zero
+//                    entry.  Integer sums: the result is independent of the order and of the launch geometry.
+// Evaluating sigma for every neighbour instead of once per cell would cost m + 1 times the hashing; the byte rows cost n bytes per permutation.
+#include <algorithm>
+
+#include "../../include/ribca_hip.h"
+#include "ribca_common.h"
+#include "ribca_scratch.h"
+#include "ribca_status.h"
+
+namespace ribca {
+namespace {
+
+constexpr int EN_M_MAX = 31;
+constexpr int EN_T_MAX = 64;
+constexpr int EN_N_MAX = 1 << 30;
+constexpr int EN_BATCH = 128;        // permutations whose label rows the workspace holds at once (gridDim.y of both kernels)
+constexpr int EN_SLAB = 4096;        // cells of one counting workgroup: 16 per thread, so a flush of T * T entries is paid once per 4096 * m counts
+constexpr uint8_t EN_SKIP = 255;     // no label: never indexes the histogram (T <= 64)
+
+static_assert(EN_T_MAX * EN_T_MAX * 4 <= 16 * 1024, "the LDS histogram");
+static_assert((long long)EN_SLAB * EN_M_MAX < (1ll << 32), "a 32-bit LDS count cannot wrap within one slab");
+
+int fail(const char* msg) { return api_fail(msg); }
+
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// sigma(i) under the key: the pass repeated until the value is back inside [0, n).  The walk follows the cycle of i in a bijection of [0, 4^h), so
+// it ends after at most 4^h - n + 1 passes; the loop is capped at 4^h all the same and reports n (no cell) if the cap is ever reached.
+__device__ __forceinline__ uint32_t feistel_walk(uint64_t key, uint32_t i, uint32_t n, int h) {
+  const uint64_t mask = (1ull << h) - 1;
+  const uint64_t domain = 1ull << (2 * h);
+  uint64_t v = i;
+  for (uint64_t pass = 0; pass < domain; ++pass) {
+    uint64_t L = v >> h, R = v & mask;
+#pragma unroll
+    for (uint64_t r = 0; r < 6; ++r) {
+      const uint64_t f = splitmix64(key ^ ((r << 32) | R)) >> (64 - h);
+      const uint64_t t = L ^ f;
+      L = R;
+      R = t;
+    }
+    v = (L << h) | R;
+    if (v < n) return (uint32_t)v;
+  }
+  return n;
+}
+
+// labels[j][i] = (uint8) cell_type[sigma_{p0 + j}(i)], EN_SKIP where that is outside [0, T): grid (ceil(n / 256), batch)
+__global__ __launch_bounds__(256) void perm_labels_kernel(const int32_t* __restrict__ cell_type, int n, int T, int h, uint64_t image_key, uint64_t p0,
+                                                          uint8_t* __restrict__ labels) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = splitmix64(image_key ^ (p0 + blockIdx.y));
+  const uint32_t src = feistel_walk(key, (uint32_t)i, (uint32_t)n, h);
+  uint8_t lab = EN_SKIP;
+  if (src < (uint32_t)n) {
+    const int32_t t = cell_type[src];
+    if ((unsigned)t < (unsigned)T) lab = (uint8_t)t;
+  }
+  labels[(size_t)blockIdx.y * n + i] = lab;
+}
+
+// counts[j][a][b] += the pairs (label(i), label(idx[i][q])) of the slab's cells: grid (ceil(n / EN_SLAB), batch)
+__global__ __launch_bounds__(256) void perm_count_kernel(const int32_t* __restrict__ idx, const uint8_t* __restrict__ labels, int n, int m, int T,
+                                                         unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int hist[EN_T_MAX * EN_T_MAX];
+  const int tid = threadIdx.x;
+  const int TT = T * T;
+  for (int e = tid; e < TT; e += 256) hist[e] = 0;
+  __syncthreads();
+  const uint8_t* __restrict__ lab = labels + (size_t)blockIdx.y * n;
+  const int first = blockIdx.x * EN_SLAB;
+  const int last = min(n, first + EN_SLAB);
+  for (int i = first + tid; i < last; i += 256) {
+    const unsigned a = lab[i];
+    if (a >= (unsigned)T) continue;
+    const int32_t* __restrict__ row = idx + (size_t)i * m;
+    for (int q = 0; q < m; ++q) {
+      const int32_t j = row[q];
+      if ((unsigned)j >= (unsigned)n) continue;
+      const unsigned b = lab[j];
+      if (b < (unsigned)T) atomicAdd(&hist[a * T + b], 1u);
+    }
+  }
+  __syncthreads();
+  unsigned long long* __restrict__ out = counts + (size_t)blockIdx.y * TT;
+  for (int e = tid; e < TT; e += 256)
+    if (hist[e]) atomicAdd(&out[e], (unsigned long long)hist[e]);
+}
+
+bool perm_sizes_ok(int n, int P) { return n >= 1 && n <= EN_N_MAX && P >= 1; }
+
+uint8_t* carve_perm(Carver& cv, int n, int P) { return cv.take<uint8_t>((size_t)std::min(P, EN_BATCH) * (size_t)n); }
+
+}  // namespace
+}  // namespace ribca
+
+using namespace ribca;
+
+extern "C" {
+
+int64_t ribca_nhood_perm_counts_ws_bytes(int32_t n, int32_t P) {
+  if (!perm_sizes_ok(n, P)) return 0;
+  Carver cv(nullptr);
+  carve_perm(cv, n, P);
+  return (int64_t)cv.off;
+}
+
+int ribca_nhood_perm_counts(const int32_t* idx, const int32_t* cell_type, int32_t n, int32_t m, int32_t T, uint64_t seed, int32_t image, int64_t p0,
+                            int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream) {
+  if (!idx || !cell_type || !counts || !ws) return fail("ribca_nhood_perm_counts: NULL buffer");
+  if (n < 1 || n > EN_N_MAX) return fail("ribca_nhood_perm_counts: needs 1 <= n <= 2^30");
+  if (m < 1 || m > EN_M_MAX) return fail("ribca_nhood_perm_counts: needs 1 <= m <= 31");
+  if (T < 1 || T > EN_T_MAX) return fail("ribca_nhood_perm_counts: needs 1 <= T <= 64");
+  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31)) return fail("ribca_nhood_perm_counts: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (ws_bytes < ribca_nhood_perm_counts_ws_bytes(n, P)) return fail("ribca_nhood_perm_counts: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  Carver cv(ws);
+  uint8_t* labels = carve_perm(cv, n, P);
+  int bits = 0;      // bit_length(n - 1)
+  while (bits < 32 && ((uint64_t)(n - 1) >> bits) != 0) ++bits;
+  const int h = std::max(1, (bits + 1) / 2);
+  const uint64_t image_key = splitmix64(splitmix64(seed) ^ (uint64_t)image);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+  for (int64_t j0 = 0; j0 < P; j0 += EN_BATCH) {      // the batches follow one another on the stream: the label rows are reused
+    const int batch = (int)std::min<int64_t>(EN_BATCH, P - j0);
+    hipLaunchKernelGGL(perm_labels_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, s, cell_type, n, T, h, image_key,
+                       (uint64_t)(p0 + j0), labels);
+    hipLaunchKernelGGL(perm_count_kernel, dim3((unsigned)((n + EN_SLAB - 1) / EN_SLAB), (unsigned)batch), dim3(256), 0, s, idx, labels, n, m, T,
+                       out + (size_t)j0 * T * T);
+  }
+  RIBCA_FINISH();
+  return 0;
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 //   enters at the bottom and bubbles up through statically indexed compare-exchanges), then neighbours 1..k-1 (0 is the cell
 //   itself) are counted into a per-workgroup LDS matrix and flushed with one atomic per non-zero entry (up to 32 cell types; above that,
 //   up to 254, each count is an integer atomic straight into the global matrix -- order-independent as well, so still deterministic).
+//   knn_cooccurrence_kernel<true> runs the same search and writes the list itself (the fixed graph of the permutation null, enrichment.hip).
 // n = 1e5 cells -> 1e10 distance evaluations, tens of milliseconds; the reference needs minutes.
 #include <algorithm>
 
@@ -21,14 +22,16 @@ constexpr int KNN_MAX_TYPES = 254;   // the most the uint8 index image of colori
 
 __device__ __forceinline__ bool knn_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
 
+// kList: the same search with the list kept instead of counted -- idx[q][p - 1] = the neighbour of rank p = 1 .. k - 1 (type, T and matrix unused)
+template <bool kList>
 __global__ __launch_bounds__(256) void knn_cooccurrence_kernel(const double* __restrict__ x, const double* __restrict__ y,
                                                                const int32_t* __restrict__ type, int n, int k, int T,
-                                                               unsigned long long* __restrict__ matrix) {
+                                                               unsigned long long* __restrict__ matrix, int32_t* __restrict__ idx) {
   __shared__ double sx[KNN_TILE], sy[KNN_TILE];
-  __shared__ unsigned int hist[KNN_TYPES * KNN_TYPES];
+  __shared__ unsigned int hist[kList ? 1 : KNN_TYPES * KNN_TYPES];
   const int tid = threadIdx.x;
   const int q = blockIdx.x * blockDim.x + tid;
-  const bool lds_hist = T <= KNN_TYPES;
+  const bool lds_hist = !kList && T <= KNN_TYPES;
   if (lds_hist)
     for (int i = tid; i < T * T; i += blockDim.x) hist[i] = 0;
   const double qx = q < n ? x[q] : 0.0, qy = q < n ? y[q] : 0.0;
@@ -63,6 +66,14 @@ __global__ __launch_bounds__(256) void knn_cooccurrence_kernel(const double* __r
         }
       }
     }
+  }
+  if constexpr (kList) {
+    if (q < n) {
+#pragma unroll
+      for (int p = 1; p < KNN_MAX; ++p)
+        if (p < k) idx[(size_t)q * (k - 1) + (p - 1)] = bi[p];
+    }
+    return;
   }
   if (q < n) {
     const int tq = type[q];
@@ -173,10 +184,17 @@ int launch_knn_compositions(const double* x, const double* y, const int32_t* typ
   return 0;
 }
 
+int launch_knn_neighbours(const double* x, const double* y, int n, int k, int32_t* idx, hipStream_t s) {
+  if (k < 2 || k > KNN_MAX || k > n) return 1;
+  hipLaunchKernelGGL(knn_cooccurrence_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, x, y, (const int32_t*)nullptr, n, k, 0,
+                     (unsigned long long*)nullptr, idx);
+  return 0;
+}
+
 int launch_knn_cooccurrence(const double* x, const double* y, const int32_t* type, int n, int k, int T, unsigned long long* matrix,
                             hipStream_t s) {
   if (k < 1 || k > KNN_MAX || T < 1 || T > KNN_MAX_TYPES || k > n) return 1;
-  hipLaunchKernelGGL(knn_cooccurrence_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, y, type, n, k, T, matrix);
+  hipLaunchKernelGGL(knn_cooccurrence_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, x, y, type, n, k, T, matrix, (int32_t*)nullptr);
   return 0;
 }
 

@@ -900,6 +900,15 @@ int ribca_knn_cooccurrence(const double* x, const double* y, const int32_t* cell
   return 0;
 }
 
+int ribca_knn_neighbours(const double* x, const double* y, int32_t n, int32_t k, int32_t* idx, void* stream) {
+  if (!x || !y || !idx) return fail("ribca_knn_neighbours: NULL buffer");
+  if (n <= 0) return fail("ribca_knn_neighbours: no cells");
+  if (k > n) return fail("ribca_knn_neighbours: k exceeds the number of cells");
+  if (launch_knn_neighbours(x, y, n, k, idx, (hipStream_t)stream)) return fail("ribca_knn_neighbours: k must be in [2, 32]");
+  RIBCA_FINISH();
+  return 0;
+}
+
 int ribca_knn_compositions(const double* x, const double* y, const int32_t* cell_type, int32_t n_cells, int32_t n_types, const int32_t* sizes,
                            int32_t n_sizes, uint16_t* counts, void* stream) {
   if (!x || !y || !cell_type || !sizes || !counts) return fail("ribca_knn_compositions: NULL buffer");

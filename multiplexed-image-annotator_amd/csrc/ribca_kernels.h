@@ -164,6 +164,9 @@ void launch_colorize(const int32_t* mask, long long npx, const int32_t* label_to
 int launch_knn_cooccurrence(const double* x, const double* y, const int32_t* type, int n, int k, int T, unsigned long long* matrix,
                             hipStream_t s);
 
+// the list itself: idx (n, k - 1) int32 = ranks 1 .. k - 1 of the same search; non-zero return = k outside [2, min(n, 32)]
+int launch_knn_neighbours(const double* x, const double* y, int n, int k, int32_t* idx, hipStream_t s);
+
 // per cell: counts of each type among its nearest list[l] other cells (k = list[last] + 1 <= 256 neighbours incl. itself)
 int launch_knn_compositions(const double* x, const double* y, const int32_t* type, int n, int k, int T, int n_lists, const int* list_dev,
                             uint16_t* counts, hipStream_t s);

@@ -251,6 +251,57 @@ def knn_cooccurrence(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
     return out
 
 
+def knn_neighbours(x: np.ndarray, y: np.ndarray, n_neighbors: int, device=None) -> torch.Tensor:
+    """(n, n_neighbors - 1) int32 device tensor: every cell's nearest other cells in rank order -- the list ``knn_cooccurrence`` counts over
+    (same fp64 search, ties towards the lower index, the cell itself dropped)."""
+    dev = device or _lib.require_gpu()
+    n = len(x)
+    if n_neighbors > n:
+        raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {n_neighbors}, n_samples_fit = {n}")
+    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
+    idx = torch.empty((n, max(int(n_neighbors) - 1, 0)), dtype=torch.int32, device=dev)
+    check(lib().ribca_knn_neighbours(ptr(xd), ptr(yd), n, int(n_neighbors), ptr(idx), stream_ptr()), "ribca_knn_neighbours")
+    return idx
+
+
+NHOOD_MAX_TYPES = 64      # the LDS histogram of csrc/enrichment.hip
+NHOOD_MAX_NEIGHBOURS = 31
+
+
+def nhood_perm_counts_ws_bytes(n: int, n_perms: int) -> int:
+    return int(lib().ribca_nhood_perm_counts_ws_bytes(int(n), int(n_perms)))
+
+
+def nhood_perm_counts(idx: torch.Tensor, cell_type: np.ndarray, n_types: int, seed: int, image: int, p0: int, n_perms: int,
+                      out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n_perms, n_types, n_types) int64 device tensor: the co-occurrence counts over the fixed (n, m) int32 device neighbour list ``idx`` under
+    the label permutations p0 .. p0 + n_perms - 1 of (seed, image) -- cell i carries cell_type[sigma_p(i)]; include/ribca_hip.h states sigma.
+    Accumulates into ``out`` when given (the images of a group).  Labels outside [0, n_types) raise before any launch."""
+    if idx.dtype != torch.int32 or idx.dim() != 2:
+        raise ValueError("nhood_perm_counts takes an (n, m) int32 neighbour list")
+    labels = np.ascontiguousarray(cell_type, dtype=np.int32)
+    n, m = idx.shape
+    if labels.shape != (n,):
+        raise ValueError(f"nhood_perm_counts: {labels.shape} labels for {n} cells")
+    if n and (int(labels.min()) < 0 or int(labels.max()) >= int(n_types)):
+        raise ValueError(f"nhood_perm_counts: labels must lie in [0, {int(n_types)}), got {int(labels.min())} .. {int(labels.max())}")
+    idx = idx.contiguous()
+    td = torch.from_numpy(labels).to(idx.device)
+    shape = (max(int(n_perms), 0), max(int(n_types), 0), max(int(n_types), 0))
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.int64, device=idx.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != idx.device:
+        raise ValueError(f"nhood_perm_counts: out must be an int64 tensor of shape {shape} on the device of idx")
+    if ws is None:
+        ws = _scratch(nhood_perm_counts_ws_bytes(n, n_perms), idx.device)
+    elif ws.dtype != torch.uint8 or ws.device != idx.device or not ws.is_contiguous():
+        raise ValueError("nhood_perm_counts: ws must be a contiguous uint8 tensor on the device of idx")
+    check(lib().ribca_nhood_perm_counts(ptr(idx), ptr(td), n, m, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0), int(n_perms), ptr(out),
+                                        ptr(ws), ws.numel(), stream_ptr()), "ribca_nhood_perm_counts")
+    return out
+
+
 TISSUE_NEIGHBOURHOODS = (10, 20, 30, 50, 75, 100, 150, 200)       # spatial_methods.py:155
 
 
@@ -551,6 +602,18 @@ def heatmap_raster(sums: torch.Tensor, counts: torch.Tensor, lut: torch.Tensor, 
     check(lib().ribca_heatmap_raster(ptr(sums), ptr(counts), t, c, ptr(lut), int(cell), int(gap), ptr(out), ctypes.byref(vmin), ctypes.byref(vmax),
                                      ptr(ws), ws.numel(), stream_ptr()), "ribca_heatmap_raster")
     return out, float(vmin.value), float(vmax.value)
+
+
+def table_raster(values: torch.Tensor, lut: torch.Tensor, cell: int, gap: int, vmin: float, vmax: float) -> torch.Tensor:
+    """(R cell, C cell, 3) uint8 device image of the (R, C) fp64 device table through the (256, 3) uint8 look-up table on the colour scale
+    vmin .. vmax the caller gives (values clamped to it, NaN silver, the middle entry when vmin == vmax).  include/ribca_hip.h states the pixels."""
+    if values.dtype != torch.float64 or values.dim() != 2 or lut.dtype != torch.uint8 or lut.shape != (256, 3):
+        raise ValueError("table_raster takes an (R, C) float64 table and a (256, 3) uint8 table of colours")
+    values, lut = values.contiguous(), lut.contiguous()
+    r, c = values.shape
+    out = torch.empty((r * max(int(cell), 0), c * max(int(cell), 0), 3), dtype=torch.uint8, device=values.device)
+    check(lib().ribca_table_raster(ptr(values), r, c, ptr(lut), int(cell), int(gap), float(vmin), float(vmax), ptr(out), stream_ptr()), "ribca_table_raster")
+    return out
 
 
 def pie_raster(rays: torch.Tensor, rgb: torch.Tensor, size: int, radius: int) -> torch.Tensor:

@@ -3,7 +3,8 @@
 (ribca_colorize), the 25-nearest-neighbour co-occurrence (ribca_knn_cooccurrence), the neighbourhood compositions and the tissue regions
 (PCA + k-means of csrc/regions.hip on the composition counts, 5 regions), the per-cell-type table of the heat map (ribca_group_sums over a 15-column
 fp64 intensity table, 12 cell types) with the two rasterisers, and, for the same table, the reference's own Python loop (model.py:708-715) restated
-on the host."""
+on the host; and the neighbourhood enrichment (csrc/enrichment.hip): the 25-nearest-neighbour list, 1000 label permutations over it at 12 cell types,
+and, for scale, the numpy restatement of tests/enrichment_numpy.py on 10 of the same permutations."""
 import os
 import sys
 import time
@@ -82,3 +83,29 @@ for j in range(len(celltypes)):
 host_ms = 1e3 * (time.perf_counter() - t0)
 err = np.abs(table - (sums / counts[:, None]).cpu().numpy()).max()
 print(f"reference's Python loop for the same table (host, model.py:708-715): {host_ms:.1f} ms for {n} cells; max |difference| to the GPU table {err:.2e}")
+
+
+# ---- the neighbourhood enrichment (csrc/knn.hip, csrc/enrichment.hip): n cells, k = 25, T = 12, P = 1000 ---------------------------------------
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import enrichment_numpy as EN  # noqa: E402
+
+PERMS = 1000
+idx = ops.knn_neighbours(x, y, 25)
+ws = torch.empty(ops.nhood_perm_counts_ws_bytes(n, PERMS), dtype=torch.uint8, device=dev)
+for name, fn in (("kNN list (k = 25, host table upload included)", lambda: ops.knn_neighbours(x, y, 25)),
+                 (f"{PERMS} label permutations counted (T = 12, m = 24, labels uploaded once per call)", lambda: ops.nhood_perm_counts(idx, tidx, 12, 0, 0, 0, PERMS, ws=ws))):
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"{name}: median {sorted(times)[2]:.1f} ms, min {min(times):.1f}, max {max(times):.1f} of 5 for {n} cells")
+idx_host = idx.cpu().numpy()
+t0 = time.perf_counter()
+want = EN.perm_counts(idx_host, tidx, 12, 0, 0, 0, 10)
+oracle_ms = 1e3 * (time.perf_counter() - t0)
+same = np.array_equal(out[:10].cpu().numpy(), want)
+print(f"numpy restatement, 10 permutations (host): {oracle_ms:.0f} ms -> {oracle_ms * PERMS / 10 / 1e3:.1f} s for {PERMS}; equal to the GPU counts: {same}")
