@@ -191,6 +191,20 @@ int64_t ribca_nhood_perm_counts_ws_bytes(int32_t n, int32_t P);
 int ribca_nhood_perm_counts(const int32_t* idx, const int32_t* cell_type, int32_t n, int32_t m, int32_t T, uint64_t seed, int32_t image, int64_t p0,
                             int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- co-occurrence by distance: cell-type pair counts per radius band (csrc/cooccurrence.hip) ---------------------------
+ * x, y (n) fp64, cell_type (n) int32 on the device; r2_host: a HOST array of the B squared radii, finite, non-negative and strictly increasing,
+ * 1 <= B <= 32 (passed to the kernel by value, as ribca_mae_impute takes present_host).  For every ORDERED pair i != j whose labels both lie in
+ * [0, T): counts[b][cell_type[i]][cell_type[j]] += 1 for the one band b with r2[b - 1] < d2 <= r2[b] (band 0: d2 <= r2[0]; a pair beyond
+ * r2[B - 1] is not counted; a label outside [0, T) is skipped on either side).  d2 in fp64 exactly as the k-NN search forms it: dx = x_i - x_j,
+ * d = dx * dx, d += dy * dy, every operation rounded on its own -- a numpy loop reproduces each comparison, ties at a band edge included (the <=
+ * is inclusive).  counts (B, T, T) uint64 is ACCUMULATED into (zero it first; call once per image of a group).  Integer atomics only: the result
+ * does not depend on the launch geometry.  While B T T 32-bit counters fit 64 KiB they are kept in LDS per workgroup, above that (up to T = 254)
+ * every count goes straight to counts.  1 <= n <= 2^21 (the work is quadratic: 4.4e12 pairs at the cap), 1 <= T <= 254.  No workspace:
+ * ribca_radial_pair_counts_ws_bytes returns 0 and ws may be NULL.  Does not synchronise. */
+int64_t ribca_radial_pair_counts_ws_bytes(int32_t n, int32_t T, int32_t B);
+int ribca_radial_pair_counts(const double* x, const double* y, const int32_t* cell_type, int32_t n, int32_t T, const double* r2_host, int32_t B,
+                             uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

@@ -5,7 +5,8 @@ Runs marker parsing -> preprocess -> predict -> export_annotations -> tissue_reg
 colorize, as the reference does (main.py:19-28), its two plotting steps included: the integrated cell-type heat map and the cell-type
 composition pies are reduced and rasterised on the GPU and written with a CSV beside each PNG.  ``--min-cells N`` (N > 0) re-clusters the cells the vote left as "Others" into
 "Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  ``--enrichment-perms N`` (N > 0) adds the
-permutation z-scores of the neighbourhood matrix (Annotator.neighborhood_enrichment).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+permutation z-scores of the neighbourhood matrix (Annotator.neighborhood_enrichment); ``--cooccurrence-bands N`` (N > 0) the cell-type pair counts
+and lifts in N distance bands of one cell size each (Annotator.cooccurrence_by_distance).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -36,6 +37,8 @@ def parse_args(argv=None):
     ap.add_argument('--n_jobs', type=int, default=0)
     ap.add_argument('--enrichment-perms', type=int, default=0,
                     help='label permutations of the neighbourhood-enrichment z-scores written beside the neighbourhood matrix (0 = off)')
+    ap.add_argument('--cooccurrence-bands', type=int, default=0,
+                    help='distance bands (one cell size wide each, at most 32) of the co-occurrence-by-distance table and figures (0 = off)')
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument('--image-path', type=str)
     grp.add_argument('--batch-csv', type=str)
@@ -57,7 +60,7 @@ def _setup():
             dist.init_process_group(os.environ.get("RIBCA_DIST_BACKEND", "nccl"))
 
 
-def _pipeline(annotator, bs, n_regions, enrichment_perms=0):
+def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -79,6 +82,9 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0):
         annotator.neighborhood_analysis(integrate=True, normalize=True)
         if enrichment_perms > 0:                    # not a step of the reference: the permutation z-scores of the same matrix
             annotator.neighborhood_enrichment(n_perms=enrichment_perms, integrate=True)
+    if cooccurrence_bands > 0:                      # nor is this one: which cell types meet at which distance (any number of cells)
+        from multiplexed_image_annotator_amd import cooccurrence
+        annotator.cooccurrence_by_distance(radii=cooccurrence.default_radii(annotator.cell_size, cooccurrence_bands), integrate=True)
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
     annotator.cell_type_composition(integrate=True)
@@ -86,7 +92,7 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0):
 
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0):
+        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _setup()
@@ -101,7 +107,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -112,13 +118,13 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0):
+              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands)
 
 
 def main(argv=None):
@@ -126,7 +132,8 @@ def main(argv=None):
     common = dict(marker_list_path=args.marker_list_path, device=args.device, main_dir=args.main_dir, batch_id=args.batch_id, bs=args.bs,
                   strict=args.strict, infer=args.infer, min_cells=args.min_cells, n_regions=args.n_regions, normalize=args.normalize,
                   blur=args.blur, amax=args.amax, confidence=args.confidence, cell_size=args.cell_size,
-                  cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms)
+                  cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms,
+                  cooccurrence_bands=args.cooccurrence_bands)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

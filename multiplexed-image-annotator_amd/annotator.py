@@ -128,6 +128,7 @@ class Annotator(object):
         self.tile_mode = dist.tile_mode(self.preprocessor._n_images, self.world_size, tile_env)
         self._loaded = False
         self.n_jobs = n_jobs
+        self.cell_size = cell_size
         self._n_images = 0
         self.min_cells = min_cells
         self.infer = infer
@@ -645,12 +646,14 @@ class Annotator(object):
                         f.write(f"{c}," + "".join(f"{m[r][j]:.3f}," for j in range(len(self.cell_types))) + "\n")
                 self.neighborhood_stats.append(self._write_table_figure(name[:-4], m, float(m.min()), float(m.max())))
 
-    def _write_table_figure(self, stem: str, table: np.ndarray, vmin: float, vmax: float) -> dict:
-        """``{stem}.png``: the (T, T) table over ``self.cell_types`` on the colour scale vmin .. vmax -- the rectangle from ops.table_raster, the
-        labels and the colour bar from plots.heatmap_figure.  Returns the record of the figure."""
+    def _write_table_figure(self, stem: str, table: np.ndarray, vmin: float, vmax: float, row_names=None, col_names=None) -> dict:
+        """``{stem}.png``: the (T, T) table over ``self.cell_types`` -- or the (rows, columns) table over ``row_names`` and ``col_names`` -- on the
+        colour scale vmin .. vmax: the rectangle from ops.table_raster, the labels and the colour bar from plots.heatmap_figure.  Returns the
+        record of the figure."""
         import time
         from . import plots
-        names = [str(c) for c in self.cell_types]
+        names = [str(c) for c in self.cell_types] if row_names is None else [str(c) for c in row_names]
+        columns = names if col_names is None else [str(c) for c in col_names]
         dev = _lib.require_gpu()
         lut = colors.diverging_table()
         t0 = time.perf_counter()
@@ -658,9 +661,9 @@ class Annotator(object):
                                 self.HEATMAP_GAP, vmin, vmax).cpu().numpy()
         raster_ms = (time.perf_counter() - t0) * 1e3
         t0 = time.perf_counter()
-        fig, lay = plots.heatmap_figure(rect, lut, vmin, vmax, names, names, self.HEATMAP_CELL)
+        fig, lay = plots.heatmap_figure(rect, lut, vmin, vmax, names, columns, self.HEATMAP_CELL)
         fig.save(os.path.join(self.result_dir, stem + ".png"))
-        return {"file": stem + ".png", "rows": len(names), "columns": len(names), "vmin": vmin, "vmax": vmax, "rect": (lay["top"], lay["left"]),
+        return {"file": stem + ".png", "rows": len(names), "columns": len(columns), "vmin": vmin, "vmax": vmax, "rect": (lay["top"], lay["left"]),
                 "raster_ms": raster_ms, "draw_ms": (time.perf_counter() - t0) * 1e3}
 
     # ---- neighbourhood enrichment: the permutation z-score beside the co-occurrence matrix (histoCAT, squidpy's nhood_enrichment) -----------------
@@ -737,6 +740,98 @@ class Annotator(object):
             self.enrichment_stats.append(rec)
             self.logger.log("Neighbourhood enrichment {}: {} cells, {} cell types, {} permutations (seed {}), |z| up to {:.4g}; kNN {:.1f}, "
                             "permutations {:.1f}, z-scores and drawing {:.1f} ms.".format(rec["file"], cells, t, p, seed, lim, knn_ms, perm_ms, draw_ms))
+        return None
+
+    # ---- co-occurrence by distance: which cell types attract or avoid each other at which physical distance ------------------------------------
+    def cooccurrence_by_distance(self, radii=None, integrate=True, anchors=None):
+        """Counts the ordered pairs of cells of one image by (radius band, cell type, neighbour type) on the GPU (ops.radial_pair_counts: band b
+        holds radii[b - 1] < distance <= radii[b], in pixels; ``radii`` None = cooccurrence.default_radii(cell_size)) and writes, per group (the
+        batch with ``integrate``, the images accumulated into one tensor, else every image), the long table ``{stem}.csv`` -- count, lift and
+        their cumulative forms, cooccurrence.table_csv -- and one ``{stem}_{slug}.png`` per anchor cell type: rows = the neighbour types,
+        columns = the bands labelled with their outer radius, log2 of the lift on the symmetric scale +- its largest finite magnitude, NaN (no
+        pair, or no such cell) silver.  stem = ``{batch_id}_integrated_cooccurrence`` or ``{batch_id}_cooccurrence`` with the image number at the
+        end of each name, as neighborhood_analysis places it; slug = cooccurrence.slug(cell type).  ``anchors``: cell-type names (or indices
+        into ``cell_types``); None = every cell type with at least one cell in the group.  Records ``cooccurrence_stats``, one record per group
+        written by this rank.  Cell-sharded multi-rank runs: rank 0 computes and writes.  Tile-per-rank: every rank does its own images; the
+        integrated tensor takes one all-reduce every rank enters (counts are exact in fp64 below 2^53; a group that could pass that is refused
+        before any collective)."""
+        import time
+        from . import cooccurrence, enrichment
+        self._check_annotated("No annotations")
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        r = cooccurrence.check_radii(cooccurrence.default_radii(self.cell_size) if radii is None else radii, ops.RADIAL_MAX_BANDS)
+        nb = len(r)
+        if t > 254:
+            raise ValueError(f"cooccurrence_by_distance handles at most 254 cell types, got {t}")
+        wanted = None
+        if anchors is not None:
+            wanted = []
+            for a in anchors:
+                k = names.index(a) if isinstance(a, str) and a in names else a
+                if isinstance(k, (str, bool)) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < t:
+                    raise ValueError(f"anchor {a!r} is not one of the cell types {names}")
+                wanted.append(int(k))
+        self.cooccurrence_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        n_local = len(self.annotations)
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        cap = ops.RADIAL_MAX_CELLS
+        sizes = [len(self.preprocessor.cell_ids[i]) for i in range(n_local)]
+        if any(n > cap for n in sizes):
+            raise ValueError(f"cooccurrence_by_distance takes at most {cap} cells per image, got {max(sizes)}")
+        # the same bound on every rank of a tile-per-rank run (each knows the number of images of the batch, not their sizes)
+        worst = self.preprocessor._n_images * cap * (cap - 1) if integrate and self.tile_mode else max([sum(sizes[i] * (sizes[i] - 1) for i in g) for g in groups] + [0])
+        if worst >= 2 ** 53:
+            raise ValueError(f"cooccurrence_by_distance: a group of up to {worst} pairs does not count exactly in fp64 (2^53)")
+        dev = _lib.require_gpu()
+        for g, members in enumerate(groups):
+            acc = torch.zeros((nb, t, t), dtype=torch.int64, device=dev)
+            present = np.zeros(t, dtype=np.int64)
+            cells, count_ms = 0, 0.0
+            for i in members:
+                tab = self.preprocessor.cell_tables[i]
+                if len(tab) == 0:      # an image without cells has no pair
+                    continue
+                x = tab[:, 5].astype(np.float64) / tab[:, 6].astype(np.float64)
+                y = tab[:, 4].astype(np.float64) / tab[:, 6].astype(np.float64)
+                types = self._cell_type_ints(i)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                acc = ops.radial_pair_counts(x, y, types, t, r, out=acc)      # pairs are only ever formed within one image
+                torch.cuda.synchronize()
+                count_ms += (time.perf_counter() - t0) * 1e3
+                present += np.bincount(types, minlength=t)[:t]
+                cells += len(x)
+            counts = acc.cpu().numpy()
+            if integrate and self.tile_mode:
+                buf = dist.all_reduce_sum(torch.cat([torch.from_numpy(counts.reshape(-1).astype(np.float64)), torch.from_numpy(present.astype(np.float64)),
+                                                     torch.tensor([float(cells)], dtype=torch.float64)])).numpy()
+                counts, present, cells = buf[:nb * t * t].astype(np.int64).reshape(nb, t, t), buf[nb * t * t:-1].astype(np.int64), int(buf[-1])
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            stem = f"{self.batch_id}_integrated_cooccurrence" if integrate else f"{self.batch_id}_cooccurrence"
+            tail = "" if integrate else f"_{self._image_number(members[0])}"
+            files = [stem + tail + ".csv"]
+            with open(os.path.join(self.result_dir, files[0]), "w") as f:
+                f.write(cooccurrence.table_csv(names, r, counts))
+            values = cooccurrence.figure_values(counts, cooccurrence.lift(counts))
+            labels = [f"{v:g}" for v in r]
+            figures = []
+            for a in (wanted if wanted is not None else [k for k in range(t) if present[k] > 0]):
+                table = np.ascontiguousarray(values[:, a, :].T)      # rows: neighbour types, columns: bands
+                lim = enrichment.colour_limit(table)
+                fig = self._write_table_figure(f"{stem}_{cooccurrence.slug(names[a])}{tail}", table, -lim, lim, row_names=names, col_names=labels)
+                figures.append({"file": fig["file"], "anchor": names[a], "limit": lim, "rect": fig["rect"]})
+                files.append(fig["file"])
+            draw_ms = (time.perf_counter() - t0) * 1e3
+            rec = {"file": files[0], "files": files, "figures": figures, "n": cells, "T": t, "B": nb, "radii": [float(v) for v in r],
+                   "pairs": int(counts.sum()), "count_ms": count_ms, "draw_ms": draw_ms}
+            self.cooccurrence_stats.append(rec)
+            self.logger.log("Co-occurrence by distance {}: {} cells, {} cell types, {} bands up to {:g} px, {} pairs in range, {} figures; counting {:.1f}, "
+                            "table and drawing {:.1f} ms.".format(files[0], cells, t, nb, float(r[-1]), rec["pairs"], len(figures), count_ms, draw_ms))
         return None
 
     # ---- tissue regions (model.py:802-804 -> spatial_methods.py:133-198) -------------------------------------------------

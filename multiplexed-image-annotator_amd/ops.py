@@ -302,6 +302,38 @@ def nhood_perm_counts(idx: torch.Tensor, cell_type: np.ndarray, n_types: int, se
     return out
 
 
+RADIAL_MAX_BANDS = 32      # the thresholds csrc/cooccurrence.hip takes by value
+RADIAL_MAX_CELLS = 1 << 21
+
+
+def radial_pair_counts_ws_bytes(n: int, n_types: int, n_bands: int) -> int:
+    return int(lib().ribca_radial_pair_counts_ws_bytes(int(n), int(n_types), int(n_bands)))
+
+
+def radial_pair_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, radii: Sequence[float], out: Optional[torch.Tensor] = None,
+                       device=None) -> torch.Tensor:
+    """(B, n_types, n_types) int64 device tensor: the ordered pairs of cells i != j by (band, type of i, type of j), band b holding the pairs with
+    radii[b - 1] < distance <= radii[b] (band 0 from distance 0; beyond the last radius: not counted; a label outside [0, n_types) is skipped).
+    ``radii`` in pixels, finite, non-negative and strictly increasing, at most RADIAL_MAX_BANDS of them; they are squared once in fp64 here and
+    the kernel compares fp64 squared distances with them.  Accumulates into ``out`` when given (the images of a group)."""
+    dev = device or _lib.require_gpu()
+    n = len(x)
+    r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    r2 = np.ascontiguousarray(r * r)
+    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
+    td = torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(dev)
+    shape = (len(r2), max(int(n_types), 0), max(int(n_types), 0))
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"radial_pair_counts: out must be a contiguous int64 tensor of shape {shape}")
+    ws = _scratch(radial_pair_counts_ws_bytes(n, n_types, len(r2)), dev)
+    check(lib().ribca_radial_pair_counts(ptr(xd), ptr(yd), ptr(td), n, int(n_types), r2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(r2),
+                                         ptr(out), ptr(ws), ws.numel(), stream_ptr()), "ribca_radial_pair_counts")
+    return out
+
+
 TISSUE_NEIGHBOURHOODS = (10, 20, 30, 50, 75, 100, 150, 200)       # spatial_methods.py:155
 
 

@@ -4,7 +4,10 @@
 (PCA + k-means of csrc/regions.hip on the composition counts, 5 regions), the per-cell-type table of the heat map (ribca_group_sums over a 15-column
 fp64 intensity table, 12 cell types) with the two rasterisers, and, for the same table, the reference's own Python loop (model.py:708-715) restated
 on the host; and the neighbourhood enrichment (csrc/enrichment.hip): the 25-nearest-neighbour list, 1000 label permutations over it at 12 cell types,
-and, for scale, the numpy restatement of tests/enrichment_numpy.py on 10 of the same permutations."""
+and, for scale, the numpy restatement of tests/enrichment_numpy.py on 10 of the same permutations; and the co-occurrence by distance
+(csrc/cooccurrence.hip): the cell-type pair counts in 16 and 32 bands of one cell size (30 px) at 12 cell types, one band reaching over the whole
+image (every pair in range: the weight of the LDS atomics), and as the host yardstick scipy's cKDTree.count_neighbors over the same radii and type
+pairs and the numpy oracle of tests/cooccurrence_numpy.py on the first 10 000 cells, scaled by n^2."""
 import os
 import sys
 import time
@@ -109,3 +112,52 @@ want = EN.perm_counts(idx_host, tidx, 12, 0, 0, 0, 10)
 oracle_ms = 1e3 * (time.perf_counter() - t0)
 same = np.array_equal(out[:10].cpu().numpy(), want)
 print(f"numpy restatement, 10 permutations (host): {oracle_ms:.0f} ms -> {oracle_ms * PERMS / 10 / 1e3:.1f} s for {PERMS}; equal to the GPU counts: {same}")
+
+
+# ---- the co-occurrence by distance (csrc/cooccurrence.hip): n cells, T = 12, bands of 30 px ---------------------------------------------------
+import cooccurrence_numpy as CO  # noqa: E402
+from multiplexed_image_annotator_amd import cooccurrence  # noqa: E402
+
+xd, yd = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+radial = {}
+for name, radii in (("16 bands up to 480 px", cooccurrence.default_radii(30, 16)), ("32 bands up to 960 px", cooccurrence.default_radii(30, 32)),
+                    ("1 band up to 480 px", [480.0]), ("1 band over the whole image (every pair counted)", [8192.0]),
+                    ("32 bands up to 8192 px (every pair counted)", np.linspace(256.0, 8192.0, 32))):
+    fn = lambda: ops.radial_pair_counts(xd, yd, tidx, 12, radii)  # noqa: E731
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    radial[name] = out.cpu().numpy()
+    print(f"radial pair counts, {name}: median {sorted(times)[2]:.1f} ms, min {min(times):.1f}, max {max(times):.1f} of 5 for {n} cells, "
+          f"{int(out.sum())} of {n * (n - 1)} pairs in range (host table upload included)")
+for bands in (16, 32):
+    radii = cooccurrence.default_radii(30, bands)
+    got = radial[f"{bands} bands up to {30 * bands} px"]
+    try:
+        from scipy.spatial import cKDTree
+        pts = np.stack([xd, yd], axis=1)
+        t0 = time.perf_counter()
+        trees = [cKDTree(pts[tidx == k]) for k in range(12)]
+        cum = np.zeros((bands, 12, 12), dtype=np.int64)
+        for a in range(12):
+            for c in range(a, 12):
+                cum[:, a, c] = cum[:, c, a] = trees[a].count_neighbors(trees[c], radii)
+            cum[:, a, a] -= int((tidx == a).sum())      # the tree counts every cell with itself
+        tree_ms = 1e3 * (time.perf_counter() - t0)
+        ring = np.diff(cum, axis=0, prepend=0)
+        print(f"scipy cKDTree.count_neighbors, {bands} radii x 78 type pairs (host, one thread): {tree_ms:.0f} ms; bands differ from the GPU counts in "
+              f"{int((ring != got).sum())} of {ring.size} entries (the tree compares distances its own way: a pair on a band edge may move)")
+    except ImportError:
+        print("scipy is not installed: no cKDTree yardstick")
+    m = 10000
+    t0 = time.perf_counter()
+    want = CO.pair_counts(xd[:m], yd[:m], tidx[:m], 12, radii * radii)
+    oracle_ms = 1e3 * (time.perf_counter() - t0)
+    same = np.array_equal(ops.radial_pair_counts(xd[:m], yd[:m], tidx[:m], 12, radii).cpu().numpy(), want)
+    print(f"numpy oracle, {bands} bands, first {m} cells (host): {oracle_ms:.0f} ms -> {oracle_ms * (n / m) ** 2 / 1e3:.1f} s at {n} cells; equal to the GPU "
+          f"counts of the same cells: {same}")
