@@ -191,6 +191,34 @@ int64_t ribca_nhood_perm_counts_ws_bytes(int32_t n, int32_t P);
 int ribca_nhood_perm_counts(const int32_t* idx, const int32_t* cell_type, int32_t n, int32_t m, int32_t T, uint64_t seed, int32_t image, int64_t p0,
                             int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- spatial autocorrelation of the markers: the numerators of Moran's I and Geary's C, observed and under a permutation null
+ * (csrc/autocorr.hip) ---------------------------------------------------------------------------------------------------
+ * z (n, C) fp64 row-major: the caller's CENTRED values (nothing is centred here); idx (n, m) int32: the neighbour list (entries outside [0, n)
+ * are skipped, by an unsigned compare before they index anything).  For the permutation with the global index p = p0 + j, j = 0 .. P - 1, cell i
+ * carries the whole row zp[i] = z[sigma_p(i)]: one sigma_p serves all channels, and it is the bijection stated under ribca_nhood_perm_counts
+ * with the same key K = s(s(s(seed) ^ image) ^ p).  ribca_autocorr_observed is the same with sigma the identity (zp = z).  Per channel c, every
+ * operation rounded on its own (no fma), no floating-point atomic anywhere:
+ *     s_i = (((+0.0 + zp[j_0][c]) + zp[j_1][c]) + ...)   over the valid entries j_q = idx[i][q], q ascending
+ *     g_i = (((+0.0 + d_0 * d_0) + d_1 * d_1) + ...),    d_q = zp[i][c] - zp[j_q][c], over the same entries
+ *     a_i = zp[i][c] * s_i
+ *     out[j][0][c] = TREE(a),  out[j][1][c] = TREE(g)     (the numerators of Moran's I and of Geary's C)
+ * TREE(v), R = 256: chunk k = the cells [k R, (k + 1) R), padded with +0.0 past n; eight rounds of adjacent pairs, v = v[0::2] + v[1::2], leave
+ * part[k]; the total is (((+0.0 + part[0]) + part[1]) + ...) over ALL chunks in ascending k.  In numpy:
+ *     v = np.concatenate([v, np.zeros(chunks * 256 - n)]).reshape(chunks, 256);  for r in range(8): v = v[:, 0::2] + v[:, 1::2]
+ *     total = 0.0;  for k in range(chunks): total = total + v[k, 0]
+ * out -- (2, C) fp64 for ribca_autocorr_observed, (P, 2, C) for ribca_autocorr_perm -- is OVERWRITTEN, not accumulated: the caller fixes the
+ * order in which the images of a group are added, as ribca_group_sums leaves it to the caller.  It is a pure function of (z, idx, seed, image, p):
+ * it does not depend on p0, P, the internal batch of permutations, the launch geometry, the workspace contents, the device or the stream.
+ * 1 <= n <= 2^30, 1 <= C <= 64, 1 <= m <= 31, image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31.  ws: ribca_autocorr_observed_ws_bytes(n, C) bytes (the
+ * chunk partials) and ribca_autocorr_perm_ws_bytes(n, C, P) bytes (the permuted rows of a batch of B = min(P, 32, max(1, 64 MiB / (8 n L)))
+ * permutations, kept in rows of L doubles -- L = the power of two >= C up to 16, the multiple of 16 >= C above -- and their chunk partials); both 0
+ * for arguments the entry point refuses.  Neither synchronises. */
+int64_t ribca_autocorr_observed_ws_bytes(int32_t n, int32_t C);
+int ribca_autocorr_observed(const double* z, const int32_t* idx, int32_t n, int32_t C, int32_t m, double* out, void* ws, int64_t ws_bytes, void* stream);
+int64_t ribca_autocorr_perm_ws_bytes(int32_t n, int32_t C, int32_t P);
+int ribca_autocorr_perm(const double* z, const int32_t* idx, int32_t n, int32_t C, int32_t m, uint64_t seed, int32_t image, int64_t p0, int32_t P,
+                        double* out, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- co-occurrence by distance: cell-type pair counts per radius band (csrc/cooccurrence.hip) ---------------------------
  * x, y (n) fp64, cell_type (n) int32 on the device; r2_host: a HOST array of the B squared radii, finite, non-negative and strictly increasing,
  * 1 <= B <= 32 (passed to the kernel by value, as ribca_mae_impute takes present_host).  For every ORDERED pair i != j whose labels both lie in

@@ -6,7 +6,8 @@ colorize, as the reference does (main.py:19-28), its two plotting steps included
 composition pies are reduced and rasterised on the GPU and written with a CSV beside each PNG.  ``--min-cells N`` (N > 0) re-clusters the cells the vote left as "Others" into
 "Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  ``--enrichment-perms N`` (N > 0) adds the
 permutation z-scores of the neighbourhood matrix (Annotator.neighborhood_enrichment); ``--cooccurrence-bands N`` (N > 0) the cell-type pair counts
-and lifts in N distance bands of one cell size each (Annotator.cooccurrence_by_distance).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+and lifts in N distance bands of one cell size each (Annotator.cooccurrence_by_distance); ``--autocorr-perms N`` (N > 0) Moran's I and Geary's C
+of every marker with an N-permutation null (Annotator.spatial_autocorrelation).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -37,6 +38,8 @@ def parse_args(argv=None):
     ap.add_argument('--n_jobs', type=int, default=0)
     ap.add_argument('--enrichment-perms', type=int, default=0,
                     help='label permutations of the neighbourhood-enrichment z-scores written beside the neighbourhood matrix (0 = off)')
+    ap.add_argument('--autocorr-perms', type=int, default=0,
+                    help="permutations of the null of Moran's I and Geary's C of every marker, Annotator.spatial_autocorrelation (0 = off)")
     ap.add_argument('--cooccurrence-bands', type=int, default=0,
                     help='distance bands (one cell size wide each, at most 32) of the co-occurrence-by-distance table and figures (0 = off)')
     grp = ap.add_mutually_exclusive_group(required=True)
@@ -60,7 +63,7 @@ def _setup():
             dist.init_process_group(os.environ.get("RIBCA_DIST_BACKEND", "nccl"))
 
 
-def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0):
+def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -82,6 +85,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
         annotator.neighborhood_analysis(integrate=True, normalize=True)
         if enrichment_perms > 0:                    # not a step of the reference: the permutation z-scores of the same matrix
             annotator.neighborhood_enrichment(n_perms=enrichment_perms, integrate=True)
+        if autocorr_perms > 0:                      # nor of this one: Moran's I and Geary's C of every marker over the same k-NN graph
+            annotator.spatial_autocorrelation(n_perms=autocorr_perms, integrate=True)
     if cooccurrence_bands > 0:                      # nor is this one: which cell types meet at which distance (any number of cells)
         from multiplexed_image_annotator_amd import cooccurrence
         annotator.cooccurrence_by_distance(radii=cooccurrence.default_radii(annotator.cell_size, cooccurrence_bands), integrate=True)
@@ -92,7 +97,7 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0):
+        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _setup()
@@ -107,7 +112,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -118,13 +123,13 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0):
+              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms)
 
 
 def main(argv=None):
@@ -133,7 +138,7 @@ def main(argv=None):
                   strict=args.strict, infer=args.infer, min_cells=args.min_cells, n_regions=args.n_regions, normalize=args.normalize,
                   blur=args.blur, amax=args.amax, confidence=args.confidence, cell_size=args.cell_size,
                   cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms,
-                  cooccurrence_bands=args.cooccurrence_bands)
+                  cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

@@ -37,6 +37,11 @@ SIGNATURES = {
     "ribca_nhood_perm_counts_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_nhood_perm_counts": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                                           c_int64, c_void_p]),
+    "ribca_autocorr_observed_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ribca_autocorr_observed": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_autocorr_perm_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ribca_autocorr_perm": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64,
+                                      c_void_p]),
     "ribca_radial_pair_counts_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_radial_pair_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_double), c_int32, c_void_p, c_void_p, c_int64,
                                            c_void_p]),

@@ -834,6 +834,103 @@ class Annotator(object):
                             "table and drawing {:.1f} ms.".format(files[0], cells, t, nb, float(r[-1]), rec["pairs"], len(figures), count_ms, draw_ms))
         return None
 
+    # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
+    def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
+        """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as
+        in neighborhood_analysis: n_neighbors - 1 neighbours per cell, unit weights), with a permutation null: the graph stays and whole rows of
+        ``preprocessor.intensity_full`` move within each image n_perms times (the keyed bijection of neighborhood_enrichment per (seed, image
+        number, permutation); seed = RIBCA_AUTOCORR_SEED, default 0).  Needs ``preprocess()`` only -- no classifier, no label.  Per image the
+        channel means are ordered fp64 sums (ops.group_sums) divided by the cells, the table is centred on the host, and the numerators come
+        from ops.autocorr_observed / ops.autocorr_perm (csrc/autocorr.hip; reproducible bits).  CENTRING IS PER IMAGE: with ``integrate`` the
+        statistic is the pooled within-image one -- the numerators and the sums of squares of the images are added from +0.0 in ascending
+        image number and n is the total number of cells -- so a slide-to-slide staining difference does not register as autocorrelation.
+        Per group (the batch, or every image) it writes ``{batch_id}_integrated_spatial_autocorr.csv`` or
+        ``{batch_id}_spatial_autocorr_{image number}.csv`` (autocorr.table_csv: one line per marker with I, C, the mean and population std of
+        their nulls, z and the permutations at or above / at or below the observed value; no p-value is formed) and ``.png`` beside it: rows =
+        the markers, columns = Moran I and 1 - Geary C on the fixed scale -1 .. 1, NaN (a constant channel) silver.  Records
+        ``autocorr_stats``, one record per group written by this rank (``knn_ms``: centring and the list; ``perm_ms``: the observed numerators
+        and the permutations; ``draw_ms``: statistics, CSV, raster and PNG).  Cell-sharded multi-rank runs: rank 0 computes and writes.
+        Tile-per-rank: every rank does its own images; the integrated table takes one all-reduce every rank enters, each image's numbers in
+        that image's row and +0.0 elsewhere, so they arrive as computed and rank 0 writes the bytes of a single-rank run."""
+        import time
+        from . import autocorr
+        full = self.preprocessor.intensity_full
+        n_local = self._n_images
+        if (len(full) == 0 or n_local == 0) and not (self.tile_mode and self.preprocessor._n_images > 0):
+            raise ValueError("No intensities: call preprocess() first")
+        p = int(n_perms)
+        if p < 1:
+            raise ValueError(f"n_perms must be at least 1, got {n_perms}")
+        k = int(n_neighbors)
+        tables = [None if full[i] is None else np.ascontiguousarray(full[i], dtype=np.float64) for i in range(n_local)]      # None: an image without cells
+        width = next((t.shape[1] for t in tables if t is not None), len(self.channel_parser.markers))
+        if width > ops.AUTOCORR_MAX_CHANNELS:
+            raise ValueError(f"spatial_autocorrelation handles at most {ops.AUTOCORR_MAX_CHANNELS} channels, got {width}")
+        for i, t in enumerate(tables):
+            if t is None or len(t) < k:
+                raise ValueError(f"image {self._image_number(i)} has {0 if t is None else len(t)} cells, fewer than n_neighbors = {k}")
+            if t.ndim != 2 or t.shape[1] != width or len(t) != len(self.preprocessor.cell_tables[i]):
+                raise ValueError(f"image {self._image_number(i)}: an intensity table of shape {t.shape} for {len(self.preprocessor.cell_tables[i])} "
+                                 f"cells of {width} channels")
+        self.autocorr_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        seed = autocorr.default_seed()
+        markers = [str(m) for m in self.channel_parser.markers]
+        markers = (markers + [f"channel {j}" for j in range(len(markers), width)])[:width]
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        dev = _lib.require_gpu()
+        one = (p + 1) * 2 * width      # per image: the observed and the permuted numerators, then the sums of squares, then the cells
+        for members in groups:
+            rows = np.zeros((len(members), one + width + 1), dtype=np.float64)
+            knn_ms, perm_ms = 0.0, 0.0
+            for r, i in enumerate(members):
+                tab = self.preprocessor.cell_tables[i]
+                x = tab[:, 5].astype(np.float64) / tab[:, 6].astype(np.float64)
+                y = tab[:, 4].astype(np.float64) / tab[:, 6].astype(np.float64)
+                n = len(tables[i])
+                group = torch.zeros(n, dtype=torch.int32, device=dev)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                mean = ops.group_sums(torch.from_numpy(tables[i]).to(dev), group, 1)[0].cpu().numpy()[0] / float(n)
+                z = tables[i] - mean
+                rows[r, one:one + width] = ops.group_sums(torch.from_numpy(z * z).to(dev), group, 1)[0].cpu().numpy()[0]
+                zd = torch.from_numpy(z).to(dev)
+                idx = ops.knn_neighbours(x, y, k)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                obs = ops.autocorr_observed(zd, idx)
+                null = ops.autocorr_perm(zd, idx, seed, self._image_number(i), 0, p)
+                rows[r, :one] = torch.cat([obs.reshape(-1), null.reshape(-1)]).cpu().numpy()
+                knn_ms += (t1 - t0) * 1e3
+                perm_ms += (time.perf_counter() - t1) * 1e3
+                rows[r, -1] = float(n)
+            if integrate and self.tile_mode:
+                buf = np.zeros((self.preprocessor._n_images, rows.shape[1]), dtype=np.float64)
+                for r, i in enumerate(members):
+                    buf[self._image_number(i)] = rows[r]
+                rows = dist.all_reduce_sum(torch.from_numpy(buf)).numpy()
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            total = self._add_in_order(rows)
+            cells = int(total[-1])
+            stats = autocorr.statistics(total[:2 * width].reshape(2, width), total[2 * width:one].reshape(p, 2, width), total[one:one + width], cells, k - 1)
+            stem = f"{self.batch_id}_integrated_spatial_autocorr" if integrate else f"{self.batch_id}_spatial_autocorr_{self._image_number(members[0])}"
+            with open(os.path.join(self.result_dir, stem + ".csv"), "w") as f:
+                f.write(autocorr.table_csv(markers, cells, stats))
+            fig = self._write_table_figure(stem, autocorr.figure_values(stats), -1.0, 1.0, row_names=markers, col_names=["Moran I", "1 - Geary C"])
+            draw_ms = (time.perf_counter() - t0) * 1e3
+            rec = {"file": fig["file"], "n": cells, "C": width, "P": p, "seed": seed, "neighbors": k, "rect": fig["rect"], "knn_ms": knn_ms,
+                   "perm_ms": perm_ms, "draw_ms": draw_ms}
+            self.autocorr_stats.append(rec)
+            finite = stats["i"][np.isfinite(stats["i"])]
+            self.logger.log("Spatial autocorrelation {}: {} cells, {} markers, {} permutations (seed {}), Moran's I {:.4g} .. {:.4g}; centring and kNN "
+                            "{:.1f}, permutations {:.1f}, statistics and drawing {:.1f} ms.".format(
+                                rec["file"], cells, width, p, seed, float(finite.min()) if finite.size else float("nan"),
+                                float(finite.max()) if finite.size else float("nan"), knn_ms, perm_ms, draw_ms))
+        return None
+
     # ---- tissue regions (model.py:802-804 -> spatial_methods.py:133-198) -------------------------------------------------
     def tissue_region_analysis(self, n, method="kmeans"):
         """Per-cell region labels from the cell-type make-up of each cell's 10 ... 200 nearest neighbours.  The 201-NN search and the

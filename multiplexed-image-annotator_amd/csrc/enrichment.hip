@@ -1,8 +1,6 @@
 // The permutation null of the neighbourhood co-occurrence counts (Annotator.neighborhood_enrichment; histoCAT / squidpy's nhood_enrichment): the
 // k-NN graph of ribca_knn_neighbours stays fixed, the cell-type labels are shuffled within the image P times and the type pairs recounted.
-//   sigma_p          a keyed bijection of [0, n): six-round balanced Feistel network over 4^h >= n with cycle walking, the round function a
-//                    splitmix64 of (key, round, right half) -- counter-based, so any (permutation, cell) is computed on its own and a numpy loop
-//                    reproduces it (include/ribca_hip.h states it; tests/enrichment_numpy.py restates it).
+//   sigma_p          the keyed bijection of [0, n) of ribca_perm.h (include/ribca_hip.h states it; tests/enrichment_numpy.py restates it).
 //   perm_labels      one thread per (cell, permutation of the batch): row j of the workspace = the n shuffled labels as bytes (255 = a label
 //                    outside [0, T): skipped later).  A row of 1e5 cells is 100 KB and stays in L2 for the gathers that follow.
 //   perm_count       one workgroup per (slab of EN_SLAB cells, permutation): each thread reads its cell's byte, gathers the bytes of its m neighbours
@@ -13,6 +11,7 @@
 
 #include "../../include/ribca_hip.h"
 #include "ribca_common.h"
+#include "ribca_perm.h"
 #include "ribca_scratch.h"
 #include "ribca_status.h"
 
@@ -31,40 +30,12 @@ static_assert((long long)EN_SLAB * EN_M_MAX < (1ll << 32), "a 32-bit LDS count c
 
 int fail(const char* msg) { return api_fail(msg); }
 
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// sigma(i) under the key: the pass repeated until the value is back inside [0, n).  The walk follows the cycle of i in a bijection of [0, 4^h), so
-// it ends after at most 4^h - n + 1 passes; the loop is capped at 4^h all the same and reports n (no cell) if the cap is ever reached.
-__device__ __forceinline__ uint32_t feistel_walk(uint64_t key, uint32_t i, uint32_t n, int h) {
-  const uint64_t mask = (1ull << h) - 1;
-  const uint64_t domain = 1ull << (2 * h);
-  uint64_t v = i;
-  for (uint64_t pass = 0; pass < domain; ++pass) {
-    uint64_t L = v >> h, R = v & mask;
-#pragma unroll
-    for (uint64_t r = 0; r < 6; ++r) {
-      const uint64_t f = splitmix64(key ^ ((r << 32) | R)) >> (64 - h);
-      const uint64_t t = L ^ f;
-      L = R;
-      R = t;
-    }
-    v = (L << h) | R;
-    if (v < n) return (uint32_t)v;
-  }
-  return n;
-}
-
 // labels[j][i] = (uint8) cell_type[sigma_{p0 + j}(i)], EN_SKIP where that is outside [0, T): grid (ceil(n / 256), batch)
 __global__ __launch_bounds__(256) void perm_labels_kernel(const int32_t* __restrict__ cell_type, int n, int T, int h, uint64_t image_key, uint64_t p0,
                                                           uint8_t* __restrict__ labels) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint64_t key = splitmix64(image_key ^ (p0 + blockIdx.y));
+  const uint64_t key = perm_key(image_key, p0 + blockIdx.y);
   const uint32_t src = feistel_walk(key, (uint32_t)i, (uint32_t)n, h);
   uint8_t lab = EN_SKIP;
   if (src < (uint32_t)n) {
@@ -131,10 +102,8 @@ int ribca_nhood_perm_counts(const int32_t* idx, const int32_t* cell_type, int32_
   hipStream_t s = (hipStream_t)stream;
   Carver cv(ws);
   uint8_t* labels = carve_perm(cv, n, P);
-  int bits = 0;      // bit_length(n - 1)
-  while (bits < 32 && ((uint64_t)(n - 1) >> bits) != 0) ++bits;
-  const int h = std::max(1, (bits + 1) / 2);
-  const uint64_t image_key = splitmix64(splitmix64(seed) ^ (uint64_t)image);
+  const int h = perm_half_bits(n);
+  const uint64_t image_key = perm_image_key(seed, image);
   unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
   for (int64_t j0 = 0; j0 < P; j0 += EN_BATCH) {      // the batches follow one another on the stream: the label rows are reused
     const int batch = (int)std::min<int64_t>(EN_BATCH, P - j0);

@@ -334,6 +334,58 @@ def radial_pair_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_ty
     return out
 
 
+AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
+AUTOCORR_MAX_NEIGHBOURS = 31
+
+
+def autocorr_observed_ws_bytes(n: int, c: int) -> int:
+    return int(lib().ribca_autocorr_observed_ws_bytes(int(n), int(c)))
+
+
+def autocorr_perm_ws_bytes(n: int, c: int, n_perms: int) -> int:
+    return int(lib().ribca_autocorr_perm_ws_bytes(int(n), int(c), int(n_perms)))
+
+
+def _autocorr_args(what: str, z: torch.Tensor, idx: torch.Tensor, ws: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    if z.dtype != torch.float64 or z.dim() != 2 or idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != z.shape[0]:
+        raise ValueError(f"{what} takes an (n, C) float64 table of centred values and an (n, m) int32 neighbour list")
+    if idx.device != z.device:
+        raise ValueError(f"{what}: the table and the neighbour list must be on the same device")
+    if ws is not None and (ws.dtype != torch.uint8 or ws.device != z.device or not ws.is_contiguous()):
+        raise ValueError(f"{what}: ws must be a contiguous uint8 tensor on the device of z")
+    if not bool(torch.isfinite(z).all()):
+        raise ValueError(f"{what}: the table holds values that are not finite")
+    return z.contiguous(), idx.contiguous()
+
+
+def autocorr_observed(z: torch.Tensor, idx: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(2, C) fp64 device tensor: the numerators of Moran's I (row 0: the sum over the cells of z[i] times the sum of its neighbours' z) and of
+    Geary's C (row 1: the sum of the squared differences to the neighbours) of every column of the (n, C) fp64 device table ``z`` of CENTRED
+    values over the fixed (n, m) int32 device neighbour list ``idx``.  A pure function of its inputs: include/ribca_hip.h states the order of
+    every addition.  Values that are not finite raise before any launch."""
+    z, idx = _autocorr_args("autocorr_observed", z, idx, ws)
+    n, c = z.shape
+    out = torch.empty((2, c), dtype=torch.float64, device=z.device)
+    if ws is None:
+        ws = _scratch(autocorr_observed_ws_bytes(n, c), z.device)
+    check(lib().ribca_autocorr_observed(ptr(z), ptr(idx), n, c, idx.shape[1], ptr(out), ptr(ws), ws.numel(), stream_ptr()), "ribca_autocorr_observed")
+    return out
+
+
+def autocorr_perm(z: torch.Tensor, idx: torch.Tensor, seed: int, image: int, p0: int, n_perms: int, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n_perms, 2, C) fp64 device tensor: the numerators of ``autocorr_observed`` under the permutations p0 .. p0 + n_perms - 1 of (seed, image)
+    -- cell i carries the whole row z[sigma_p(i)], one bijection for all channels (the sigma of ``nhood_perm_counts``, keyed the same way).
+    Slice j depends on (z, idx, seed, image, p0 + j) alone."""
+    z, idx = _autocorr_args("autocorr_perm", z, idx, ws)
+    n, c = z.shape
+    out = torch.empty((max(int(n_perms), 0), 2, c), dtype=torch.float64, device=z.device)
+    if ws is None:
+        ws = _scratch(autocorr_perm_ws_bytes(n, c, n_perms), z.device)
+    check(lib().ribca_autocorr_perm(ptr(z), ptr(idx), n, c, idx.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0), int(n_perms), ptr(out),
+                                    ptr(ws), ws.numel(), stream_ptr()), "ribca_autocorr_perm")
+    return out
+
+
 TISSUE_NEIGHBOURHOODS = (10, 20, 30, 50, 75, 100, 150, 200)       # spatial_methods.py:155
 
 

@@ -7,7 +7,9 @@ on the host; and the neighbourhood enrichment (csrc/enrichment.hip): the 25-near
 and, for scale, the numpy restatement of tests/enrichment_numpy.py on 10 of the same permutations; and the co-occurrence by distance
 (csrc/cooccurrence.hip): the cell-type pair counts in 16 and 32 bands of one cell size (30 px) at 12 cell types, one band reaching over the whole
 image (every pair in range: the weight of the LDS atomics), and as the host yardstick scipy's cKDTree.count_neighbors over the same radii and type
-pairs and the numpy oracle of tests/cooccurrence_numpy.py on the first 10 000 cells, scaled by n^2."""
+pairs and the numpy oracle of tests/cooccurrence_numpy.py on the first 10 000 cells, scaled by n^2; and the spatial autocorrelation
+(csrc/autocorr.hip): the observed numerators of Moran's I and Geary's C of the 15-column table over the 25-nearest-neighbour list, 1000 row
+permutations, and the numpy restatement of tests/autocorr_numpy.py on 10 of the same permutations."""
 import os
 import sys
 import time
@@ -161,3 +163,28 @@ for bands in (16, 32):
     same = np.array_equal(ops.radial_pair_counts(xd[:m], yd[:m], tidx[:m], 12, radii).cpu().numpy(), want)
     print(f"numpy oracle, {bands} bands, first {m} cells (host): {oracle_ms:.0f} ms -> {oracle_ms * (n / m) ** 2 / 1e3:.1f} s at {n} cells; equal to the GPU "
           f"counts of the same cells: {same}")
+
+
+# ---- the spatial autocorrelation (csrc/autocorr.hip): n cells, C = 15, k = 25, P = 1000 -----------------------------------------------------------
+import autocorr_numpy as AN  # noqa: E402
+
+z_host = intensity - intensity.mean(axis=0)
+z_dev = torch.from_numpy(z_host).to(dev)
+ws = torch.empty(ops.autocorr_perm_ws_bytes(n, 15, PERMS), dtype=torch.uint8, device=dev)
+for name, fn in (("autocorrelation numerators, observed (C = 15, m = 24, table on the device)", lambda: ops.autocorr_observed(z_dev, idx)),
+                 (f"autocorrelation numerators, {PERMS} row permutations (C = 15, m = 24, table on the device, {ws.numel() / 2 ** 20:.1f} MiB workspace)",
+                  lambda: ops.autocorr_perm(z_dev, idx, 0, 0, 0, PERMS, ws=ws))):
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"{name}: median {sorted(times)[2]:.1f} ms, min {min(times):.1f}, max {max(times):.1f} of 5 for {n} cells")
+t0 = time.perf_counter()
+want = AN.perm(z_host, idx_host, 0, 0, 0, 10)
+oracle_ms = 1e3 * (time.perf_counter() - t0)
+same = out[:10].cpu().numpy().tobytes() == want.tobytes()
+print(f"numpy restatement, 10 row permutations (host): {oracle_ms:.0f} ms -> {oracle_ms * PERMS / 10 / 1e3:.1f} s for {PERMS}; bit-equal to the GPU numerators: {same}")
