@@ -219,6 +219,30 @@ int64_t ribca_autocorr_perm_ws_bytes(int32_t n, int32_t C, int32_t P);
 int ribca_autocorr_perm(const double* z, const int32_t* idx, int32_t n, int32_t C, int32_t m, uint64_t seed, int32_t image, int64_t p0, int32_t P,
                         double* out, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- local indicators of spatial association: per cell and channel the neighbour sum and its conditional-permutation counts
+ * (csrc/local_autocorr.hip) ---------------------------------------------------------------------------------------------
+ * z (n, C) fp64 row-major, the caller's CENTRED values, and idx (n, m) int32, the neighbour list, as for ribca_autocorr_observed: entries outside
+ * [0, n) are skipped, by an unsigned compare before they index anything.  Every operation rounded on its own (no fma), no floating-point atomic.
+ *     lag[i][c] = (((+0.0 + z[j_0][c]) + z[j_1][c]) + ...)   over the valid entries j_q = idx[i][q], q ascending        (ribca_local_lag)
+ * Conditional permutation p = p0 + b, b = 0 .. P - 1: cell i keeps its own row and the other n - 1 rows are permuted around it by sigma_p, the
+ * bijection stated under ribca_nhood_perm_counts with the same key K = s(s(s(seed) ^ image) ^ p), followed by the swap that fixes i.  For a valid
+ * entry j of the list of i the source row is, by the first rule that matches,
+ *     i if j == i;   sigma_p(i) if sigma_p(j) == i;   sigma_p(j) otherwise
+ * (tau o sigma_p with tau the transposition (i, sigma_p(i)): a bijection with the fixed point i, so distinct entries j != i draw distinct other
+ * cells), and s_p[i][c] is the same ordered sum over z[source][c].  Then
+ *     ge[i][c] = the number of p in [p0, p0 + P) with s_p[i][c] >= lag[i][c],     le[i][c] = the same with <=
+ * ge, le (n, C) uint32 are OVERWRITTEN; lag (n, C) fp64 is an INPUT of ribca_local_perm_counts (what ribca_local_lag wrote).  The counts are a
+ * pure function of (z, idx, lag, seed, image, p0, P): counts over [p0, p0 + P) equal counts over [p0, p0 + Q) plus counts over [p0 + Q, p0 + P),
+ * entry by entry, and nothing depends on the internal batch, the launch geometry, the workspace contents, the device or the stream.
+ * 1 <= n <= 2^30, 1 <= C <= 64, 1 <= m <= 31, image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31.  ws: ribca_local_perm_counts_ws_bytes(n, C, P) bytes,
+ * two pieces, each rounded up to 256 bytes: the permuted rows of a batch of B = min(P, 32, max(1, 64 MiB / (8 n L))) permutations, 8 B n L bytes
+ * (L as for ribca_autocorr_perm: the power of two >= C up to 16, the multiple of 16 >= C above), and the inverse of sigma for each of them, 4 B n
+ * bytes; 0 for arguments the entry point refuses.  Neither entry point synchronises. */
+int ribca_local_lag(const double* z, const int32_t* idx, int32_t n, int32_t C, int32_t m, double* lag, void* stream);
+int64_t ribca_local_perm_counts_ws_bytes(int32_t n, int32_t C, int32_t P);
+int ribca_local_perm_counts(const double* z, const int32_t* idx, const double* lag, int32_t n, int32_t C, int32_t m, uint64_t seed, int32_t image,
+                            int64_t p0, int32_t P, uint32_t* ge, uint32_t* le, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- co-occurrence by distance: cell-type pair counts per radius band (csrc/cooccurrence.hip) ---------------------------
  * x, y (n) fp64, cell_type (n) int32 on the device; r2_host: a HOST array of the B squared radii, finite, non-negative and strictly increasing,
  * 1 <= B <= 32 (passed to the kernel by value, as ribca_mae_impute takes present_host).  For every ORDERED pair i != j whose labels both lie in

@@ -7,7 +7,8 @@ composition pies are reduced and rasterised on the GPU and written with a CSV be
 "Additional type c" labels (GPU UMAP embedding + GPU HDBSCAN, as the reference's min_cells).  ``--enrichment-perms N`` (N > 0) adds the
 permutation z-scores of the neighbourhood matrix (Annotator.neighborhood_enrichment); ``--cooccurrence-bands N`` (N > 0) the cell-type pair counts
 and lifts in N distance bands of one cell size each (Annotator.cooccurrence_by_distance); ``--autocorr-perms N`` (N > 0) Moran's I and Geary's C
-of every marker with an N-permutation null (Annotator.spatial_autocorrelation).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+of every marker with an N-permutation null (Annotator.spatial_autocorrelation); ``--local-autocorr-perms N`` (N > 0) local Moran's I, Getis-Ord
+Gi* and a hot-spot map per marker and image from N conditional permutations (Annotator.local_autocorrelation).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -40,6 +41,8 @@ def parse_args(argv=None):
                     help='label permutations of the neighbourhood-enrichment z-scores written beside the neighbourhood matrix (0 = off)')
     ap.add_argument('--autocorr-perms', type=int, default=0,
                     help="permutations of the null of Moran's I and Geary's C of every marker, Annotator.spatial_autocorrelation (0 = off)")
+    ap.add_argument('--local-autocorr-perms', type=int, default=0,
+                    help="conditional permutations of the per-cell local Moran's I / Getis-Ord Gi* and hot-spot maps, Annotator.local_autocorrelation (0 = off)")
     ap.add_argument('--cooccurrence-bands', type=int, default=0,
                     help='distance bands (one cell size wide each, at most 32) of the co-occurrence-by-distance table and figures (0 = off)')
     grp = ap.add_mutually_exclusive_group(required=True)
@@ -63,7 +66,7 @@ def _setup():
             dist.init_process_group(os.environ.get("RIBCA_DIST_BACKEND", "nccl"))
 
 
-def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0):
+def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -87,6 +90,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
             annotator.neighborhood_enrichment(n_perms=enrichment_perms, integrate=True)
         if autocorr_perms > 0:                      # nor of this one: Moran's I and Geary's C of every marker over the same k-NN graph
             annotator.spatial_autocorrelation(n_perms=autocorr_perms, integrate=True)
+        if local_autocorr_perms > 0:                # and WHERE each marker is structured: per-cell statistics and hot-spot maps, per image
+            annotator.local_autocorrelation(n_perms=local_autocorr_perms)
     if cooccurrence_bands > 0:                      # nor is this one: which cell types meet at which distance (any number of cells)
         from multiplexed_image_annotator_amd import cooccurrence
         annotator.cooccurrence_by_distance(radii=cooccurrence.default_radii(annotator.cell_size, cooccurrence_bands), integrate=True)
@@ -97,7 +102,7 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0):
+        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _setup()
@@ -112,7 +117,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -123,13 +128,14 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0):
+              confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
+              local_autocorr_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms)
 
 
 def main(argv=None):
@@ -138,7 +144,8 @@ def main(argv=None):
                   strict=args.strict, infer=args.infer, min_cells=args.min_cells, n_regions=args.n_regions, normalize=args.normalize,
                   blur=args.blur, amax=args.amax, confidence=args.confidence, cell_size=args.cell_size,
                   cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms,
-                  cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms)
+                  cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
+                  local_autocorr_perms=args.local_autocorr_perms)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

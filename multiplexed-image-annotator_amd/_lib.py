@@ -42,6 +42,10 @@ SIGNATURES = {
     "ribca_autocorr_perm_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_autocorr_perm": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                       c_void_p]),
+    "ribca_local_lag": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ribca_local_perm_counts_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ribca_local_perm_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_int32, c_int64, c_int32, c_void_p,
+                                          c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_radial_pair_counts_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_radial_pair_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_double), c_int32, c_void_p, c_void_p, c_int64,
                                            c_void_p]),

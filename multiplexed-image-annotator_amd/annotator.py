@@ -931,6 +931,108 @@ class Annotator(object):
                                 float(finite.max()) if finite.size else float("nan"), knn_ms, perm_ms, draw_ms))
         return None
 
+    # ---- local indicators of spatial association: WHERE a marker is structured (PySAL's esda.Moran_Local / G_Local) ------------------------------
+    def local_autocorrelation(self, n_neighbors=25, n_perms=999, alpha=0.05, markers=None):
+        """Local Moran's I and Getis-Ord Gi* of every cell for every selected image channel over the k-NN graph of spatial_autocorrelation
+        (``n_neighbors`` counts the cell itself), with a conditional-permutation pseudo-p-value per cell: the cell keeps its row, the other rows
+        of ``preprocessor.intensity_full`` move around it n_perms times (the keyed bijection of neighborhood_enrichment per (seed, image number,
+        permutation); seed = RIBCA_LOCAL_SEED, default 0), and the neighbour sums are recounted on the GPU (ops.local_lag,
+        ops.local_perm_counts, csrc/local_autocorr.hip; reproducible bits).  Needs ``preprocess()`` only.  Centring and the list are per image
+        and exactly those of spatial_autocorrelation, so the mean of ``local_i`` over an image is that image's Moran's I.  p =
+        min(1, 2 (min(n_ge, n_le) + 1) / (n_perms + 1)), two-sided; a cell with p <= alpha (decided in integers, local_autocorr.statistics) is
+        classed HH / LH / LL / HL by the signs of its centred value and its neighbour sum.  NO MULTIPLE-TESTING CORRECTION IS APPLIED: about
+        alpha of the cells of an unstructured channel are flagged.  ``markers``: names out of the marker list; None = all.  Per image it writes
+        ``{batch_id}_local_autocorr_{image number}.csv`` (local_autocorr.table_csv: one line per cell in ``cell_ids`` order),
+        ``..._{image number}_summary.csv`` (the cells per class and marker) and one ``..._{image number}_{marker}.png`` per selected marker:
+        the mask painted by class through ops.colorize with colors.LISA_COLORS, background 0.  There is no integrated form and no collective:
+        cell-sharded multi-rank runs, rank 0 computes and writes; tile-per-rank, every rank writes its own images' files.  Records
+        ``local_autocorr_stats``, one record per image written by this rank (``knn_ms``: centring, the list and the observed sums;
+        ``perm_ms``: the permutations; ``draw_ms``: statistics, CSVs, painting and PNGs)."""
+        import time
+        from PIL import Image
+        from . import cooccurrence, local_autocorr
+        full = self.preprocessor.intensity_full
+        n_local = self._n_images
+        if (len(full) == 0 or n_local == 0) and not (self.tile_mode and self.preprocessor._n_images > 0):
+            raise ValueError("No intensities: call preprocess() first")
+        p = int(n_perms)
+        if p < 1:
+            raise ValueError(f"n_perms must be at least 1, got {n_perms}")
+        k = int(n_neighbors)
+        num_den = local_autocorr.alpha_fraction(alpha)
+        tables = [None if full[i] is None else np.ascontiguousarray(full[i], dtype=np.float64) for i in range(n_local)]      # None: an image without cells
+        width = next((t.shape[1] for t in tables if t is not None), len(self.channel_parser.markers))
+        if width > ops.AUTOCORR_MAX_CHANNELS:
+            raise ValueError(f"local_autocorrelation handles at most {ops.AUTOCORR_MAX_CHANNELS} channels, got {width}")
+        names = [str(m) for m in self.channel_parser.markers]
+        names = (names + [f"channel {j}" for j in range(len(names), width)])[:width]
+        if markers is None:
+            chosen = list(range(width))
+        else:
+            chosen = []
+            for name in markers:
+                if str(name) not in names:
+                    raise ValueError(f"marker {name!r} is not one of the markers {names}")
+                chosen.append(names.index(str(name)))
+            if not chosen:
+                raise ValueError("markers selects no channel")
+        for i, t in enumerate(tables):
+            if t is None or len(t) < k:
+                raise ValueError(f"image {self._image_number(i)} has {0 if t is None else len(t)} cells, fewer than n_neighbors = {k}")
+            if t.ndim != 2 or t.shape[1] != width or len(t) != len(self.preprocessor.cell_tables[i]):
+                raise ValueError(f"image {self._image_number(i)}: an intensity table of shape {t.shape} for {len(self.preprocessor.cell_tables[i])} "
+                                 f"cells of {width} channels")
+        self.local_autocorr_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        seed = local_autocorr.default_seed()
+        selected = [names[c] for c in chosen]
+        dev = _lib.require_gpu()
+        for i in range(n_local):
+            tab = self.preprocessor.cell_tables[i]
+            x = tab[:, 5].astype(np.float64) / tab[:, 6].astype(np.float64)
+            y = tab[:, 4].astype(np.float64) / tab[:, 6].astype(np.float64)
+            n = len(tables[i])
+            group = torch.zeros(n, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mean = ops.group_sums(torch.from_numpy(tables[i]).to(dev), group, 1)[0].cpu().numpy()[0] / float(n)
+            z = tables[i] - mean
+            m2 = ops.group_sums(torch.from_numpy(z * z).to(dev), group, 1)[0].cpu().numpy()[0][chosen]
+            z = np.ascontiguousarray(z[:, chosen])      # every channel is computed on its own: only the selected ones go to the device
+            zd = torch.from_numpy(z).to(dev)
+            idx = ops.knn_neighbours(x, y, k)
+            lag = ops.local_lag(zd, idx)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            ge, le = ops.local_perm_counts(zd, idx, lag, seed, self._image_number(i), 0, p)
+            ge, le = ge.cpu().numpy(), le.cpu().numpy()
+            t2 = time.perf_counter()
+            stats = local_autocorr.statistics(z, lag.cpu().numpy(), ge, le, m2, k - 1, p, alpha)
+            ids = self.preprocessor.cell_ids[i]
+            stem = f"{self.batch_id}_local_autocorr_{self._image_number(i)}"
+            files = [stem + ".csv", stem + "_summary.csv"]
+            with open(os.path.join(self.result_dir, files[0]), "w") as f:
+                f.write(local_autocorr.table_csv(ids, selected, stats))
+            with open(os.path.join(self.result_dir, files[1]), "w") as f:
+                f.write(local_autocorr.summary_csv(selected, stats["class"]))
+            for c, name in enumerate(selected):
+                cls = np.ascontiguousarray(stats["class"][:, c])
+                rgb = colors.LISA_COLORS[cls]
+                painted = ops.colorize(self.preprocessor.masks_dev[i], ids, rgb, rgb, cls)[0].cpu().numpy()
+                files.append(f"{stem}_{cooccurrence.slug(name)}.png")
+                Image.fromarray(painted).save(os.path.join(self.result_dir, files[-1]))
+            counts = local_autocorr.class_counts(stats["class"])
+            rec = {"file": files[0], "files": files, "n": n, "C": len(chosen), "P": p, "seed": seed, "neighbors": k, "alpha": num_den,
+                   "markers": selected, "significant": int(counts[:, 1:].sum()), "knn_ms": (t1 - t0) * 1e3, "perm_ms": (t2 - t1) * 1e3,
+                   "draw_ms": (time.perf_counter() - t2) * 1e3}
+            self.local_autocorr_stats.append(rec)
+            self.logger.log("Local autocorrelation {}: {} cells, {} markers, {} permutations (seed {}), {} significant (cell, marker) pairs at alpha "
+                            "{}/{}; centring, kNN and lags {:.1f}, permutations {:.1f}, statistics and drawing {:.1f} ms.".format(
+                                files[0], n, len(chosen), p, seed, rec["significant"], num_den[0], num_den[1], rec["knn_ms"], rec["perm_ms"],
+                                rec["draw_ms"]))
+        return None
+
     # ---- tissue regions (model.py:802-804 -> spatial_methods.py:133-198) -------------------------------------------------
     def tissue_region_analysis(self, n, method="kmeans"):
         """Per-cell region labels from the cell-type make-up of each cell's 10 ... 200 nearest neighbours.  The 201-NN search and the

@@ -13,6 +13,8 @@ _FIXED = np.array([[255, 0, 0], [0, 0, 255], [0, 128, 0], [255, 255, 0], [255, 0
                    [0, 128, 128], [128, 0, 0], [0, 0, 128], [128, 128, 0], [255, 192, 203], [165, 42, 42], [0, 255, 0], [135, 206, 235],
                    [75, 0, 130], [255, 215, 0], [192, 192, 192]], dtype=np.uint8)
 SILVER = (192, 192, 192)
+#: the hot-spot maps of Annotator.local_autocorrelation, by class index (local_autocorr.CLASSES): not significant, HH, LH, LL, HL
+LISA_COLORS = np.array([[211, 211, 211], [215, 25, 28], [171, 217, 233], [44, 123, 182], [253, 174, 97]], dtype=np.uint8)
 _GOLDEN = 0.618033988749895
 _LEVELS = (0.7, 0.8, 0.9, 1.0)
 _VIRIDIS = None

@@ -386,6 +386,40 @@ def autocorr_perm(z: torch.Tensor, idx: torch.Tensor, seed: int, image: int, p0:
     return out
 
 
+def local_perm_counts_ws_bytes(n: int, c: int, n_perms: int) -> int:
+    return int(lib().ribca_local_perm_counts_ws_bytes(int(n), int(c), int(n_perms)))
+
+
+def local_lag(z: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """(n, C) fp64 device tensor: per cell and channel the sum of the neighbours' values of the (n, C) fp64 device table ``z`` of CENTRED values
+    over the (n, m) int32 device neighbour list ``idx``, added in list order (csrc/local_autocorr.hip).  Values that are not finite raise
+    before any launch."""
+    z, idx = _autocorr_args("local_lag", z, idx, None)
+    n, c = z.shape
+    lag = torch.empty((n, c), dtype=torch.float64, device=z.device)
+    check(lib().ribca_local_lag(ptr(z), ptr(idx), n, c, idx.shape[1], ptr(lag), stream_ptr()), "ribca_local_lag")
+    return lag
+
+
+def local_perm_counts(z: torch.Tensor, idx: torch.Tensor, lag: torch.Tensor, seed: int, image: int, p0: int, n_perms: int,
+                      ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ge, le), two (n, C) int64 device tensors: how many of the conditional permutations p0 .. p0 + n_perms - 1 of (seed, image) -- cell i
+    keeps its row, the others move around it with the sigma of ``nhood_perm_counts`` -- give cell i a neighbour sum at or above / at or below
+    ``lag`` (the output of ``local_lag``).  Counts of adjoining ranges of permutations add up entry by entry."""
+    z, idx = _autocorr_args("local_perm_counts", z, idx, ws)
+    n, c = z.shape
+    if lag.dtype != torch.float64 or tuple(lag.shape) != (n, c) or lag.device != z.device:
+        raise ValueError("local_perm_counts takes the (n, C) float64 lag of local_lag on the device of z")
+    lag = lag.contiguous()
+    ge = torch.empty((n, c), dtype=torch.int32, device=z.device)      # the library's uint32, widened below: a count may reach 2^31
+    le = torch.empty((n, c), dtype=torch.int32, device=z.device)
+    if ws is None:
+        ws = _scratch(local_perm_counts_ws_bytes(n, c, n_perms), z.device)
+    check(lib().ribca_local_perm_counts(ptr(z), ptr(idx), ptr(lag), n, c, idx.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0),
+                                        int(n_perms), ptr(ge), ptr(le), ptr(ws), ws.numel(), stream_ptr()), "ribca_local_perm_counts")
+    return ge.to(torch.int64) & 0xFFFFFFFF, le.to(torch.int64) & 0xFFFFFFFF
+
+
 TISSUE_NEIGHBOURHOODS = (10, 20, 30, 50, 75, 100, 150, 200)       # spatial_methods.py:155
 
 

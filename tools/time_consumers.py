@@ -9,7 +9,9 @@ and, for scale, the numpy restatement of tests/enrichment_numpy.py on 10 of the 
 image (every pair in range: the weight of the LDS atomics), and as the host yardstick scipy's cKDTree.count_neighbors over the same radii and type
 pairs and the numpy oracle of tests/cooccurrence_numpy.py on the first 10 000 cells, scaled by n^2; and the spatial autocorrelation
 (csrc/autocorr.hip): the observed numerators of Moran's I and Geary's C of the 15-column table over the 25-nearest-neighbour list, 1000 row
-permutations, and the numpy restatement of tests/autocorr_numpy.py on 10 of the same permutations."""
+permutations, and the numpy restatement of tests/autocorr_numpy.py on 10 of the same permutations; and the local indicators
+(csrc/local_autocorr.hip): the per-cell neighbour sums and the counts of 999 conditional permutations of the same table, and the numpy restatement
+of tests/local_autocorr_numpy.py on one of them."""
 import os
 import sys
 import time
@@ -188,3 +190,31 @@ want = AN.perm(z_host, idx_host, 0, 0, 0, 10)
 oracle_ms = 1e3 * (time.perf_counter() - t0)
 same = out[:10].cpu().numpy().tobytes() == want.tobytes()
 print(f"numpy restatement, 10 row permutations (host): {oracle_ms:.0f} ms -> {oracle_ms * PERMS / 10 / 1e3:.1f} s for {PERMS}; bit-equal to the GPU numerators: {same}")
+
+
+# ---- the local indicators (csrc/local_autocorr.hip): the same table and list, 999 conditional permutations ----------------------------------------
+import local_autocorr_numpy as LN  # noqa: E402
+
+LOCAL_PERMS = 999
+ws = torch.empty(ops.local_perm_counts_ws_bytes(n, 15, LOCAL_PERMS), dtype=torch.uint8, device=dev)
+lag = ops.local_lag(z_dev, idx)
+for name, fn in (("local lags (C = 15, m = 24, table on the device)", lambda: ops.local_lag(z_dev, idx)),
+                 (f"local counts, {LOCAL_PERMS} conditional permutations (C = 15, m = 24, table on the device, {ws.numel() / 2 ** 20:.1f} MiB workspace)",
+                  lambda: ops.local_perm_counts(z_dev, idx, lag, 0, 0, 0, LOCAL_PERMS, ws=ws))):
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"{name}: median {sorted(times)[2]:.1f} ms, min {min(times):.1f}, max {max(times):.1f} of 5 for {n} cells")
+lag_host = lag.cpu().numpy()
+t0 = time.perf_counter()
+want = LN.perm_counts(z_host, idx_host, lag_host, 0, 0, 0, 1)
+oracle_ms = 1e3 * (time.perf_counter() - t0)
+got = [t.cpu().numpy() for t in ops.local_perm_counts(z_dev, idx, lag, 0, 0, 0, 1)]
+same = lag_host.tobytes() == LN.lag(z_host, idx_host).tobytes() and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+print(f"numpy restatement, 1 conditional permutation (host): {oracle_ms:.0f} ms -> {oracle_ms * LOCAL_PERMS / 1e3:.1f} s for {LOCAL_PERMS}; equal to the GPU "
+      f"lags and counts: {same}")
