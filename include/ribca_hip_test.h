@@ -102,6 +102,15 @@ int ribca_test_gemm_duo_gelu(const uint16_t* A, int32_t lda, const uint16_t* W, 
  * ribca_test_qkv_attention_fold, q / k / v never leave the CU.  Non-zero return: geometry not supported. */
 int ribca_test_cell_attention(const uint16_t* z_ps, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D,
                               const float* bias2, const float* csum, const float* rowstat, uint16_t* out, int32_t ldo, void* stream);
+/* proj + residual, norm2, fc1, GELU, fc2 + residual of a 144-wide block in ONE kernel (cell_mlp.hip), token rows stationary in registers.
+ * projw / fc1w (gamma o W, from fold_weight) / fc2w: packed-split weights [>= N][2 * Kp]; img_scratch (ribca_test_cell_mlp_image_bytes(D)
+ * bytes): their stage image, written here when pack != 0 and only read otherwise.  z_ps rows 0 .. M - 1 are updated in place (columns
+ * D .. Dp never written), rowstat [M] float2 holds (rstd, mean) of the stored rows on entry and of the new rows on return; xa is read only.
+ * Non-zero return: D is not 144. */
+int64_t ribca_test_cell_mlp_image_bytes(int32_t D);
+int ribca_test_cell_mlp(const uint16_t* xa, int32_t ldx, const uint16_t* projw, const uint16_t* fc1w, const uint16_t* fc2w, const float* projb,
+                        const float* fc1c, const float* fc1b2, const float* fc2b, uint16_t* img_scratch, int32_t pack, uint16_t* z_ps,
+                        int32_t ldz, float* rowstat, int32_t M, int32_t D, void* stream);
 int32_t ribca_gemm_padded_n(int32_t N);
 
 #pragma GCC visibility pop

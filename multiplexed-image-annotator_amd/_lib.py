@@ -156,6 +156,9 @@ TEST_SIGNATURES = {
                                            c_void_p, c_void_p, c_int32, c_void_p]),
     "ribca_test_cell_attention": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                             c_void_p]),
+    "ribca_test_cell_mlp_image_bytes": (c_int64, [c_int32]),
+    "ribca_test_cell_mlp": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "ribca_gemm_padded_n": (c_int32, [c_int32]),
 }
 

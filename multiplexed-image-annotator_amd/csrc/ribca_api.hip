@@ -117,14 +117,17 @@ struct BlockW {
   // attn.qkv / mlp.fc1 (gamma o W) in the MX weight image, K padded to a multiple of 128, where the residual rows are kept in MX3 as well
   // (BlockPath::mx_z): proj and fc2 then write the new rows twice -- packed-split for the residual tile of the next proj / fc2, MX3 for these
   const uint16_t *qkvmxh = nullptr, *fc1mxh = nullptr; const unsigned char *qkvmxx = nullptr, *fc1mxx = nullptr;
+  // proj, gamma o fc1 and fc2 as the stage image of the one-kernel second half (cell_mlp.hip; BlockPath::cell_mlp)
+  const uint16_t* mlpimg = nullptr;
 };
 
 // The process switches (A/B), read from the environment once per process.  RIBCA_MX=0: the fp16x3 kernels everywhere.  RIBCA_MXZ=0: qkv / fc1
-// stay on the fp16x3 kernels.  RIBCA_CELL_ATTN=0: the unfused qkv GEMM + attention pair in place of the per-cell kernel.
+// stay on the fp16x3 kernels.  RIBCA_CELL_ATTN=0: the unfused qkv GEMM + attention pair in place of the per-cell kernel.  RIBCA_CELL_MLP=0: proj,
+// fc1 and fc2 of the 144-wide classifier as three GEMMs with their finalisers in place of the one-kernel second half.
 bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
-struct Switches { bool mx, mxz, cell_attn; };
+struct Switches { bool mx, mxz, cell_attn, cell_mlp; };
 const Switches& switches() {
-  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN")};
+  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN"), env_on("RIBCA_CELL_MLP")};
   return sw;
 }
 // The choice depends on the model's width alone, never on the chunk: a cell's bits must not depend on the size of the chunk it was computed in.
@@ -140,16 +143,19 @@ bool mx_z_on(int D) { return switches().mxz && mx_on(D) && D % 192 == 0; }
 //   mx_z       the residual rows are kept in MX3 as well: qkv (where it is a GEMM of its own) and fc1 run on the MX kernel.  Implies mx_fc2
 //   cell_attn  norm1 -> qkv -> attention of a whole block in ONE per-cell kernel (cell_attention.hip; D = 144, 288, 384):
 //              13.9 -> 14.4 k cells/s in a same-box A/B (profiles/r3/ab_cell_attention.txt)
+//   cell_mlp   behind the per-cell kernel, proj -> norm2 -> fc1 -> GELU -> fc2 of a whole block in ONE kernel with the token rows stationary in
+//              registers (cell_mlp.hip; D = 144): no h buffer, no statistics partials, no finaliser on this path
 struct BlockPath {
-  bool fold, mx_fc2, mx_z, cell_attn;
-  // ribca_vit_forward_precise: no MX product.  The fused per-cell kernel is fp16x3 and stays.  Layouts always take the handle's own path, so
+  bool fold, mx_fc2, mx_z, cell_attn, cell_mlp;
+  // ribca_vit_forward_precise: no MX product.  The fused per-cell kernels are fp16x3 and stay.  Layouts always take the handle's own path, so
   // that both entry points share one arena and one workspace size.
-  BlockPath precise() const { return {fold, false, false, cell_attn}; }
+  BlockPath precise() const { return {fold, false, false, cell_attn, cell_mlp}; }
   // a whole block's qkv product reads the MX3 copy of the residual rows (so whatever wrote those rows must have left one)
   bool qkv_mx3() const { return mx_z && !cell_attn; }
 };
 BlockPath block_path(const AttnGeom& a, bool fold) {
-  return {fold, fold && mx_on(a.D), fold && mx_z_on(a.D), fold && switches().cell_attn && cell_attention_supported(a.D, a.H, a.T)};
+  const bool cell_attn = fold && switches().cell_attn && cell_attention_supported(a.D, a.H, a.T);
+  return {fold, fold && mx_on(a.D), fold && mx_z_on(a.D), cell_attn, cell_attn && switches().cell_mlp && cell_mlp_supported(a.D)};
 }
 
 struct ribca_vit {
@@ -209,6 +215,7 @@ void layout_block(Carver& c, BlockW& L, int D, const BlockPath& p) {
     L.qkvmxh = c.take<uint16_t>(mx_wh_bytes(3 * D, Kz) / 2); L.qkvmxx = c.take<unsigned char>(mx_wx_bytes(3 * D, Kz));
     L.fc1mxh = c.take<uint16_t>(mx_wh_bytes(4 * D, Kz) / 2); L.fc1mxx = c.take<unsigned char>(mx_wx_bytes(4 * D, Kz));
   }
+  if (p.cell_mlp) L.mlpimg = c.take<uint16_t>(cell_mlp_image_bytes(D) / 2);
 }
 
 // lays the arena out; with base == nullptr only measures
@@ -288,6 +295,7 @@ struct BlobReader {
       launch_mx_pack_w(L.qkvw, 2 * Dp, 3 * D, Dp, Kz, const_cast<uint16_t*>(L.qkvmxh), const_cast<unsigned char*>(L.qkvmxx), s);
       launch_mx_pack_w(L.fc1w, 2 * Dp, 4 * D, Dp, Kz, const_cast<uint16_t*>(L.fc1mxh), const_cast<unsigned char*>(L.fc1mxx), s);
     }
+    if (path.cell_mlp) launch_cell_mlp_pack(L.projw, L.fc1w, L.fc2w, D, const_cast<uint16_t*>(L.mlpimg), s);
   }
 };
 int64_t block_params(int64_t d) { return 2 * d + 3 * d * d + 3 * d + d * d + d + 2 * d + 4 * d * d + 4 * d + 4 * d * d + d; }
@@ -310,7 +318,8 @@ BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, const BlockPath& p
   if (p.fold) {
     w.z = nullptr;
     w.zps = c.take<uint16_t>(Mc * 2 * Dp);
-    w.part = c.take<float2>(Mc * gemm_resid_part_rows(a.D));
+    // (cell_mlp: whole blocks leave final statistics and keep h in registers; partials and h serve the CLS-only last block alone)
+    w.part = c.take<float2>((p.cell_mlp ? (size_t)cells : Mc) * gemm_resid_part_rows(a.D));
     w.rs = c.take<float2>(Mc);
     if (p.mx_z) {
       const int Kz = round_up(a.D, 128);
@@ -332,7 +341,7 @@ BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, const BlockPath& p
   const size_t vt = attention_v_elems(a, cells);
   w.vt_bytes = vt * sizeof(uint16_t);
   w.vt = c.take<uint16_t>(vt);
-  w.h = c.take<uint16_t>(Mc * 2 * 4 * a.D);
+  w.h = c.take<uint16_t>((p.cell_mlp ? (size_t)cells : Mc) * 2 * 4 * a.D);
   return w;
 }
 // pads (tokens >= T, head dims >= hd, feature columns >= D) are never written by any kernel: zero them once per call
@@ -416,6 +425,12 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
       }
     }
     { ProfScope ps(P_ATTN, s); launch_attention(w.q, w.k, w.vt, w.xa, ld_x, cells, a, s); }
+  }
+  if (p.cell_mlp) {
+    // the whole second half: new rows and their FINAL (rstd, mean) in place; timed with fc2 (the profile has a fixed table of classes)
+    ProfScope ps(P_FC2, s);
+    launch_cell_mlp(w.xa, ld_x, L.mlpimg, L.projb, L.fc1c, L.fc1b2, L.fc2b, w.zps, ld_x, w.rs, Mc, D, s);
+    return;
   }
   {
     ProfScope ps(P_PROJ, s);

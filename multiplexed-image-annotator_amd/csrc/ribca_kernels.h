@@ -105,6 +105,17 @@ bool cell_attention_supported(int D, int H, int T);
 void launch_cell_qkv_attention(const uint16_t* z, int ldz, const uint16_t* W, int ldw, const float* bias2, const float* csum, const float2* rowstat,
                                uint16_t* out, int ldo, int cells, int D, float scale, hipStream_t s);
 
+// ----- second half of a 144-wide block in one kernel (cell_mlp.hip): proj + residual, norm2, fc1, GELU, fc2 + residual, token rows
+// stationary in registers.  img: the block's proj / (gamma o fc1) / fc2 weights as ONE stage image in consumption order
+// (launch_cell_mlp_pack from the packed-split weights, cell_mlp_image_bytes bytes, once at create).  xa: attention output rows (read only),
+// z: packed-split residual rows, updated in place (stored-row convention of EpiResidZK; pad columns never written), rs: (rstd, mean) of
+// the stored rows -- read for the re-centring, overwritten with the FINAL statistics of the new rows (no partials, no finaliser).
+bool cell_mlp_supported(int D);
+size_t cell_mlp_image_bytes(int D);
+void launch_cell_mlp_pack(const uint16_t* projw, const uint16_t* fc1w, const uint16_t* fc2w, int D, uint16_t* img, hipStream_t s);
+void launch_cell_mlp(const uint16_t* xa, int ldx, const uint16_t* img, const float* projb, const float* fc1c, const float* fc1b2, const float* fc2b,
+                     uint16_t* z, int ldz, float2* rs, int M, int D, hipStream_t s);
+
 // ----- small ViT kernels (vit_misc.hip) ----------------------------------------------------------------------
 void launch_layernorm_ps(const float* z, int ldz, const float* gamma, const float* beta, uint16_t* out, int ldo, int M, int D,
                          hipStream_t s);

@@ -299,6 +299,19 @@ int ribca_test_cell_attention(const uint16_t* z_ps, int32_t lda, const uint16_t*
   RIBCA_FINISH();
   return 0;
 }
+int64_t ribca_test_cell_mlp_image_bytes(int32_t D) { if (table() == nullptr) return 0; return (int64_t)cell_mlp_image_bytes(D); }
+int ribca_test_cell_mlp(const uint16_t* xa, int32_t ldx, const uint16_t* projw, const uint16_t* fc1w, const uint16_t* fc2w, const float* projb,
+                        const float* fc1c, const float* fc1b2, const float* fc2b, uint16_t* img_scratch, int32_t pack, uint16_t* z_ps,
+                        int32_t ldz, float* rowstat, int32_t M, int32_t D, void* stream) {
+  RIBCA_NEED_TABLE();
+  if (!cell_mlp_supported(D)) return fail("ribca_test_cell_mlp: D must be 144");
+  if (!xa || !projw || !fc1w || !fc2w || !projb || !fc1c || !fc1b2 || !fc2b || !img_scratch || !z_ps || !rowstat)
+    return fail("ribca_test_cell_mlp: NULL buffer");
+  if (pack) launch_cell_mlp_pack(projw, fc1w, fc2w, D, img_scratch, (hipStream_t)stream);
+  launch_cell_mlp(xa, ldx, img_scratch, projb, fc1c, fc1b2, fc2b, z_ps, ldz, reinterpret_cast<float2*>(rowstat), M, D, (hipStream_t)stream);
+  RIBCA_FINISH();
+  return 0;
+}
 int ribca_test_qkv_attention(const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D, int32_t Kp,
                              const float* bias, uint16_t* q, uint16_t* k, uint16_t* vt, uint16_t* out, int32_t ldo, void* stream) {
   RIBCA_NEED_TABLE();
