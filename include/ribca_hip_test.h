@@ -111,6 +111,14 @@ int64_t ribca_test_cell_mlp_image_bytes(int32_t D);
 int ribca_test_cell_mlp(const uint16_t* xa, int32_t ldx, const uint16_t* projw, const uint16_t* fc1w, const uint16_t* fc2w, const float* projb,
                         const float* fc1c, const float* fc1b2, const float* fc2b, uint16_t* img_scratch, int32_t pack, uint16_t* z_ps,
                         int32_t ldz, float* rowstat, int32_t M, int32_t D, void* stream);
+/* attention of the CLS query alone without the K / V product (cls_attention.hip): z_ps [cells * 101][ld] packed-split residual rows, rowstat
+ * [cells * 101] float2 (rstd, mean), W / bias2 the folded qkv weight [>= 3 D][ldw] and bias (from fold_weight); g / ybar: fp32 scratch of
+ * cells * 12 * D floats each, written before it is read.  Writes columns 0 .. D - 1 of row 0 of every cell of out ([cells * 101][ldo]
+ * packed-split) and nothing else.  ribca_test_cls_attention_cell_tile: cells per workgroup of the two per-head launches.
+ * Non-zero return: D is not 144 / 288 / 384 / 576. */
+int32_t ribca_test_cls_attention_cell_tile(void);
+int ribca_test_cls_attention(const uint16_t* z_ps, int32_t ld, const uint16_t* W, int32_t ldw, const float* bias2, const float* rowstat,
+                             int32_t cells, int32_t D, float* g, float* ybar, uint16_t* out, int32_t ldo, void* stream);
 int32_t ribca_gemm_padded_n(int32_t N);
 
 #pragma GCC visibility pop

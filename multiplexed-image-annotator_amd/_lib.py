@@ -159,6 +159,9 @@ TEST_SIGNATURES = {
     "ribca_test_cell_mlp_image_bytes": (c_int64, [c_int32]),
     "ribca_test_cell_mlp": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                       c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    "ribca_test_cls_attention_cell_tile": (c_int32, []),
+    "ribca_test_cls_attention": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                           c_int32, c_void_p]),
     "ribca_gemm_padded_n": (c_int32, [c_int32]),
 }
 

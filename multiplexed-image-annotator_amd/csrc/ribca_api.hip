@@ -123,11 +123,12 @@ struct BlockW {
 
 // The process switches (A/B), read from the environment once per process.  RIBCA_MX=0: the fp16x3 kernels everywhere.  RIBCA_MXZ=0: qkv / fc1
 // stay on the fp16x3 kernels.  RIBCA_CELL_ATTN=0: the unfused qkv GEMM + attention pair in place of the per-cell kernel.  RIBCA_CELL_MLP=0: proj,
-// fc1 and fc2 of the 144-wide classifier as three GEMMs with their finalisers in place of the one-kernel second half.
+// fc1 and fc2 of the 144-wide classifier as three GEMMs with their finalisers in place of the one-kernel second half.  RIBCA_CLS_ATTN=0: the
+// last block's attention as K / V GEMM + Q GEMM + attention kernel in place of the CLS-only form (cls_attention.hip).
 bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
-struct Switches { bool mx, mxz, cell_attn, cell_mlp; };
+struct Switches { bool mx, mxz, cell_attn, cell_mlp, cls_attn; };
 const Switches& switches() {
-  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN"), env_on("RIBCA_CELL_MLP")};
+  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN"), env_on("RIBCA_CELL_MLP"), env_on("RIBCA_CLS_ATTN")};
   return sw;
 }
 // The choice depends on the model's width alone, never on the chunk: a cell's bits must not depend on the size of the chunk it was computed in.
@@ -145,17 +146,22 @@ bool mx_z_on(int D) { return switches().mxz && mx_on(D) && D % 192 == 0; }
 //              13.9 -> 14.4 k cells/s in a same-box A/B (profiles/r3/ab_cell_attention.txt)
 //   cell_mlp   behind the per-cell kernel, proj -> norm2 -> fc1 -> GELU -> fc2 of a whole block in ONE kernel with the token rows stationary in
 //              registers (cell_mlp.hip; D = 144): no h buffer, no statistics partials, no finaliser on this path
+//   cls_attn   the attention of the CLS-only last block without the K / V product (cls_attention.hip; D = 144, 288, 384, 576; the imputer
+//              has no CLS-only block): three short fp32 launches in place of a [cells T x D] [D x 2 D] GEMM, a Q GEMM and the attention kernel
 struct BlockPath {
-  bool fold, mx_fc2, mx_z, cell_attn, cell_mlp;
-  // ribca_vit_forward_precise: no MX product.  The fused per-cell kernels are fp16x3 and stay.  Layouts always take the handle's own path, so
-  // that both entry points share one arena and one workspace size.
-  BlockPath precise() const { return {fold, false, false, cell_attn, cell_mlp}; }
+  bool fold, mx_fc2, mx_z, cell_attn, cell_mlp, cls_attn;
+  // ribca_vit_forward_precise: no MX product.  The fused per-cell kernels and the CLS-only attention are fp16x3 / fp32 and stay.  Layouts always
+  // take the handle's own path, so that both entry points share one arena and one workspace size.
+  BlockPath precise() const { return {fold, false, false, cell_attn, cell_mlp, cls_attn}; }
   // a whole block's qkv product reads the MX3 copy of the residual rows (so whatever wrote those rows must have left one)
   bool qkv_mx3() const { return mx_z && !cell_attn; }
+  // q / k / vt exist: some launch of this path goes through the qkv GEMM + attention kernel pair
+  bool qkv_buffers() const { return !(cell_attn && cls_attn); }
 };
 BlockPath block_path(const AttnGeom& a, bool fold) {
   const bool cell_attn = fold && switches().cell_attn && cell_attention_supported(a.D, a.H, a.T);
-  return {fold, fold && mx_on(a.D), fold && mx_z_on(a.D), cell_attn, cell_attn && switches().cell_mlp && cell_mlp_supported(a.D)};
+  return {fold, fold && mx_on(a.D), fold && mx_z_on(a.D), cell_attn, cell_attn && switches().cell_mlp && cell_mlp_supported(a.D),
+          fold && switches().cls_attn && cls_attention_supported(a.D, a.H, a.T)};
 }
 
 struct ribca_vit {
@@ -310,6 +316,8 @@ struct BlockWs {
   // the residual rows again in MX3 (BlockPath::mx_z; Kp = D rounded up to 128, M set per chunk by the caller) and the bytes of its planes
   MxAct zmx = MxAct{nullptr, nullptr, nullptr, 0, 0};
   size_t zmx_rows = 0;
+  // CLS-only attention of the last block (BlockPath::cls_attn): g and ybar, fp32 [cells][12][D] each
+  float *cls_g = nullptr, *cls_y = nullptr;
 };
 BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, const BlockPath& p) {
   BlockWs w;
@@ -334,14 +342,31 @@ BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, const BlockPath& p
   }
   w.xa_bytes = Mc * 2 * Dp * sizeof(uint16_t);
   w.xa = c.take<uint16_t>(Mc * 2 * Dp);
-  const size_t qk = (size_t)cells * a.H * a.TP * 2 * a.hdq;
-  w.qk_bytes = qk * sizeof(uint16_t);
-  w.q = c.take<uint16_t>(qk);
-  w.k = c.take<uint16_t>(qk);
-  const size_t vt = attention_v_elems(a, cells);
-  w.vt_bytes = vt * sizeof(uint16_t);
-  w.vt = c.take<uint16_t>(vt);
+  // q / k / vt: only where some launch still goes through the qkv GEMM + attention kernel pair (whole blocks without the per-cell kernel, or
+  // the last block without the CLS-only attention)
+  w.q = w.k = w.vt = nullptr;
+  w.qk_bytes = w.vt_bytes = 0;
+  if (p.qkv_buffers()) {
+    const size_t qk = (size_t)cells * a.H * a.TP * 2 * a.hdq;
+    w.qk_bytes = qk * sizeof(uint16_t);
+    w.q = c.take<uint16_t>(qk);
+    w.k = c.take<uint16_t>(qk);
+    const size_t vt = attention_v_elems(a, cells);
+    w.vt_bytes = vt * sizeof(uint16_t);
+    w.vt = c.take<uint16_t>(vt);
+  }
+  const size_t cls_elems = p.cls_attn ? cls_attention_scratch_elems(cells, a.D) : 0;
+  if (p.cls_attn && !p.qkv_buffers()) {      // in the place q / k / vt had: 96 D bytes per cell where q alone took >= 86 016
+    w.cls_g = c.take<float>(cls_elems);
+    w.cls_y = c.take<float>(cls_elems);
+  }
   w.h = c.take<uint16_t>((p.cell_mlp ? (size_t)cells : Mc) * 2 * 4 * a.D);
+  if (p.cls_attn && p.qkv_buffers()) {
+    // whole blocks still need q / k / vt, and pads of theirs must stay zero over the call: g and ybar lie in the head of h, which the last
+    // block writes (fc1) only after out is complete.  !cell_attn implies !cell_mlp: h has T * 16 D bytes per cell, g and ybar need 96 D.
+    w.cls_g = reinterpret_cast<float*>(w.h);
+    w.cls_y = w.cls_g + cls_elems;
+  }
   return w;
 }
 // pads (tokens >= T, head dims >= hd, feature columns >= D) are never written by any kernel: zero them once per call
@@ -350,13 +375,16 @@ BlockWs carve_blocks(Carver& c, int cells, const AttnGeom& a, const BlockPath& p
 //     xa, zps  feature columns D .. Dp (the K pad of proj / qkv / fc1);     q, k, vt  head dims hd .. hdq (the Q K^T product runs over them);
 //     vt of a one-tile attention (imputer)  pad keys T .. KP - 1, read under P = 0;     zmx  columns D .. Kz of the three planes
 //   don't-care: the pad token rows T .. TP - 1 of q, k and row-major vt (never fetched, or masked), every row beyond the chunk's bc * T rows
-//     of every buffer, and all of part, rs, h, enc_zf / dec_zf, tok_ps, tables (written before they are read): none of them is touched here
+//     of every buffer, and all of part, rs, h, cls_g, cls_y, enc_zf / dec_zf, tok_ps, tables (written before they are read): none of them is
+//     touched here
 int zero_pads(const BlockWs& w, const BlockPath& p, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(w.xa, 0, w.xa_bytes, s));
   if (p.fold) HIP_TRY(hipMemsetAsync(w.zps, 0, w.xa_bytes, s));     // same shape as xa: the K pad of the next GEMM must read as zeros
-  HIP_TRY(hipMemsetAsync(w.q, 0, w.qk_bytes, s));
-  HIP_TRY(hipMemsetAsync(w.k, 0, w.qk_bytes, s));
-  HIP_TRY(hipMemsetAsync(w.vt, 0, w.vt_bytes, s));
+  if (p.qkv_buffers()) {
+    HIP_TRY(hipMemsetAsync(w.q, 0, w.qk_bytes, s));
+    HIP_TRY(hipMemsetAsync(w.k, 0, w.qk_bytes, s));
+    HIP_TRY(hipMemsetAsync(w.vt, 0, w.vt_bytes, s));
+  }
   if (p.mx_z) {      // the K pad of the MX3 residual rows (D = 576: columns 576 .. 639) is never written either; scale byte 0 = 2^-127
     HIP_TRY(hipMemsetAsync(w.zmx.hi, 0, w.zmx_rows * w.zmx.Kp * 2, s));
     HIP_TRY(hipMemsetAsync(w.zmx.l8, 0, w.zmx_rows * w.zmx.Kp, s));
@@ -481,21 +509,34 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
 // on the CLS rows only: GEMM row m = cell, addressed in place with a row stride of T rows; the statistics of norm2 are indexed by GEMM
 // row too.  Same values as the full block on those rows; the other 100 rows of the last block are never read again.  Nothing reads
 // statistics after the last fc2 (the head normalises itself).
-// It has no MX form and takes no path: it is identical under ribca_vit_forward and ribca_vit_forward_precise.
-void run_last_block_cls_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, hipStream_t s) {
+// It has no MX form: p.cls_attn is all it reads of the path, and precise() keeps that, so it is identical under ribca_vit_forward and
+// ribca_vit_forward_precise.
+// cls_attn: the attention output of the CLS row needs neither K nor V of any token (cls_attention.hip has the algebra): q and g = scale W_k^T q
+// per head from the CLS row, softmax over g . y_j and ybar = sum_j p_j y_j from one cell's normalised rows, o = W_v ybar + b_v -- into row 0 of
+// the cell in xa, where the attention kernel left it.
+void run_last_block_cls_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom& a, const BlockPath& p, hipStream_t s) {
   const int D = a.D, Dp = round_up(D, 32), ld_x = 2 * Dp, ld_h = 2 * 4 * D, Mc = cells * a.T;
   const float scale = 1.0f / sqrtf((float)a.hd);
-  {
-    // only the CLS query is used (launch_attention below: one query tile, and only its row 0 is read afterwards): K and V for every
-    // token (output columns D .. 3D of the product), Q for the CLS rows alone -- a third of this block's qkv work is never done.
-    // (Rows 1 .. 15 of the first Q tile keep the previous block's values: finite, feeding output rows nothing reads.)
-    ProfScope ps(P_QKV, s);
-    GemmArgs gkv{w.zps, ld_x, L.qkvw + (size_t)D * ld_x, ld_x, Mc, 2 * D, Dp, L.qkvb2 + D};
-    launch_gemm_qkv_ln(gkv, w.rs, L.qkvc + D, w.q, w.k, w.vt, a, scale, s, D, 0, 1);
-    GemmArgs gq{w.zps, a.T * ld_x, L.qkvw, ld_x, cells, D, Dp, L.qkvb2};
-    launch_gemm_qkv_ln(gq, w.rs, L.qkvc, w.q, w.k, w.vt, a, scale, s, 0, 1, a.T);
+  if (p.cls_attn) {
+    { ProfScope ps(P_QKV, s); launch_cls_attn_qg(w.zps, ld_x, L.qkvw, ld_x, L.qkvb2, w.rs, cells, D, scale, w.cls_g, s); }
+    {
+      ProfScope ps(P_ATTN, s);
+      launch_cls_attn_ybar(w.zps, ld_x, w.rs, w.cls_g, cells, D, w.cls_y, s);
+      launch_cls_attn_out(w.cls_y, L.qkvw, ld_x, L.qkvb2, cells, D, w.xa, ld_x, s);
+    }
+  } else {
+    {
+      // only the CLS query is used (launch_attention below: one query tile, and only its row 0 is read afterwards): K and V for every
+      // token (output columns D .. 3D of the product), Q for the CLS rows alone -- a third of this block's qkv work is never done.
+      // (Rows 1 .. 15 of the first Q tile keep the previous block's values: finite, feeding output rows nothing reads.)
+      ProfScope ps(P_QKV, s);
+      GemmArgs gkv{w.zps, ld_x, L.qkvw + (size_t)D * ld_x, ld_x, Mc, 2 * D, Dp, L.qkvb2 + D};
+      launch_gemm_qkv_ln(gkv, w.rs, L.qkvc + D, w.q, w.k, w.vt, a, scale, s, D, 0, 1);
+      GemmArgs gq{w.zps, a.T * ld_x, L.qkvw, ld_x, cells, D, Dp, L.qkvb2};
+      launch_gemm_qkv_ln(gq, w.rs, L.qkvc, w.q, w.k, w.vt, a, scale, s, 0, 1, a.T);
+    }
+    { ProfScope ps(P_ATTN, s); launch_attention(w.q, w.k, w.vt, w.xa, ld_x, cells, a, s, 1); }
   }
-  { ProfScope ps(P_ATTN, s); launch_attention(w.q, w.k, w.vt, w.xa, ld_x, cells, a, s, 1); }
   {
     ProfScope ps(P_PROJ, s);
     GemmArgs g{w.xa, a.T * ld_x, L.projw, ld_x, cells, D, Dp, L.projb};
@@ -628,7 +669,7 @@ static int vit_forward_impl(const ribca_vit_t* m, const BlockPath& path, const f
       launch_mx_pack_act(w.zps, ld_z, bc * kTokens, m->Dp, zmx, s);
     }
     for (size_t li = 0; li < n_whole; ++li) run_block_fold(m->layers[li], w, bc, geom, path, path.qkv_mx3() && li + 1 < n_whole, s);
-    run_last_block_cls_fold(m->layers.back(), w, bc, geom, s);
+    run_last_block_cls_fold(m->layers.back(), w, bc, geom, path, s);
     {
       ProfScope ps(P_HEAD, s);
       launch_head_softmax_ps(w.zps, ld_z, m->norm_w, m->norm_b, m->head_w, m->head_b, probs + (size_t)c0 * m->K, D, m->K, bc, s);

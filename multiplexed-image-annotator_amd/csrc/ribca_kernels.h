@@ -116,6 +116,22 @@ void launch_cell_mlp_pack(const uint16_t* projw, const uint16_t* fc1w, const uin
 void launch_cell_mlp(const uint16_t* xa, int ldx, const uint16_t* img, const float* projb, const float* fc1c, const float* fc1b2, const float* fc2b,
                      uint16_t* z, int ldz, float2* rs, int M, int D, hipStream_t s);
 
+// ----- attention of the CLS query alone, without the K / V product (cls_attention.hip): D = 144 / 288 / 384 / 576, 101 tokens, 12 heads.
+// The attention half of a classifier's CLS-only last block.  z / rowstat: the packed-split residual rows and their (rstd, mean), W / bias2:
+// the folded qkv weight (row-major packed-split, rows q | k | v) and its bias; g, yb: fp32 scratch [cells][12][D] each
+// (cls_attention_scratch_elems floats; written before they are read); out: packed-split rows, only columns 0 .. D - 1 of token row 0 of
+// every cell are written -- what launch_attention(..., q_tiles = 1) leaves there.  Three launches, in this order:
+//   qg    q_h = W'_q y_0 + b'_q and g_h = scale W'_k[S_h]^T q_h per (head, tile of cls_attention_cell_tile() cells)
+//   ybar  p_hj = softmax_j(g_h . y_j), ybar_h = sum_j p_hj y_j, one cell per workgroup
+//   out   o[S_h] = W'_v[S_h] ybar_h + b'_v[S_h] per (head, tile of cells)
+bool cls_attention_supported(int D, int H, int T);
+int cls_attention_cell_tile();
+size_t cls_attention_scratch_elems(int cells, int D);
+void launch_cls_attn_qg(const uint16_t* z, int ldz, const uint16_t* W, int ldw, const float* bias2, const float2* rowstat, int cells, int D,
+                        float scale, float* g, hipStream_t s);
+void launch_cls_attn_ybar(const uint16_t* z, int ldz, const float2* rowstat, const float* g, int cells, int D, float* yb, hipStream_t s);
+void launch_cls_attn_out(const float* yb, const uint16_t* W, int ldw, const float* bias2, int cells, int D, uint16_t* out, int ldo, hipStream_t s);
+
 // ----- small ViT kernels (vit_misc.hip) ----------------------------------------------------------------------
 void launch_layernorm_ps(const float* z, int ldz, const float* gamma, const float* beta, uint16_t* out, int ldo, int M, int D,
                          hipStream_t s);

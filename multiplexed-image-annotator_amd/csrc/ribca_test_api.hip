@@ -312,6 +312,20 @@ int ribca_test_cell_mlp(const uint16_t* xa, int32_t ldx, const uint16_t* projw, 
   RIBCA_FINISH();
   return 0;
 }
+int32_t ribca_test_cls_attention_cell_tile(void) { if (table() == nullptr) return 0; return cls_attention_cell_tile(); }
+int ribca_test_cls_attention(const uint16_t* z_ps, int32_t ld, const uint16_t* W, int32_t ldw, const float* bias2, const float* rowstat,
+                             int32_t cells, int32_t D, float* g, float* ybar, uint16_t* out, int32_t ldo, void* stream) {
+  RIBCA_NEED_TABLE();
+  if (!cls_attention_supported(D, kHeads, kTokens)) return fail("ribca_test_cls_attention: D must be 144, 288, 384 or 576");
+  if (!z_ps || !W || !bias2 || !rowstat || !g || !ybar || !out || cells < 0) return fail("ribca_test_cls_attention: NULL buffer");
+  const float scale = 1.0f / sqrtf((float)(D / kHeads));
+  const float2* rs = reinterpret_cast<const float2*>(rowstat);
+  launch_cls_attn_qg(z_ps, ld, W, ldw, bias2, rs, cells, D, scale, g, (hipStream_t)stream);
+  launch_cls_attn_ybar(z_ps, ld, rs, g, cells, D, ybar, (hipStream_t)stream);
+  launch_cls_attn_out(ybar, W, ldw, bias2, cells, D, out, ldo, (hipStream_t)stream);
+  RIBCA_FINISH();
+  return 0;
+}
 int ribca_test_qkv_attention(const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D, int32_t Kp,
                              const float* bias, uint16_t* q, uint16_t* k, uint16_t* vt, uint16_t* out, int32_t ldo, void* stream) {
   RIBCA_NEED_TABLE();

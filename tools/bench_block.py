@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """per-kernel time of ONE classifier's forward (the library's own event profile): which of a block's launches pays under a switch
-(RIBCA_MX / RIBCA_MXZ / RIBCA_CELL_ATTN / RIBCA_CELL_MLP are read once per process, so run one process per setting).
+(RIBCA_MX / RIBCA_MXZ / RIBCA_CELL_ATTN / RIBCA_CELL_MLP / RIBCA_CLS_ATTN are read once per process, so run one process per setting).
 usage: python tools/bench_block.py [model names ...]   (default: immune_extended immune_full); cells via RIBCA_BENCH_CELLS (4096)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +11,7 @@ from multiplexed_image_annotator_amd import _lib, ops, synth
 names = sys.argv[1:] or ["immune_extended", "immune_full"]
 cells = int(os.environ.get("RIBCA_BENCH_CELLS", "4096"))
 dev = _lib.require_gpu()
-tag = " ".join(f"{k}={os.environ[k]}" for k in ("RIBCA_MX", "RIBCA_MXZ", "RIBCA_CELL_ATTN", "RIBCA_CELL_MLP") if k in os.environ) or "default"
+tag = " ".join(f"{k}={os.environ[k]}" for k in ("RIBCA_MX", "RIBCA_MXZ", "RIBCA_CELL_ATTN", "RIBCA_CELL_MLP", "RIBCA_CLS_ATTN") if k in os.environ) or "default"
 for name in names:
     d, c, k = synth.VIT_CONFIGS[name]
     model = ops.VitModel(synth.make_vit_state_dict(name, 1), device=dev)
