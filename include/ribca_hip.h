@@ -257,6 +257,39 @@ int64_t ribca_radial_pair_counts_ws_bytes(int32_t n, int32_t T, int32_t B);
 int ribca_radial_pair_counts(const double* x, const double* y, const int32_t* cell_type, int32_t n, int32_t T, const double* r2_host, int32_t B,
                              uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- nearest cell of every type: per-cell distances and the cross-type G function under a label null (csrc/nearest.hip) --
+ * x, y (n) fp64 (finite), cell_type (n) int32 on the device.  d2(i, j) in fp64 exactly as ribca_radial_pair_counts forms it: dx = x_i - x_j,
+ * dy = y_i - y_j, d2 = dx * dx + dy * dy with the two products and the sum each rounded on its own (no fma) -- a numpy loop reproduces every
+ * comparison.
+ * ribca_nearest_by_type: for every cell i and every type b in [0, T)
+ *     near2[i][b] = min of d2(i, j) over j != i with cell_type[j] == b,  +inf if there is no such cell
+ *     arg[i][b]   = the LOWEST such j that attains the minimum,           -1 if there is none
+ * near2 (n, T) fp64 and arg (n, T) int32 are OVERWRITTEN.  A label outside [0, T) is never a target, but its cell still gets a row.  Exact
+ * duplicates are distinct cells: d2 == 0 is a valid minimum.  1 <= n <= 2^21 (the work is quadratic, the cap of ribca_radial_pair_counts),
+ * 1 <= T <= 254.
+ * ribca_nearest_perm_counts: r2_host is a HOST array of the B squared radii, finite, non-negative and strictly increasing, 1 <= B <= 32, as for
+ * ribca_radial_pair_counts.  The positions stay, the labels move: for the permutation with the global index p = p0 + j, j = 0 .. P - 1, cell i
+ * carries label_p(i) = cell_type[sigma_p(i)], sigma_p the bijection stated under ribca_nhood_perm_counts with the same key
+ * K = s(s(s(seed) ^ image) ^ p).  For every cell i with a = label_p(i) in [0, T) and every b in [0, T):
+ *     m = min of d2(i, k) over k != i with label_p(k) == b;   if m <= r2[B - 1]: counts[j][band][a][b] += 1
+ * for the one band with r2[band - 1] < m <= r2[band] (band 0: m <= r2[0]); otherwise, or if no other cell carries b, nothing is counted.  A label
+ * outside [0, T) is skipped as a query and as a target.  counts (P, B, T, T) uint64 is ACCUMULATED into (zero it first; call once per image of a
+ * group); the bands are not cumulative.  Under the identity labelling the same rule applied to near2 gives the observed counts.  The result is a
+ * pure function of (x, y, cell_type, r2, seed, image, p): it does not depend on p0, P, the internal batch of permutations, the launch geometry,
+ * the workspace contents or the stream.  Integer atomics only, no floating-point atomic anywhere.  1 <= n <= 2^21, 1 <= T <= 64, image >= 0,
+ * p0 >= 0, 1 <= P, p0 + P <= 2^31.
+ * ws: ribca_nearest_by_type_ws_bytes(n, T) and ribca_nearest_perm_counts_ws_bytes(n, T, P) bytes, six pieces, each rounded up to 256 bytes: the
+ * counting sort of the cells by (type, index) -- 1024 bytes per chunk of 1024 cells, 4 (T + 2) bytes of segment offsets, three int32 arrays of n
+ * (the slot of a cell, the cell of a slot, the segment of a slot) -- and the coordinates in slot order, 16 n bytes, for the permutation counts one
+ * copy for each of a batch of min(P, 32, max(1, 64 MiB / (16 n))) permutations; both 0 for arguments the entry point refuses.  Neither entry
+ * point synchronises. */
+int64_t ribca_nearest_by_type_ws_bytes(int32_t n, int32_t T);
+int ribca_nearest_by_type(const double* x, const double* y, const int32_t* cell_type, int32_t n, int32_t T, double* near2, int32_t* arg, void* ws,
+                          int64_t ws_bytes, void* stream);
+int64_t ribca_nearest_perm_counts_ws_bytes(int32_t n, int32_t T, int32_t P);
+int ribca_nearest_perm_counts(const double* x, const double* y, const int32_t* cell_type, int32_t n, int32_t T, const double* r2_host, int32_t B,
+                              uint64_t seed, int32_t image, int64_t p0, int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

@@ -8,7 +8,9 @@ composition pies are reduced and rasterised on the GPU and written with a CSV be
 permutation z-scores of the neighbourhood matrix (Annotator.neighborhood_enrichment); ``--cooccurrence-bands N`` (N > 0) the cell-type pair counts
 and lifts in N distance bands of one cell size each (Annotator.cooccurrence_by_distance); ``--autocorr-perms N`` (N > 0) Moran's I and Geary's C
 of every marker with an N-permutation null (Annotator.spatial_autocorrelation); ``--local-autocorr-perms N`` (N > 0) local Moran's I, Getis-Ord
-Gi* and a hot-spot map per marker and image from N conditional permutations (Annotator.local_autocorrelation).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+Gi* and a hot-spot map per marker and image from N conditional permutations (Annotator.local_autocorrelation); ``--nearest-bands N`` (N > 0) the
+distance of every cell to the nearest cell of each type and the cross-type G function at N radii of one cell size each, with ``--nearest-perms P``
+(P > 0) against a P-permutation label null (Annotator.nearest_type_distances).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -45,6 +47,10 @@ def parse_args(argv=None):
                     help="conditional permutations of the per-cell local Moran's I / Getis-Ord Gi* and hot-spot maps, Annotator.local_autocorrelation (0 = off)")
     ap.add_argument('--cooccurrence-bands', type=int, default=0,
                     help='distance bands (one cell size wide each, at most 32) of the co-occurrence-by-distance table and figures (0 = off)')
+    ap.add_argument('--nearest-bands', type=int, default=0,
+                    help='radii (one cell size apart, at most 32) of the nearest-cell-of-every-type tables, maps and G figures (0 = off)')
+    ap.add_argument('--nearest-perms', type=int, default=0,
+                    help='label permutations of the null of the cross-type G function; read only with --nearest-bands > 0 (0 = no null)')
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument('--image-path', type=str)
     grp.add_argument('--batch-csv', type=str)
@@ -66,7 +72,8 @@ def _setup():
             dist.init_process_group(os.environ.get("RIBCA_DIST_BACKEND", "nccl"))
 
 
-def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0):
+def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
+              nearest_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -95,6 +102,10 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
     if cooccurrence_bands > 0:                      # nor is this one: which cell types meet at which distance (any number of cells)
         from multiplexed_image_annotator_amd import cooccurrence
         annotator.cooccurrence_by_distance(radii=cooccurrence.default_radii(annotator.cell_size, cooccurrence_bands), integrate=True)
+    if nearest_bands > 0:                           # and how far every cell is from the nearest cell of each type (any number of cells)
+        from multiplexed_image_annotator_amd import cooccurrence
+        annotator.nearest_type_distances(radii=cooccurrence.default_radii(annotator.cell_size, nearest_bands), n_perms=max(nearest_perms, 0),
+                                         integrate=True)
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
     annotator.cell_type_composition(integrate=True)
@@ -102,7 +113,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
-        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0):
+        confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
+        nearest_bands=0, nearest_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _setup()
@@ -117,7 +129,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -129,13 +141,13 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0):
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
-    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms)
+    _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms)
 
 
 def main(argv=None):
@@ -145,7 +157,7 @@ def main(argv=None):
                   blur=args.blur, amax=args.amax, confidence=args.confidence, cell_size=args.cell_size,
                   cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms,
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
-                  local_autocorr_perms=args.local_autocorr_perms)
+                  local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

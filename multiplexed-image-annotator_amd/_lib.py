@@ -49,6 +49,11 @@ SIGNATURES = {
     "ribca_radial_pair_counts_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_radial_pair_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_double), c_int32, c_void_p, c_void_p, c_int64,
                                            c_void_p]),
+    "ribca_nearest_by_type_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ribca_nearest_by_type": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_nearest_perm_counts_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ribca_nearest_perm_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_double), c_int32, c_uint64, c_int32, c_int64,
+                                            c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_knn_compositions": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "ribca_region_gram_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_region_gram": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -834,6 +834,148 @@ class Annotator(object):
                             "table and drawing {:.1f} ms.".format(files[0], cells, t, nb, float(r[-1]), rec["pairs"], len(figures), count_ms, draw_ms))
         return None
 
+    # ---- nearest cell of every type: how far is each cell from the nearest cell of type b (scimap's spatial_distance, spatstat's Gcross) ---------
+    NEAREST_NULL_BYTES = 64 << 20      # the permutation counts of one call stay under this on the device; longer nulls go in ranges of permutations
+
+    def nearest_type_distances(self, radii=None, n_perms=0, integrate=True, targets=None):
+        """Per cell and cell type the distance to the nearest OTHER cell of that type, searched on the GPU in fp64 (ops.nearest_by_type,
+        csrc/nearest.hip; reproducible bits), and from it the cross-type nearest-neighbour distribution G_ab(r): the fraction of a-cells whose
+        nearest b-cell lies within r, for r = each of ``radii`` (pixels; None = cooccurrence.default_radii(cell_size)).  No edge correction.
+        ``n_perms`` > 0 adds a label-permutation null -- the positions stay, the cell-type labels are shuffled within each image (the keyed
+        bijection of neighborhood_enrichment per (seed, image number, permutation); seed = RIBCA_NEAREST_SEED, default 0) and the nearest
+        distances are searched again (ops.nearest_perm_counts) -- and z = (observed - mean) / std of every cumulative count; no p-value and no
+        multiple-testing correction.  Per image it writes ``{batch_id}_nearest_{image number}.csv`` (nearest.cells_csv: one line per cell in
+        ``cell_ids`` order, distance and id of the nearest cell of every type) and one map ``{batch_id}_nearest_{slug}_{image number}.png`` per
+        target type: the mask painted through ops.colorize with viridis at int(min(d / r_max, 1) * 255), r_max the last radius, background 0;
+        an image without a cell of that type is silver.  ``targets``: cell-type names (or indices into ``cell_types``); None = every type with
+        a cell in the image.  Per group (the batch with ``integrate``, the images added up, else every image) ``{stem}.csv`` (nearest.table_csv)
+        and one ``{stem}_{slug}.png`` per anchor type present -- rows = the target types, columns = the radii, G on the fixed scale 0 .. 1 --
+        and with a null ``{stem}_{slug}_z.png`` on the scale +- its largest finite |z|; stem = ``{batch_id}_integrated_nearest_table`` or
+        ``{batch_id}_nearest_table`` with the image number at the end of each name.  Records ``nearest_stats``, one record per group written by
+        this rank.  Cell-sharded multi-rank runs: rank 0 computes and writes.  Tile-per-rank: every rank does its own images; the integrated
+        counts take one all-reduce every rank enters (exact in fp64 below 2^53; a group that could pass that is refused before any
+        collective)."""
+        import time
+        from PIL import Image
+        from . import cooccurrence, enrichment, nearest
+        self._check_annotated("No annotations")
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        r = cooccurrence.check_radii(cooccurrence.default_radii(self.cell_size) if radii is None else radii, ops.RADIAL_MAX_BANDS)
+        nb = len(r)
+        p = int(n_perms)
+        if p < 0:
+            raise ValueError(f"n_perms must not be negative, got {n_perms}")
+        if t > ops.NEAREST_MAX_TYPES:
+            raise ValueError(f"nearest_type_distances handles at most {ops.NEAREST_MAX_TYPES} cell types, got {t}")
+        if p > 0 and t > ops.NEAREST_PERM_MAX_TYPES:
+            raise ValueError(f"nearest_type_distances with a permutation null handles at most {ops.NEAREST_PERM_MAX_TYPES} cell types, got {t}")
+        wanted = None
+        if targets is not None:
+            wanted = []
+            for a in targets:
+                k = names.index(a) if isinstance(a, str) and a in names else a
+                if isinstance(k, (str, bool)) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < t:
+                    raise ValueError(f"target {a!r} is not one of the cell types {names}")
+                wanted.append(int(k))
+        n_local = len(self.annotations)
+        cap = ops.NEAREST_MAX_CELLS
+        sizes = [len(self.preprocessor.cell_ids[i]) for i in range(n_local)]
+        if any(n > cap for n in sizes):
+            raise ValueError(f"nearest_type_distances takes at most {cap} cells per image, got {max(sizes)}")
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        # no count passes the cells of its group; the same bound on every rank of a tile-per-rank run (each knows the number of images, not their sizes)
+        worst = self.preprocessor._n_images * cap if integrate and self.tile_mode else max([sum(sizes[i] for i in g) for g in groups] + [0])
+        if worst >= 2 ** 53:
+            raise ValueError(f"nearest_type_distances: a group of up to {worst} cells does not count exactly in fp64 (2^53)")
+        self.nearest_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        seed = nearest.default_seed()
+        r2 = r * r
+        r_max = float(r[-1])
+        lut = colors.viridis_table()
+        per_call = max(1, self.NEAREST_NULL_BYTES // (8 * nb * t * t))
+        for g, members in enumerate(groups):
+            observed = np.zeros((nb, t, t), dtype=np.int64)
+            null = np.zeros((p, nb, t, t), dtype=np.int64)
+            present = np.zeros(t, dtype=np.int64)
+            cells, distance_ms, perm_ms, draw_ms = 0, 0.0, 0.0, 0.0
+            image_files = []
+            for i in members:
+                tab = self.preprocessor.cell_tables[i]
+                ids = self.preprocessor.cell_ids[i]
+                n = len(tab)
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                near2, arg = np.full((0, t), np.inf), np.full((0, t), -1, dtype=np.int32)
+                if n:
+                    x = tab[:, 5].astype(np.float64) / tab[:, 6].astype(np.float64)
+                    y = tab[:, 4].astype(np.float64) / tab[:, 6].astype(np.float64)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    near2_d, arg_d = ops.nearest_by_type(x, y, types, t)
+                    near2, arg = near2_d.cpu().numpy(), arg_d.cpu().numpy()
+                    t1 = time.perf_counter()
+                    for q0 in range(0, p, per_call):      # the entry point is pure in the permutation index: the ranges are invisible
+                        q = min(per_call, p - q0)
+                        null[q0:q0 + q] += ops.nearest_perm_counts(x, y, types, t, r, seed, self._image_number(i), q0, q).cpu().numpy()
+                    distance_ms += (t1 - t0) * 1e3
+                    perm_ms += (time.perf_counter() - t1) * 1e3
+                    observed += nearest.observed_counts(near2, types, t, r2)
+                here = np.bincount(types, minlength=t)[:t]
+                present += here
+                cells += n
+                t0 = time.perf_counter()
+                number = self._image_number(i)
+                image_files.append(f"{self.batch_id}_nearest_{number}.csv")
+                with open(os.path.join(self.result_dir, image_files[-1]), "w") as f:
+                    f.write(nearest.cells_csv(ids, types, names, near2, arg))
+                for b in (wanted if wanted is not None else [k for k in range(t) if here[k] > 0]):
+                    idx = nearest.distance_colour_index(near2[:, b], r_max)
+                    rgb = lut[idx] if here[b] > 0 else np.tile(np.array(colors.SILVER, dtype=np.uint8), (n, 1))
+                    painted = ops.colorize(self.preprocessor.masks_dev[i], ids, rgb, rgb, idx)[0].cpu().numpy()
+                    image_files.append(f"{self.batch_id}_nearest_{cooccurrence.slug(names[b])}_{number}.png")
+                    Image.fromarray(painted).save(os.path.join(self.result_dir, image_files[-1]))
+                draw_ms += (time.perf_counter() - t0) * 1e3
+            if integrate and self.tile_mode:
+                buf = dist.all_reduce_sum(torch.cat([torch.from_numpy(observed.reshape(-1).astype(np.float64)),
+                                                     torch.from_numpy(null.reshape(-1).astype(np.float64)),
+                                                     torch.from_numpy(present.astype(np.float64)),
+                                                     torch.tensor([float(cells)], dtype=torch.float64)])).numpy()
+                no, nn = nb * t * t, p * nb * t * t
+                observed, null = buf[:no].astype(np.int64).reshape(nb, t, t), buf[no:no + nn].astype(np.int64).reshape(p, nb, t, t)
+                present, cells = buf[no + nn:-1].astype(np.int64), int(buf[-1])
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            stats = nearest.statistics(observed, null if p > 0 else None, present)
+            stem = f"{self.batch_id}_integrated_nearest_table" if integrate else f"{self.batch_id}_nearest_table"
+            tail = "" if integrate else f"_{self._image_number(members[0])}"
+            files = [stem + tail + ".csv"]
+            with open(os.path.join(self.result_dir, files[0]), "w") as f:
+                f.write(nearest.table_csv(names, r, observed, present, stats))
+            labels = [f"{v:g}" for v in r]
+            figures = []
+            for a in [k for k in range(t) if present[k] > 0]:
+                table = np.ascontiguousarray(stats["G"][:, a, :].T)      # rows: target types, columns: radii
+                fig = self._write_table_figure(f"{stem}_{cooccurrence.slug(names[a])}{tail}", table, 0.0, 1.0, row_names=names, col_names=labels)
+                figures.append({"file": fig["file"], "anchor": names[a], "what": "G", "limit": 1.0, "rect": fig["rect"]})
+                files.append(fig["file"])
+                if p > 0:
+                    table = np.ascontiguousarray(stats["z"][:, a, :].T)
+                    lim = enrichment.colour_limit(table)
+                    fig = self._write_table_figure(f"{stem}_{cooccurrence.slug(names[a])}_z{tail}", table, -lim, lim, row_names=names, col_names=labels)
+                    figures.append({"file": fig["file"], "anchor": names[a], "what": "z", "limit": lim, "rect": fig["rect"]})
+                    files.append(fig["file"])
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            rec = {"file": files[0], "files": files, "image_files": image_files, "figures": figures, "n": cells, "T": t, "B": nb, "P": p, "seed": seed,
+                   "radii": [float(v) for v in r], "distance_ms": distance_ms, "perm_ms": perm_ms, "draw_ms": draw_ms}
+            self.nearest_stats.append(rec)
+            self.logger.log("Nearest cell of every type {}: {} cells, {} cell types, {} radii up to {:g} px, {} permutations (seed {}), {} figures; "
+                            "distances {:.1f}, permutations {:.1f}, tables and drawing {:.1f} ms.".format(
+                                files[0], cells, t, nb, r_max, p, seed, len(figures), distance_ms, perm_ms, draw_ms))
+        return None
+
     # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
     def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
         """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as

@@ -334,6 +334,69 @@ def radial_pair_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_ty
     return out
 
 
+NEAREST_MAX_TYPES = 254           # csrc/nearest.hip: the distance table
+NEAREST_PERM_MAX_TYPES = 64       # ... and the permutation counts
+NEAREST_MAX_CELLS = 1 << 21
+
+
+def nearest_by_type_ws_bytes(n: int, n_types: int) -> int:
+    return int(lib().ribca_nearest_by_type_ws_bytes(int(n), int(n_types)))
+
+
+def nearest_perm_counts_ws_bytes(n: int, n_types: int, n_perms: int) -> int:
+    return int(lib().ribca_nearest_perm_counts_ws_bytes(int(n), int(n_types), int(n_perms)))
+
+
+def _nearest_inputs(x, y, cell_type, dev):
+    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
+    td = torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(dev)
+    if xd.dim() != 1 or yd.shape != xd.shape or td.shape != xd.shape:
+        raise ValueError(f"the nearest-cell search takes n coordinates and n labels, got {tuple(xd.shape)}, {tuple(yd.shape)}, {tuple(td.shape)}")
+    return xd, yd, td
+
+
+def nearest_by_type(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, ws: Optional[torch.Tensor] = None,
+                    device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(near2, arg): (n, n_types) fp64 and int32 device tensors, per cell and cell type the squared distance to the nearest OTHER cell of that
+    type (+inf where there is none) and the lowest index that attains it (-1 where there is none); a label outside [0, n_types) is never a
+    target, its cell still has a row.  fp64 brute force, csrc/nearest.hip; include/ribca_hip.h states every comparison."""
+    dev = device or _lib.require_gpu()
+    xd, yd, td = _nearest_inputs(x, y, cell_type, dev)
+    n = xd.numel()
+    near2 = torch.empty((n, max(int(n_types), 0)), dtype=torch.float64, device=dev)
+    arg = torch.empty((n, max(int(n_types), 0)), dtype=torch.int32, device=dev)
+    if ws is None:
+        ws = _scratch(nearest_by_type_ws_bytes(n, n_types), dev)
+    check(lib().ribca_nearest_by_type(ptr(xd), ptr(yd), ptr(td), n, int(n_types), ptr(near2), ptr(arg), ptr(ws), ws.numel(), stream_ptr()),
+          "ribca_nearest_by_type")
+    return near2, arg
+
+
+def nearest_perm_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, radii: Sequence[float], seed: int, image: int, p0: int,
+                        n_perms: int, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """(n_perms, B, n_types, n_types) int64 device tensor: under the label permutations p0 .. p0 + n_perms - 1 of (seed, image) -- the positions
+    stay, cell i carries cell_type[sigma_p(i)], the sigma of ``nhood_perm_counts`` -- the cells of type a whose nearest other cell of type b lies
+    in the band radii[k - 1] < distance <= radii[k] (band 0 from distance 0; beyond the last radius: not counted).  ``radii`` in pixels, squared
+    once in fp64 here as ``radial_pair_counts`` squares them.  Accumulates into ``out`` when given (the images of a group)."""
+    dev = device or _lib.require_gpu()
+    xd, yd, td = _nearest_inputs(x, y, cell_type, dev)
+    n = xd.numel()
+    r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    r2 = np.ascontiguousarray(r * r)
+    shape = (max(int(n_perms), 0), len(r2), max(int(n_types), 0), max(int(n_types), 0))
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"nearest_perm_counts: out must be a contiguous int64 tensor of shape {shape}")
+    if ws is None:
+        ws = _scratch(nearest_perm_counts_ws_bytes(n, n_types, n_perms), dev)
+    check(lib().ribca_nearest_perm_counts(ptr(xd), ptr(yd), ptr(td), n, int(n_types), r2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(r2),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0), int(n_perms), ptr(out), ptr(ws), ws.numel(),
+                                          stream_ptr()), "ribca_nearest_perm_counts")
+    return out
+
+
 AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
 AUTOCORR_MAX_NEIGHBOURS = 31
 

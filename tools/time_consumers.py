@@ -11,7 +11,9 @@ pairs and the numpy oracle of tests/cooccurrence_numpy.py on the first 10 000 ce
 (csrc/autocorr.hip): the observed numerators of Moran's I and Geary's C of the 15-column table over the 25-nearest-neighbour list, 1000 row
 permutations, and the numpy restatement of tests/autocorr_numpy.py on 10 of the same permutations; and the local indicators
 (csrc/local_autocorr.hip): the per-cell neighbour sums and the counts of 999 conditional permutations of the same table, and the numpy restatement
-of tests/local_autocorr_numpy.py on one of them."""
+of tests/local_autocorr_numpy.py on one of them; and the nearest cell of every type (csrc/nearest.hip): the (n, 12) distance table and 100 label
+permutations of the nearest-distance band counts in 16 bands of 30 px, inputs on the device, for a uniform label mix and for one with half the cells
+of one type, and the numpy restatement of tests/nearest_numpy.py on the first 10 000 cells, scaled by n^2 (``--nearest``: this section alone)."""
 import os
 import sys
 import time
@@ -34,6 +36,70 @@ conf = rng.random(n).astype(np.float32)
 pal = np.array(colors.get_colors(12), np.uint8)
 x = tab[:, 5] / tab[:, 6]
 y = tab[:, 4] / tab[:, 6]
+
+
+# ---- the nearest cell of every type (csrc/nearest.hip): n cells, T = 12; the distance table, and P = 100 label permutations of the band counts ----
+def time_nearest():
+    """inputs, outputs and workspaces on the device before the clock starts: the entry points themselves, median of five calls after a warm-up"""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nearest_numpy as NN
+    from multiplexed_image_annotator_amd import cooccurrence
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    perms, t = 100, 12
+    radii = cooccurrence.default_radii(30, 16)
+    r2 = np.ascontiguousarray(radii * radii)
+    edges = r2.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    xd, yd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev), torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
+    skew = np.random.default_rng(1).choice(t, n, p=[0.5, 0.2, 0.1] + [0.2 / 9] * 9)
+    near2 = torch.empty((n, t), dtype=torch.float64, device=dev)
+    arg = torch.empty((n, t), dtype=torch.int32, device=dev)
+    counts = torch.zeros((perms, 16, t, t), dtype=torch.int64, device=dev)
+    ws1 = torch.empty(ops.nearest_by_type_ws_bytes(n, t), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(ops.nearest_perm_counts_ws_bytes(n, t, perms), dtype=torch.uint8, device=dev)
+    for mix, labels in (("12 types, uniform", tidx), ("12 types, half the cells of one type", skew)):
+        td = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+
+        def table():
+            _lib.check(lib().ribca_nearest_by_type(ptr(xd), ptr(yd), ptr(td), n, t, ptr(near2), ptr(arg), ptr(ws1), ws1.numel(), stream_ptr()), "nearest")
+
+        def null():
+            counts.zero_()
+            _lib.check(lib().ribca_nearest_perm_counts(ptr(xd), ptr(yd), ptr(td), n, t, edges, 16, 0, 0, 0, perms, ptr(counts), ptr(ws2), ws2.numel(),
+                                                       stream_ptr()), "nearest")
+
+        for name, fn in ((f"nearest cell of every type, distance table ({mix})", table),
+                         (f"nearest-distance band counts, {perms} label permutations, 16 bands up to 480 px ({mix}, {ws2.numel() / 2 ** 20:.1f} MiB workspace)", null)):
+            fn()
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times.append(1e3 * (time.perf_counter() - t0))
+            print(f"{name}: median {sorted(times)[2]:.1f} ms, min {min(times):.1f}, max {max(times):.1f} of 5 for {n} cells, "
+                  f"{n * (n - 1) * (perms if fn is null else 1):.3g} distance evaluations")
+    m, few = 10000, 2
+    t0 = time.perf_counter()
+    want2, want_arg = NN.nearest_by_type(x[:m], y[:m], tidx[:m], t)
+    table_ms = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    want = NN.perm_counts(x[:m], y[:m], tidx[:m], t, r2, 0, 0, 0, few)
+    oracle_ms = 1e3 * (time.perf_counter() - t0)
+    got2, got_arg = ops.nearest_by_type(x[:m], y[:m], tidx[:m], t)
+    same = (got2.cpu().numpy().tobytes() == want2.tobytes() and np.array_equal(got_arg.cpu().numpy(), want_arg)
+            and np.array_equal(ops.nearest_perm_counts(x[:m], y[:m], tidx[:m], t, radii, 0, 0, 0, few).cpu().numpy(), want))
+    scale = (n / m) ** 2
+    print(f"numpy restatement, first {m} cells (host): table {table_ms:.0f} ms -> {table_ms * scale / 1e3:.1f} s at {n} cells; {few} permutations "
+          f"{oracle_ms:.0f} ms -> {oracle_ms * scale * perms / few / 1e3:.0f} s for {perms} at {n} cells; equal to the GPU table and counts of the same "
+          f"cells: {same}")
+
+
+if "--nearest" in sys.argv:      # this section alone
+    time_nearest()
+    sys.exit(0)
+
 for name, fn in (("colorize", lambda: ops.colorize(mask, ids, pal[tidx], colors.confidence_colors(conf), (tidx + 1).astype(np.uint8))),
                  ("knn25", lambda: ops.knn_cooccurrence(x, y, tidx, 12, 25)),
                  ("compositions (201-NN, 8 sizes)", lambda: ops.knn_compositions(x, y, tidx, 12)),
@@ -218,3 +284,7 @@ got = [t.cpu().numpy() for t in ops.local_perm_counts(z_dev, idx, lag, 0, 0, 0, 
 same = lag_host.tobytes() == LN.lag(z_host, idx_host).tobytes() and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
 print(f"numpy restatement, 1 conditional permutation (host): {oracle_ms:.0f} ms -> {oracle_ms * LOCAL_PERMS / 1e3:.1f} s for {LOCAL_PERMS}; equal to the GPU "
       f"lags and counts: {same}")
+
+
+# ---- the nearest cell of every type: defined above, beside the switch that runs it alone ------------------------------------------------------------
+time_nearest()
