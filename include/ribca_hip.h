@@ -290,6 +290,37 @@ int64_t ribca_nearest_perm_counts_ws_bytes(int32_t n, int32_t T, int32_t P);
 int ribca_nearest_perm_counts(const double* x, const double* y, const int32_t* cell_type, int32_t n, int32_t T, const double* r2_host, int32_t B,
                               uint64_t seed, int32_t image, int64_t p0, int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- cell contact graph of the segmentation mask and the label null over an edge list (csrc/contact.hip) ---------------
+ * mask (H, W) int32 row-major and label_to_cell (L) int32 on the device.  The pixel p belongs to the cell c = label_to_cell[mask[p]] when
+ * 0 <= mask[p] < L and 0 <= c < n, and to no cell otherwise (negative labels, labels >= L, labels mapped outside [0, n); the background label 0
+ * is excluded by mapping it to -1, as ops.contact_graph does).  A label in two blobs is one cell.  For the integer reach d, 1 <= d <= 8,
+ *     w(i, j) = #{ (p, q) : cell(p) = i, cell(q) = j, i != j, (p_r - q_r)^2 + (p_c - q_c)^2 <= d^2 }
+ * the ordered pixel pairs within the Euclidean disk, all in integers (4, 12, 28, 48, 80, 112, 148, 196 offsets for d = 1 .. 8; at d = 1 the shared
+ * border in pixel edges); nothing outside the image is read.  w is symmetric, and i and j are IN CONTACT iff w(i, j) > 0.
+ * ribca_contact_table: nbr (n, S) int32, pairs (n, S) uint64, degree (n) int32 and over (2) int32 are all OVERWRITTEN (the library initialises
+ * them and its workspace itself).  over[0] == 0: degree[i] = the number of cells in contact with i; nbr[i][0 .. degree[i]) holds them in ASCENDING
+ * index order with w(i, .) beside them in pairs; the rest of either row is -1 / 0; over[1] = -1.  over[0] > 0: that many cells have more than S
+ * neighbours, over[1] is the lowest such cell index, the other outputs are unspecified -- call again with a larger S.  The result is a pure
+ * function of (mask, label_to_cell, d): the same for every S that fits, every launch geometry and every run (integer sums; the rows are sorted).
+ * 1 <= H, W, H W < 2^31, 1 <= L, 1 <= n <= 2^21, S a power of two in 8 .. 1024.  ws: ribca_contact_table_ws_bytes(H, W, n, S) bytes, three
+ * pieces, each rounded up to 256 bytes: the open-addressing table the kernels insert into, 4 n S bytes of keys and 8 n S bytes of sums, and 4 n
+ * bytes of overflow flags; 0 for arguments the entry point refuses.  No loop of any kernel waits for another thread: every probe sequence ends
+ * after at most S slots.
+ * ribca_edge_perm_counts: the general graph form of the null of ribca_nhood_perm_counts.  src, dst (E) int32: directed edges.  For the permutation
+ * with the global index p = p0 + j, j = 0 .. P - 1, cell i carries label_p(i) = cell_type[sigma_p(i)], sigma_p the bijection stated under
+ * ribca_nhood_perm_counts with the same key K = s(s(s(seed) ^ image) ^ p), and counts[j][label_p(src[e])][label_p(dst[e])] += 1 for every edge e;
+ * an edge with an end outside [0, n) or a label outside [0, T) is skipped.  counts (P, T, T) uint64 is ACCUMULATED into (zero it first; call once
+ * per image of a group).  Integer atomics only; a pure function of (src, dst, cell_type, seed, image, p): a split of the permutation range is
+ * invisible.  1 <= E < 2^31, 1 <= n <= 2^30, 1 <= T <= 64, image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31.  ws: ribca_edge_perm_counts_ws_bytes(n, P)
+ * bytes, the shuffled labels of a batch of min(P, 128, max(1, 64 MiB / n)) permutations, one byte per cell; 0 for arguments the entry point
+ * refuses.  Neither entry point synchronises. */
+int64_t ribca_contact_table_ws_bytes(int32_t H, int32_t W, int32_t n, int32_t S);
+int ribca_contact_table(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, int32_t d, int32_t S,
+                        int32_t* nbr, uint64_t* pairs, int32_t* degree, int32_t* over, void* ws, int64_t ws_bytes, void* stream);
+int64_t ribca_edge_perm_counts_ws_bytes(int32_t n, int32_t P);
+int ribca_edge_perm_counts(const int32_t* src, const int32_t* dst, int64_t E, const int32_t* cell_type, int32_t n, int32_t T, uint64_t seed,
+                           int32_t image, int64_t p0, int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

@@ -976,6 +976,144 @@ class Annotator(object):
                                 files[0], cells, t, nb, r_max, p, seed, len(figures), distance_ms, perm_ms, draw_ms))
         return None
 
+    # ---- contact graph: which cells actually touch, read off the segmentation mask (histoCAT's neighbourhood analysis, steinbock's expansion graph) --
+    CONTACT_NULL_BYTES = 64 << 20      # the permutation counts of one call stay under this on the device; longer nulls go in ranges of permutations
+
+    def contact_analysis(self, distance=1, n_perms=0, integrate=True):
+        """The contact graph of every image, built on the GPU from the segmentation mask (ops.contact_graph, csrc/contact.hip): two cells are
+        neighbours when pixels of theirs lie within ``distance`` pixels of each other (an integer 1 .. 8, Euclidean; 1 = they share a border), and
+        every contact carries its number of ordered pixel pairs within that reach (at distance 1 the length of the shared border).  No edge
+        correction and no physical units.  ``n_perms`` > 0 adds the label-permutation null of neighborhood_enrichment on THIS graph -- the graph
+        stays, the cell-type labels are shuffled within each image (the same keyed bijection per (seed, image number, permutation); seed =
+        RIBCA_CONTACT_SEED, default 0; ops.edge_perm_counts) -- and z = (observed - mean) / std of every (cell type, neighbour type) count of
+        directed edges (enrichment.z_scores); no p-value and no multiple-testing correction.  Per image it writes
+        ``{batch_id}_contact_edges_{image number}.csv`` (every contact once, contact.edges_csv), ``{batch_id}_contact_cells_{image number}.csv``
+        (degree, pixel pairs and the neighbours of every type per cell, contact.cells_csv) and ``{batch_id}_contact_degree_{image number}.png``:
+        the mask painted through ops.colorize with viridis at int(min(degree / 12, 1) * 255), background 0 -- twelve is a FIXED scale, so that the
+        maps of different images compare.  Per group (the batch with ``integrate``, the images added up, else every image), with stem =
+        ``{batch_id}_integrated_contact`` or ``{batch_id}_contact`` and the image number at the end of each name: ``{stem}_table.csv``
+        (contact.table_csv), ``{stem}_pairs.png`` (the pixel-pair matrix, every row over its sum, on the scale 0 .. its maximum) and with a null
+        ``{stem}.csv`` (the z matrix, enrichment.matrix_csv) and ``{stem}.png`` (z on the symmetric scale +- its largest finite magnitude).  A
+        group without any edge writes its tables with NaN statistics and launches no null.  Records ``contact_stats``, one record per group
+        written by this rank (``max_degree`` and ``slots`` over this rank's images).  Cell-sharded multi-rank runs: rank 0 computes and writes.
+        Tile-per-rank: every rank does its own images; the integrated counts take one all-reduce every rank enters (exact in fp64 below 2^53; a
+        group that could pass that is refused before any collective)."""
+        import time
+        from PIL import Image
+        from . import contact, enrichment
+        self._check_annotated("No annotations")
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)) or not 1 <= int(distance) <= ops.CONTACT_MAX_REACH:
+            raise ValueError(f"distance must be an integer from 1 to {ops.CONTACT_MAX_REACH} pixels, got {distance!r}")
+        d = int(distance)
+        p = int(n_perms)
+        if p < 0:
+            raise ValueError(f"n_perms must not be negative, got {n_perms}")
+        if t > ops.CONTACT_MAX_TYPES:
+            raise ValueError(f"contact_analysis handles at most {ops.CONTACT_MAX_TYPES} cell types, got {t}")
+        if p > 0 and t > ops.CONTACT_PERM_MAX_TYPES:
+            raise ValueError(f"contact_analysis with a permutation null handles at most {ops.CONTACT_PERM_MAX_TYPES} cell types, got {t}")
+        n_local = len(self.annotations)
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        # no sum of pixel pairs passes pixels x offsets of its group; the same bound on every rank of a tile-per-rank run (each knows the number
+        # of images of the batch, not their sizes: a mask holds fewer than 2^31 pixels)
+        reach = contact.DISK_OFFSETS[d - 1]
+        pixels = [int(self.preprocessor.masks_dev[i].numel()) for i in range(n_local)]
+        worst = self.preprocessor._n_images * (2 ** 31) * reach if integrate and self.tile_mode else max([sum(pixels[i] for i in g) * reach for g in groups] + [0])
+        if worst >= 2 ** 53:
+            raise ValueError(f"contact_analysis: a group of up to {worst} pixel pairs does not count exactly in fp64 (2^53)")
+        self.contact_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        seed = contact.default_seed()
+        lut = colors.viridis_table()
+        per_call = max(1, self.CONTACT_NULL_BYTES // (8 * t * t))
+        dev = _lib.require_gpu()
+        for g, members in enumerate(groups):
+            edges = np.zeros((t, t), dtype=np.int64)
+            weight = np.zeros((t, t), dtype=np.int64)
+            null = np.zeros((p, t, t), dtype=np.int64)
+            cells, n_edges, max_degree, slots, graph_ms, perm_ms, draw_ms = 0, 0, 0, 0, 0.0, 0.0, 0.0
+            image_files = []
+            for i in members:
+                ids = self.preprocessor.cell_ids[i]
+                mask = self.preprocessor.masks_dev[i]
+                n = len(ids)
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                graph = ops.contact_graph(mask, ids, d)
+                t1 = time.perf_counter()
+                src, dst, pairs, degree = graph["src"], graph["dst"], graph["pairs"], graph["degree"]
+                if p > 0 and len(src) > 0:
+                    src_d, dst_d = torch.from_numpy(src).to(dev), torch.from_numpy(dst).to(dev)
+                    for q0 in range(0, p, per_call):      # the entry point is pure in the permutation index: the ranges are invisible
+                        q = min(per_call, p - q0)
+                        null[q0:q0 + q] += ops.edge_perm_counts(src_d, dst_d, types, t, seed, self._image_number(i), q0, q).cpu().numpy()
+                graph_ms += (t1 - t0) * 1e3
+                perm_ms += (time.perf_counter() - t1) * 1e3
+                here_edges, here_weight = contact.observed(src, dst, pairs, types, t)
+                edges += here_edges
+                weight += here_weight
+                cells += n
+                n_edges += len(src)
+                max_degree = max(max_degree, int(degree.max()) if n else 0)
+                slots = max(slots, int(graph["slots"]))
+                t0 = time.perf_counter()
+                number = self._image_number(i)
+                image_files += [f"{self.batch_id}_contact_edges_{number}.csv", f"{self.batch_id}_contact_cells_{number}.csv",
+                                f"{self.batch_id}_contact_degree_{number}.png"]
+                with open(os.path.join(self.result_dir, image_files[-3]), "w") as f:
+                    f.write(contact.edges_csv(ids, types, names, src, dst, pairs))
+                with open(os.path.join(self.result_dir, image_files[-2]), "w") as f:
+                    f.write(contact.cells_csv(ids, types, names, src, dst, pairs, degree))
+                idx = contact.degree_colour_index(degree)
+                rgb = lut[idx].reshape(n, 3)
+                painted = ops.colorize(mask, ids, rgb, rgb, idx)[0].cpu().numpy()
+                Image.fromarray(painted).save(os.path.join(self.result_dir, image_files[-1]))
+                draw_ms += (time.perf_counter() - t0) * 1e3
+            if integrate and self.tile_mode:
+                buf = dist.all_reduce_sum(torch.cat([torch.from_numpy(edges.reshape(-1).astype(np.float64)),
+                                                     torch.from_numpy(weight.reshape(-1).astype(np.float64)),
+                                                     torch.from_numpy(null.reshape(-1).astype(np.float64)),
+                                                     torch.tensor([float(cells), float(n_edges)], dtype=torch.float64)])).numpy()
+                tt = t * t
+                edges, weight = buf[:tt].astype(np.int64).reshape(t, t), buf[tt:2 * tt].astype(np.int64).reshape(t, t)
+                null, cells, n_edges = buf[2 * tt:-2].astype(np.int64).reshape(p, t, t), int(buf[-2]), int(buf[-1])
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            stats = None
+            if p > 0:
+                stats = enrichment.z_scores(edges, null) if n_edges > 0 else contact.nan_stats(t)
+            stem = f"{self.batch_id}_integrated_contact" if integrate else f"{self.batch_id}_contact"
+            tail = "" if integrate else f"_{self._image_number(members[0])}"
+            files = [stem + "_table" + tail + ".csv"]
+            with open(os.path.join(self.result_dir, files[0]), "w") as f:
+                f.write(contact.table_csv(names, edges, weight, stats))
+            share = contact.row_normalised(weight)
+            top = float(share.max()) if share.size else 0.0
+            fig = self._write_table_figure(stem + "_pairs" + tail, share, 0.0, top if top > 0.0 else 1.0)
+            figures = [{"file": fig["file"], "what": "pairs", "limit": top, "rect": fig["rect"]}]
+            files.append(fig["file"])
+            if p > 0:
+                files.append(stem + tail + ".csv")
+                with open(os.path.join(self.result_dir, files[-1]), "w") as f:
+                    f.write(enrichment.matrix_csv(names, stats["z"]))
+                lim = enrichment.colour_limit(stats["z"])
+                fig = self._write_table_figure(stem + tail, stats["z"], -lim, lim)
+                figures.append({"file": fig["file"], "what": "z", "limit": lim, "rect": fig["rect"]})
+                files.append(fig["file"])
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            rec = {"file": files[0], "files": files, "image_files": image_files, "figures": figures, "n": cells, "E": n_edges, "T": t, "P": p, "d": d,
+                   "seed": seed, "max_degree": max_degree, "slots": slots, "graph_ms": graph_ms, "perm_ms": perm_ms, "draw_ms": draw_ms}
+            self.contact_stats.append(rec)
+            self.logger.log("Contact graph {}: {} cells, {} directed edges within {} px, {} cell types, largest degree {} ({} slots), {} permutations "
+                            "(seed {}); graph {:.1f}, permutations {:.1f}, tables and drawing {:.1f} ms.".format(
+                                files[0], cells, n_edges, d, t, max_degree, slots, p, seed, graph_ms, perm_ms, draw_ms))
+        return None
+
     # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
     def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
         """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as

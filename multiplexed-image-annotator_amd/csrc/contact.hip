@@ -1,0 +1,346 @@
+// The cell contact graph of a segmentation mask (Annotator.contact_analysis; histoCAT's neighbourhood analysis, steinbock's expansion graph): two
+// cells are neighbours when pixels of theirs lie within a Euclidean reach of d pixels, and w(i, j) counts those ordered pixel pairs
+// (ribca_contact_table), and the label-permutation null of the type pairs over ANY directed edge list (ribca_edge_perm_counts).  Integers only:
+// include/ribca_hip.h states the contract, tests/contact_numpy.py restates it.
+//   contact_init     the (n, S) hash table of the workspace (keys -1, sums 0), the overflow flags and over = (0, INT_MAX).
+//   contact_stencil  one workgroup per CT_TILE x CT_TILE pixel tile: the tile and a d-wide halo go to LDS already mapped to cell indices (-1 = no
+//                    cell, also outside the image), one global read of the mask per staged pixel.  Every foreground pixel walks the offsets of
+//                    the disk in LDS ((dr, dc) loops with the integer disk test, no table) and keeps ONE run (neighbour, count) in scalars, so a
+//                    stretch of offsets that meets the same cell is one event; no per-pixel array, nothing goes to scratch.  Events (i, j, count)
+//                    are summed in an LDS hash table per workgroup (64-bit compare-and-swap on the key, 32-bit add on the count, CT_PROBES slots
+//                    at most); an event that finds no slot goes straight to the global table.  The flush is one global insert per distinct pair.
+//   global insert    open addressing in row i of the (n, S) table: a 32-bit compare-and-swap on the key, a 64-bit integer add on the sum, at most S
+//                    probes, then the overflow is recorded (flag of the cell, count of flagged cells, lowest flagged cell).  A row holds S distinct
+//                    keys whatever the arrival order, so it overflows exactly when its degree exceeds S.  No loop waits for another thread.
+//   contact_rows     one wave per row: the keys to LDS, every entry finds its rank among the row's keys (they are distinct) and goes to that
+//                    slot of the output; degree = the number of keys.  Slot positions depend on the arrival order, ranks and integer sums do not.
+//   edge_labels      the shuffled labels of a batch of permutations, one byte per cell (the rows of enrichment.hip, which stays as it is).
+//   edge_count       one thread per directed edge of a slab, a [T][T] LDS histogram of at most 16 KiB, one 64-bit atomic per non-zero entry.
+// Measured forms: DESIGN.md section 19.
+#include <limits.h>
+
+#include <algorithm>
+
+#include "../../include/ribca_hip.h"
+#include "ribca_common.h"
+#include "ribca_perm.h"
+#include "ribca_scratch.h"
+#include "ribca_status.h"
+
+namespace ribca {
+namespace {
+
+constexpr int CT_TILE = 32;                  // pixels of a workgroup's tile along either axis
+constexpr int CT_D_MAX = 8;                  // the reach: a halo of 8 pixels
+constexpr int CT_SIDE = CT_TILE + 2 * CT_D_MAX;
+constexpr int CT_HASH = 1024;                // entries of the workgroup's LDS table
+constexpr int CT_HASH_BITS = 10;
+constexpr int CT_PROBES = 8;                 // slots an event tries in LDS before it goes to the global table
+constexpr int CT_N_MAX = 1 << 21;
+constexpr int CT_S_MIN = 8, CT_S_MAX = 1024;
+constexpr int CT_ROWS = 4;                   // rows of one contact_rows workgroup: one wave each
+constexpr unsigned long long CT_EMPTY = ~0ull;
+
+constexpr int EP_T_MAX = 64;
+constexpr int EP_N_MAX = 1 << 30;
+constexpr int EP_BATCH = 128;                // permutations whose label rows the workspace holds at most
+constexpr long long EP_ROW_BYTES = 64ll << 20;      // ... and the bytes of them (one row when a single one is larger)
+constexpr int EP_SLAB = 4096;                // edges of one counting workgroup
+constexpr uint8_t EP_SKIP = 255;
+
+static_assert(1 << CT_HASH_BITS == CT_HASH, "the LDS table is indexed by the top bits of a 32-bit hash");
+static_assert(CT_TILE * CT_TILE % 256 == 0, "whole rounds of a 256-thread workgroup");
+static_assert(CT_SIDE * CT_SIDE * 4 + CT_HASH * 12 <= 32 * 1024, "LDS of contact_stencil");
+static_assert(CT_ROWS * CT_S_MAX * 4 <= 16 * 1024, "LDS of contact_rows");
+static_assert(EP_T_MAX * EP_T_MAX * 4 <= 16 * 1024, "the LDS histogram");
+
+int fail(const char* msg) { return api_fail(msg); }
+
+__global__ __launch_bounds__(256) void contact_init_kernel(int32_t* __restrict__ keys, unsigned long long* __restrict__ sums, size_t slots,
+                                                           int32_t* __restrict__ flag, int n, int32_t* __restrict__ over) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < slots; e += stride) {
+    keys[e] = -1;
+    sums[e] = 0ull;
+  }
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < (size_t)n; e += stride) flag[e] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    over[0] = 0;
+    over[1] = INT_MAX;
+  }
+}
+
+// sums[i][slot of j] += count; at most S probes, then the overflow of row i is recorded
+__device__ __forceinline__ void global_insert(int32_t* __restrict__ keys, unsigned long long* __restrict__ sums, int32_t* __restrict__ flag,
+                                              int32_t* __restrict__ over, int S, int log_s, int i, int j, unsigned int count) {
+  int32_t* __restrict__ row = keys + (size_t)i * S;
+  int slot = (int)(((uint32_t)j * 0x9E3779B1u) >> (32 - log_s));
+  for (int probe = 0; probe < S; ++probe) {
+    const int32_t old = atomicCAS(&row[slot], -1, j);
+    if (old == -1 || old == j) {
+      atomicAdd(&sums[(size_t)i * S + slot], (unsigned long long)count);
+      return;
+    }
+    slot = (slot + 1) & (S - 1);
+  }
+  if (atomicExch(&flag[i], 1) == 0) atomicAdd(&over[0], 1);
+  atomicMin(&over[1], i);
+}
+
+// one event of the stencil: into the workgroup's table if one of CT_PROBES slots takes it, else into the global one
+__device__ __forceinline__ void emit(unsigned long long* hkey, unsigned int* hcount, int32_t* __restrict__ keys,
+                                     unsigned long long* __restrict__ sums, int32_t* __restrict__ flag, int32_t* __restrict__ over, int S, int log_s,
+                                     int i, int j, unsigned int count) {
+  const unsigned long long key = ((unsigned long long)(uint32_t)i << 32) | (uint32_t)j;
+  uint32_t h = (uint32_t)i * 0x9E3779B1u ^ (uint32_t)j * 0x85EBCA77u;
+  h ^= h >> 15;
+  int slot = (int)((h * 0x2C1B3C6Du) >> (32 - CT_HASH_BITS));
+  for (int probe = 0; probe < CT_PROBES; ++probe) {
+    const unsigned long long old = atomicCAS(&hkey[slot], CT_EMPTY, key);
+    if (old == CT_EMPTY || old == key) {
+      atomicAdd(&hcount[slot], count);
+      return;
+    }
+    slot = (slot + 1) & (CT_HASH - 1);
+  }
+  global_insert(keys, sums, flag, over, S, log_s, i, j, count);
+}
+
+// grid: the tiles in row-major order, tiles_x of them per row of tiles
+__global__ __launch_bounds__(256) void contact_stencil_kernel(const int32_t* __restrict__ mask, int H, int W, const int32_t* __restrict__ label_to_cell,
+                                                              int L, int n, int d, int tiles_x, int S, int log_s, int32_t* __restrict__ keys,
+                                                              unsigned long long* __restrict__ sums, int32_t* __restrict__ flag,
+                                                              int32_t* __restrict__ over) {
+  __shared__ int cell[CT_SIDE * CT_SIDE];
+  __shared__ unsigned long long hkey[CT_HASH];
+  __shared__ unsigned int hcount[CT_HASH];
+  const int tid = threadIdx.x;
+  const int r0 = (int)(blockIdx.x / (unsigned)tiles_x) * CT_TILE, c0 = (int)(blockIdx.x % (unsigned)tiles_x) * CT_TILE;
+  const int side = CT_TILE + 2 * d;
+  for (int e = tid; e < CT_HASH; e += 256) {
+    hkey[e] = CT_EMPTY;
+    hcount[e] = 0u;
+  }
+  for (int e = tid; e < side * side; e += 256) {
+    const int r = r0 - d + e / side, c = c0 - d + e % side;
+    int v = -1;
+    if (r >= 0 && r < H && c >= 0 && c < W) {
+      const int32_t lab = mask[(size_t)r * W + c];
+      if ((unsigned)lab < (unsigned)L) {
+        const int32_t t = label_to_cell[lab];
+        if ((unsigned)t < (unsigned)n) v = t;      // a table entry outside [0, n) is no cell: it never indexes a row
+      }
+    }
+    cell[e] = v;
+  }
+  __syncthreads();
+  const int d2 = d * d;
+  for (int k = tid; k < CT_TILE * CT_TILE; k += 256) {
+    const int pr = k / CT_TILE + d, pc = k % CT_TILE + d;      // in the staged square; pixels outside the image hold -1
+    const int own = cell[pr * side + pc];
+    if (own < 0) continue;
+    int run = -1;
+    unsigned int run_count = 0u;
+    for (int dr = -d; dr <= d; ++dr) {
+      for (int dc = -d; dc <= d; ++dc) {
+        if (dr * dr + dc * dc > d2) continue;
+        const int q = cell[(pr + dr) * side + pc + dc];
+        if (q < 0 || q == own) continue;      // (0, 0) is the pixel itself
+        if (q == run) {
+          ++run_count;
+        } else {
+          if (run_count) emit(hkey, hcount, keys, sums, flag, over, S, log_s, own, run, run_count);
+          run = q;
+          run_count = 1u;
+        }
+      }
+    }
+    if (run_count) emit(hkey, hcount, keys, sums, flag, over, S, log_s, own, run, run_count);
+  }
+  __syncthreads();
+  for (int e = tid; e < CT_HASH; e += 256) {
+    const unsigned long long key = hkey[e];
+    if (key != CT_EMPTY) global_insert(keys, sums, flag, over, S, log_s, (int)(key >> 32), (int)(uint32_t)key, hcount[e]);
+  }
+}
+
+// nbr[i], pairs[i] = the entries of row i in ascending key order, -1 / 0 behind them; degree[i] = their number: one wave per row
+__global__ __launch_bounds__(64 * CT_ROWS) void contact_rows_kernel(const int32_t* __restrict__ keys, const unsigned long long* __restrict__ sums, int n,
+                                                                    int S, int32_t* __restrict__ nbr, unsigned long long* __restrict__ pairs,
+                                                                    int32_t* __restrict__ degree, int32_t* __restrict__ over) {
+  __shared__ int row[CT_ROWS][CT_S_MAX];
+  __shared__ int filled[CT_ROWS];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long i = (long long)blockIdx.x * CT_ROWS + w;
+  const bool live = i < n;
+  if (lane == 0) filled[w] = 0;
+  if (live)
+    for (int e = lane; e < S; e += 64) row[w][e] = keys[(size_t)i * S + e];
+  __syncthreads();
+  if (live) {
+    int mine = 0;
+    for (int e = lane; e < S; e += 64) mine += row[w][e] >= 0 ? 1 : 0;
+    if (mine) atomicAdd(&filled[w], mine);
+  }
+  __syncthreads();
+  if (live) {
+    const int deg = filled[w];
+    for (int e = lane; e < S; e += 64) {
+      const int key = row[w][e];
+      if (key >= 0) {
+        int rank = 0;
+        for (int o = 0; o < S; ++o) {
+          const int other = row[w][o];
+          rank += other >= 0 && other < key ? 1 : 0;
+        }
+        nbr[(size_t)i * S + rank] = key;      // distinct keys: distinct ranks below deg
+        pairs[(size_t)i * S + rank] = sums[(size_t)i * S + e];
+      }
+      if (e >= deg) {
+        nbr[(size_t)i * S + e] = -1;
+        pairs[(size_t)i * S + e] = 0ull;
+      }
+    }
+    if (lane == 0) degree[i] = deg;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && over[0] == 0) over[1] = -1;      // nobody else touches over in this launch
+}
+
+// labels[j][i] = (uint8) cell_type[sigma_{p0 + j}(i)], EP_SKIP where that is outside [0, T): grid (ceil(n / 256), batch)
+__global__ __launch_bounds__(256) void edge_labels_kernel(const int32_t* __restrict__ cell_type, int n, int T, int h, uint64_t image_key, uint64_t p0,
+                                                          uint8_t* __restrict__ labels) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = feistel_walk(perm_key(image_key, p0 + blockIdx.y), (uint32_t)i, (uint32_t)n, h);
+  uint8_t lab = EP_SKIP;
+  if (s < (uint32_t)n) {
+    const int32_t t = cell_type[s];
+    if ((unsigned)t < (unsigned)T) lab = (uint8_t)t;
+  }
+  labels[(size_t)blockIdx.y * n + i] = lab;
+}
+
+// counts[j][label(src[e])][label(dst[e])] += 1 over the slab's edges: grid (ceil(E / EP_SLAB), batch)
+__global__ __launch_bounds__(256) void edge_count_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ dst, long long E,
+                                                         const uint8_t* __restrict__ labels, int n, int T, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int hist[EP_T_MAX * EP_T_MAX];
+  const int tid = threadIdx.x;
+  const int TT = T * T;
+  for (int e = tid; e < TT; e += 256) hist[e] = 0u;
+  __syncthreads();
+  const uint8_t* __restrict__ lab = labels + (size_t)blockIdx.y * n;
+  const long long first = (long long)blockIdx.x * EP_SLAB;
+  const long long last = first + EP_SLAB < E ? first + EP_SLAB : E;
+  for (long long e = first + tid; e < last; e += 256) {
+    const int32_t s = src[e], t = dst[e];
+    if ((unsigned)s >= (unsigned)n || (unsigned)t >= (unsigned)n) continue;
+    const unsigned a = lab[s], b = lab[t];
+    if (a < (unsigned)T && b < (unsigned)T) atomicAdd(&hist[a * T + b], 1u);
+  }
+  __syncthreads();
+  unsigned long long* __restrict__ out = counts + (size_t)blockIdx.y * TT;
+  for (int e = tid; e < TT; e += 256)
+    if (hist[e]) atomicAdd(&out[e], (unsigned long long)hist[e]);
+}
+
+int log2_of_slots(int S) {      // 3 .. 10 for a power of two in 8 .. 1024, -1 otherwise
+  for (int b = 3; b <= 10; ++b)
+    if (S == 1 << b) return b;
+  return -1;
+}
+
+bool table_sizes_ok(int H, int W, int n, int S) {
+  return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31) && n >= 1 && n <= CT_N_MAX && S >= CT_S_MIN && S <= CT_S_MAX && log2_of_slots(S) > 0;
+}
+
+struct ContactWs {
+  int32_t* keys;                  // (n, S): the neighbour of a slot, -1 = free
+  unsigned long long* sums;       // (n, S): its pixel pairs
+  int32_t* flag;                  // (n): the row did not fit
+};
+
+ContactWs carve_contact(Carver& cv, int n, int S) {
+  ContactWs w;
+  w.keys = cv.take<int32_t>((size_t)n * S);
+  w.sums = cv.take<unsigned long long>((size_t)n * S);
+  w.flag = cv.take<int32_t>((size_t)n);
+  return w;
+}
+
+// B = min(P, 128, max(1, 64 MiB / n))
+int edge_batch(int n, int P) { return (int)std::min<long long>(std::min(P, EP_BATCH), std::max(1ll, EP_ROW_BYTES / n)); }
+
+bool edge_sizes_ok(int n, int P) { return n >= 1 && n <= EP_N_MAX && P >= 1; }
+
+}  // namespace
+}  // namespace ribca
+
+using namespace ribca;
+
+extern "C" {
+
+int64_t ribca_contact_table_ws_bytes(int32_t H, int32_t W, int32_t n, int32_t S) {
+  if (!table_sizes_ok(H, W, n, S)) return 0;
+  Carver cv(nullptr);
+  carve_contact(cv, n, S);
+  return (int64_t)cv.off;
+}
+
+int ribca_contact_table(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, int32_t d, int32_t S,
+                        int32_t* nbr, uint64_t* pairs, int32_t* degree, int32_t* over, void* ws, int64_t ws_bytes, void* stream) {
+  if (!mask || !label_to_cell || !nbr || !pairs || !degree || !over || !ws) return fail("ribca_contact_table: NULL buffer");
+  if (H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return fail("ribca_contact_table: needs 1 <= H, W and H W < 2^31");
+  if (L < 1) return fail("ribca_contact_table: needs 1 <= L");
+  if (n < 1 || n > CT_N_MAX) return fail("ribca_contact_table: needs 1 <= n <= 2^21");
+  if (d < 1 || d > CT_D_MAX) return fail("ribca_contact_table: needs 1 <= d <= 8");
+  if (S < CT_S_MIN || S > CT_S_MAX || log2_of_slots(S) < 0) return fail("ribca_contact_table: S must be a power of two in 8 .. 1024");
+  if (ws_bytes < ribca_contact_table_ws_bytes(H, W, n, S)) return fail("ribca_contact_table: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  Carver cv(ws);
+  const ContactWs w = carve_contact(cv, n, S);
+  const size_t slots = (size_t)n * S;
+  const int tiles_x = (W + CT_TILE - 1) / CT_TILE, tiles_y = (H + CT_TILE - 1) / CT_TILE;      // tiles_x tiles_y < 2^31 / 1024 + H + W
+  hipLaunchKernelGGL(contact_init_kernel, dim3((unsigned)std::min<size_t>((slots + 255) / 256, 16384)), dim3(256), 0, s, w.keys, w.sums, slots, w.flag,
+                     n, over);
+  hipLaunchKernelGGL(contact_stencil_kernel, dim3((unsigned)((long long)tiles_x * tiles_y)), dim3(256), 0, s, mask, H, W, label_to_cell, L, n, d,
+                     tiles_x, S, log2_of_slots(S), w.keys, w.sums, w.flag, over);
+  hipLaunchKernelGGL(contact_rows_kernel, dim3((unsigned)((n + CT_ROWS - 1) / CT_ROWS)), dim3(64 * CT_ROWS), 0, s, w.keys, w.sums, n, S, nbr,
+                     reinterpret_cast<unsigned long long*>(pairs), degree, over);
+  RIBCA_FINISH();
+  return 0;
+}
+
+int64_t ribca_edge_perm_counts_ws_bytes(int32_t n, int32_t P) {
+  if (!edge_sizes_ok(n, P)) return 0;
+  Carver cv(nullptr);
+  cv.take<uint8_t>((size_t)edge_batch(n, P) * (size_t)n);
+  return (int64_t)cv.off;
+}
+
+int ribca_edge_perm_counts(const int32_t* src, const int32_t* dst, int64_t E, const int32_t* cell_type, int32_t n, int32_t T, uint64_t seed,
+                           int32_t image, int64_t p0, int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream) {
+  if (!src || !dst || !cell_type || !counts || !ws) return fail("ribca_edge_perm_counts: NULL buffer");
+  if (E < 1 || E >= (1ll << 31)) return fail("ribca_edge_perm_counts: needs 1 <= E < 2^31");
+  if (n < 1 || n > EP_N_MAX) return fail("ribca_edge_perm_counts: needs 1 <= n <= 2^30");
+  if (T < 1 || T > EP_T_MAX) return fail("ribca_edge_perm_counts: needs 1 <= T <= 64");
+  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31)) return fail("ribca_edge_perm_counts: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (ws_bytes < ribca_edge_perm_counts_ws_bytes(n, P)) return fail("ribca_edge_perm_counts: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int batch_max = edge_batch(n, P);
+  Carver cv(ws);
+  uint8_t* labels = cv.take<uint8_t>((size_t)batch_max * (size_t)n);
+  const int h = perm_half_bits(n);
+  const uint64_t image_key = perm_image_key(seed, image);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+  for (int64_t j0 = 0; j0 < P; j0 += batch_max) {      // the batches follow one another on the stream: the label rows are reused
+    const int batch = (int)std::min<int64_t>(batch_max, P - j0);
+    hipLaunchKernelGGL(edge_labels_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, s, cell_type, n, T, h, image_key,
+                       (uint64_t)(p0 + j0), labels);
+    hipLaunchKernelGGL(edge_count_kernel, dim3((unsigned)((E + EP_SLAB - 1) / EP_SLAB), (unsigned)batch), dim3(256), 0, s, src, dst, (long long)E,
+                       labels, n, T, out + (size_t)j0 * T * T);
+  }
+  RIBCA_FINISH();
+  return 0;
+}
+
+}  // extern "C"

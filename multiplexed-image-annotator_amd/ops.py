@@ -397,6 +397,109 @@ def nearest_perm_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_t
     return out
 
 
+CONTACT_MAX_REACH = 8             # csrc/contact.hip: the halo of a pixel tile
+CONTACT_MAX_TYPES = 254           # the uint8 index image of colorize, as for the other cell-type steps
+CONTACT_PERM_MAX_TYPES = 64       # the LDS histogram of the null
+CONTACT_FIRST_SLOTS = 32          # slots per row of the first attempt; doubled while a row overflows
+CONTACT_MAX_SLOTS = 1024
+CONTACT_MAX_TABLE_BYTES = 2 << 30      # of nbr + pairs, 12 bytes per slot
+
+
+def contact_table_ws_bytes(h: int, w: int, n: int, slots: int) -> int:
+    return int(lib().ribca_contact_table_ws_bytes(int(h), int(w), int(n), int(slots)))
+
+
+def edge_perm_counts_ws_bytes(n: int, n_perms: int) -> int:
+    return int(lib().ribca_edge_perm_counts_ws_bytes(int(n), int(n_perms)))
+
+
+def contact_table(mask: torch.Tensor, label_to_cell: torch.Tensor, n: int, d: int, slots: int, ws: Optional[torch.Tensor] = None):
+    """(nbr (n, slots) int32, pairs (n, slots) int64, degree (n) int32, over (2) int32) device tensors of ribca_contact_table, one attempt at
+    ``slots`` slots per row: with over[0] == 0 row i lists the cells in contact with cell i in ascending index order and the ordered pixel pairs
+    within the reach ``d`` beside them; include/ribca_hip.h states the contract."""
+    if mask.dtype != torch.int32 or mask.dim() != 2 or not mask.is_cuda or label_to_cell.dtype != torch.int32 or label_to_cell.dim() != 1:
+        raise ValueError("contact_table takes an (H, W) int32 device mask and an (L) int32 label -> cell table")
+    dev = mask.device
+    mask, table = mask.contiguous(), label_to_cell.contiguous().to(dev)
+    h, w = mask.shape
+    rows, cols = max(int(n), 0), max(int(slots), 0)
+    nbr = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+    pairs = torch.empty((rows, cols), dtype=torch.int64, device=dev)
+    degree = torch.empty((rows,), dtype=torch.int32, device=dev)
+    over = torch.empty((2,), dtype=torch.int32, device=dev)
+    if ws is None:
+        ws = _scratch(contact_table_ws_bytes(h, w, n, slots), dev)
+    check(lib().ribca_contact_table(ptr(mask), h, w, ptr(table), table.numel(), int(n), int(d), int(slots), ptr(nbr), ptr(pairs), ptr(degree),
+                                    ptr(over), ptr(ws), ws.numel(), stream_ptr()), "ribca_contact_table")
+    return nbr, pairs, degree, over
+
+
+def contact_graph(mask: torch.Tensor, ids: np.ndarray, d: int, first_slots: int = CONTACT_FIRST_SLOTS) -> Dict[str, np.ndarray]:
+    """The contact graph of an (H, W) int32 device mask over the cells ``ids`` (ascending mask labels, cell i = ids[i]; the label -> cell table
+    is built as ``colorize`` builds it, label 0 never a cell): two cells are in contact when pixels of theirs lie within ``d`` pixels (Euclidean,
+    1 <= d <= 8).  Returns host arrays: the directed edge list ``src``, ``dst`` int32 and ``pairs`` int64 (the ordered pixel pairs within the
+    reach) sorted by (src, dst), each contact in both directions, ``degree`` (n) int32, and ``slots`` = the row length that fitted.  The table
+    starts at ``first_slots`` slots per cell and doubles while a row overflows; ValueError when that would pass 1024 slots or 2 GiB -- a
+    background region labelled as a cell is the usual cause, and the message names its mask label."""
+    assert mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n = len(ids)
+    if n == 0:
+        return {"src": np.zeros(0, np.int32), "dst": np.zeros(0, np.int32), "pairs": np.zeros(0, np.int64), "degree": np.zeros(0, np.int32),
+                "slots": int(first_slots)}
+    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
+    table[ids] = np.arange(n, dtype=np.int32)
+    table[0] = -1      # colorize paints labels > 0 only
+    tab_d = torch.from_numpy(table).to(mask.device)
+    slots = int(first_slots)
+    while True:
+        nbr, pairs, degree, over = contact_table(mask, tab_d, n, d, slots)
+        failed, lowest = over.tolist()
+        if failed == 0:
+            break
+        why = (f"contact_graph: {failed} cell(s) touch more than {slots} others at reach {d}, the lowest of them mask label {int(ids[lowest])}; "
+               "a background region labelled as a cell is the usual cause")
+        if slots * 2 > CONTACT_MAX_SLOTS:
+            raise ValueError(f"{why} (the table stops at {CONTACT_MAX_SLOTS} slots per cell)")
+        if 12 * n * slots * 2 > CONTACT_MAX_TABLE_BYTES:
+            raise ValueError(f"{why} (a table of {slots * 2} slots for {n} cells would pass 2 GiB)")
+        slots *= 2
+    nbr_h, pairs_h, deg_h = nbr.cpu().numpy(), pairs.cpu().numpy(), degree.cpu().numpy()
+    keep = np.arange(slots)[None, :] < deg_h[:, None]      # row-major: sorted by (src, dst)
+    src = np.repeat(np.arange(n, dtype=np.int32), deg_h)
+    return {"src": src, "dst": np.ascontiguousarray(nbr_h[keep], dtype=np.int32), "pairs": np.ascontiguousarray(pairs_h[keep], dtype=np.int64),
+            "degree": deg_h.astype(np.int32), "slots": slots}
+
+
+def edge_perm_counts(src, dst, cell_type: np.ndarray, n_types: int, seed: int, image: int, p0: int, n_perms: int,
+                     out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """(n_perms, n_types, n_types) int64 device tensor: the type pairs over the directed edges (src[e], dst[e]) -- int32 arrays or device
+    tensors -- under the label permutations p0 .. p0 + n_perms - 1 of (seed, image): cell i carries cell_type[sigma_p(i)], the sigma of
+    ``nhood_perm_counts``.  An edge with an end outside [0, n) or a label outside [0, n_types) is skipped.  Accumulates into ``out`` when given
+    (the images of a group)."""
+    dev = device or (src.device if isinstance(src, torch.Tensor) else _lib.require_gpu())
+    sd = src.to(dev) if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, dtype=np.int32)).to(dev)
+    dd = dst.to(dev) if isinstance(dst, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(dst, dtype=np.int32)).to(dev)
+    if sd.dtype != torch.int32 or dd.dtype != torch.int32 or sd.dim() != 1 or dd.shape != sd.shape:
+        raise ValueError("edge_perm_counts takes two (E) int32 edge arrays")
+    sd, dd = sd.contiguous(), dd.contiguous()
+    labels = np.ascontiguousarray(cell_type, dtype=np.int32).reshape(-1)
+    n = len(labels)
+    td = torch.from_numpy(labels).to(dev)
+    shape = (max(int(n_perms), 0), max(int(n_types), 0), max(int(n_types), 0))
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != sd.device:
+        raise ValueError(f"edge_perm_counts: out must be a contiguous int64 tensor of shape {shape} on the device of the edges")
+    if ws is None:
+        ws = _scratch(edge_perm_counts_ws_bytes(n, n_perms), dev)
+    elif ws.dtype != torch.uint8 or ws.device != sd.device or not ws.is_contiguous():
+        raise ValueError("edge_perm_counts: ws must be a contiguous uint8 tensor on the device of the edges")
+    check(lib().ribca_edge_perm_counts(ptr(sd), ptr(dd), sd.numel(), ptr(td), n, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0),
+                                       int(n_perms), ptr(out), ptr(ws), ws.numel(), stream_ptr()), "ribca_edge_perm_counts")
+    return out
+
+
 AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
 AUTOCORR_MAX_NEIGHBOURS = 31
 

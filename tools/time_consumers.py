@@ -13,7 +13,10 @@ permutations, and the numpy restatement of tests/autocorr_numpy.py on 10 of the 
 (csrc/local_autocorr.hip): the per-cell neighbour sums and the counts of 999 conditional permutations of the same table, and the numpy restatement
 of tests/local_autocorr_numpy.py on one of them; and the nearest cell of every type (csrc/nearest.hip): the (n, 12) distance table and 100 label
 permutations of the nearest-distance band counts in 16 bands of 30 px, inputs on the device, for a uniform label mix and for one with half the cells
-of one type, and the numpy restatement of tests/nearest_numpy.py on the first 10 000 cells, scaled by n^2 (``--nearest``: this section alone)."""
+of one type, and the numpy restatement of tests/nearest_numpy.py on the first 10 000 cells, scaled by n^2 (``--nearest``: this section alone); and
+the contact graph of the mask (csrc/contact.hip): the (n, 32) contact table at the reaches 1, 4 and 8 px, mask and label table on the device, then
+1000 label permutations over the directed edges of each at 12 cell types, and the numpy restatement of tests/contact_numpy.py on the top-left
+1024 x 1024 crop of the same mask, scaled by the area (``--contact``: this section alone)."""
 import os
 import sys
 import time
@@ -96,8 +99,84 @@ def time_nearest():
           f"cells: {same}")
 
 
+# ---- the contact graph of the mask (csrc/contact.hip): the table at d = 1, 4, 8 and P = 1000 label permutations over its edges, T = 12 ----------------
+def time_contact():
+    """mask, label table, outputs and workspaces on the device before the clock starts: the entry points themselves, median of five calls after a
+    warm-up; then the restatement on a crop, checked against the GPU on the same crop"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import contact_numpy as CN
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    perms, t, slots = 1000, 12, 32
+    h, w = mask.shape
+    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
+    table[ids] = np.arange(n, dtype=np.int32)
+    tab_d = torch.from_numpy(table).to(dev)
+    td = torch.from_numpy(np.ascontiguousarray(tidx, dtype=np.int32)).to(dev)
+    nbr = torch.empty((n, slots), dtype=torch.int32, device=dev)
+    pairs = torch.empty((n, slots), dtype=torch.int64, device=dev)
+    degree = torch.empty((n,), dtype=torch.int32, device=dev)
+    over = torch.empty((2,), dtype=torch.int32, device=dev)
+    ws1 = torch.empty(ops.contact_table_ws_bytes(h, w, n, slots), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty(ops.edge_perm_counts_ws_bytes(n, perms), dtype=torch.uint8, device=dev)
+    counts = torch.zeros((perms, t, t), dtype=torch.int64, device=dev)
+
+    def median_of_five(fn):
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(1e3 * (time.perf_counter() - t0))
+        return f"median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} of 5"
+
+    for d in (1, 4, 8):
+        def graph():
+            _lib.check(lib().ribca_contact_table(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, d, slots, ptr(nbr), ptr(pairs), ptr(degree), ptr(over),
+                                                 ptr(ws1), ws1.numel(), stream_ptr()), "contact")
+
+        line = median_of_five(graph)
+        g = ops.contact_graph(mask, ids, d)
+        print(f"contact table, d = {d}, {slots} slots ({ws1.numel() / 2 ** 20:.1f} MiB workspace): {line} for {n} cells, {h}x{w}; {len(g['src'])} directed "
+              f"edges, largest degree {int(g['degree'].max())}, overflow {over.tolist()}")
+        if len(g["src"]) == 0:
+            continue
+        sd, dd = torch.from_numpy(g["src"]).to(dev), torch.from_numpy(g["dst"]).to(dev)
+
+        def null():
+            counts.zero_()
+            _lib.check(lib().ribca_edge_perm_counts(ptr(sd), ptr(dd), sd.numel(), ptr(td), n, t, 0, 0, 0, perms, ptr(counts), ptr(ws2), ws2.numel(),
+                                                    stream_ptr()), "contact")
+
+        print(f"edge type pairs, {perms} label permutations, d = {d} ({ws2.numel() / 2 ** 20:.1f} MiB workspace): {median_of_five(null)} for {len(g['src'])} "
+              f"directed edges")
+    side = 1024
+    crop = np.ascontiguousarray(mask[:side, :side].cpu().numpy())
+    crop_d = torch.from_numpy(crop).to(dev)
+    for d in (1, 4, 8):
+        t0 = time.perf_counter()
+        want = CN.edge_list(CN.pair_weights(crop, table, n, d))
+        host_ms = 1e3 * (time.perf_counter() - t0)
+        g = ops.contact_graph(crop_d, ids, d)
+        same = all(np.array_equal(a, b) for a, b in zip(want, (g["src"], g["dst"], g["pairs"])))
+        print(f"numpy restatement, d = {d}, top-left {side}x{side} crop (host): {host_ms:.0f} ms -> {host_ms * (h * w) / (side * side) / 1e3:.1f} s scaled by "
+              f"area to {h}x{w}; equal to the GPU edge list of the same crop: {same}")
+    few = 10
+    g = ops.contact_graph(mask, ids, 4)
+    t0 = time.perf_counter()
+    want = CN.edge_perm_counts(g["src"], g["dst"], tidx, t, 0, 0, 0, few)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    same = np.array_equal(ops.edge_perm_counts(g["src"], g["dst"], tidx, t, 0, 0, 0, few).cpu().numpy(), want)
+    print(f"numpy restatement of the null, d = 4, {few} permutations over {len(g['src'])} edges (host): {host_ms:.0f} ms -> "
+          f"{host_ms * perms / few / 1e3:.1f} s for {perms}; equal to the GPU counts: {same}")
+
+
 if "--nearest" in sys.argv:      # this section alone
     time_nearest()
+    sys.exit(0)
+if "--contact" in sys.argv:      # this section alone
+    time_contact()
     sys.exit(0)
 
 for name, fn in (("colorize", lambda: ops.colorize(mask, ids, pal[tidx], colors.confidence_colors(conf), (tidx + 1).astype(np.uint8))),
@@ -288,3 +367,6 @@ print(f"numpy restatement, 1 conditional permutation (host): {oracle_ms:.0f} ms 
 
 # ---- the nearest cell of every type: defined above, beside the switch that runs it alone ------------------------------------------------------------
 time_nearest()
+
+# ---- the contact graph of the mask: defined above as well -----------------------------------------------------------------------------------------
+time_contact()
