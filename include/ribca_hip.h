@@ -321,6 +321,33 @@ int64_t ribca_edge_perm_counts_ws_bytes(int32_t n, int32_t P);
 int ribca_edge_perm_counts(const int32_t* src, const int32_t* dst, int64_t E, const int32_t* cell_type, int32_t n, int32_t T, uint64_t seed,
                            int32_t image, int64_t p0, int32_t P, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- per-cell morphology sums of the segmentation mask (csrc/morphology.hip) -----------------------------------------
+ * mask (H, W) int32 row-major and label_to_cell (L) int32 on the device; pixel ownership is the rule of ribca_contact_table: the pixel p belongs to
+ * the cell c = label_to_cell[mask[p]] when 0 <= mask[p] < L and 0 <= c < n, and to no cell otherwise; a label in several blobs is one cell.  With
+ * S = the set of the pixels (r, c) of cell i, sums (n, 16) uint64 is OVERWRITTEN with
+ *     0        the area |S|
+ *     1, 2     sum r, sum c                    3, 4, 5   sum r^2, sum c^2, sum r c
+ *     6, 7, 8  the 4-neighbour pixel edges that leave S -- one (pixel of S, neighbour) pair each -- into another cell / into no cell inside the
+ *              image / out of the image; column 6 is the sum over j of w(i, j) of ribca_contact_table at d = 1
+ *     9 .. 11  the perimeter classes p_a, p_b, p_c of scikit-image's perimeter(neighbourhood=4): a pixel of S is a BORDER pixel of i when one of
+ *              its four neighbours is not in S (outside the image is not in S); for a border pixel, a = the number of its 4-neighbours that are
+ *              border pixels of i, b = the same over its four diagonal neighbours, v = 1 + 2 a + 10 b; p_a counts v in {5, 7, 15, 17, 25, 27},
+ *              p_b counts v in {21, 33}, p_c counts v in {13, 23}, every other v counts nowhere (perimeter = p_a + p_b sqrt 2 + p_c (1 + sqrt 2) / 2)
+ *     12 .. 14 the bit-quad counts q1, q3, qd: over each of the (H + 1)(W + 1) 2 x 2 windows of the mask extended by one ring of "no cell", every
+ *              window once, a cell that holds k of the window's four pixels counts q1 at k = 1, q3 at k = 3 and qd at k = 2 with the two on a
+ *              diagonal; (q1 - q3 - 2 qd) / 4 is the Euler number at 8-connectivity: components (8-connected) minus holes (4-connected)
+ *     15       the pixels of S with r0 <= r < r1 and c0 <= c < c1 of the cell's row (r0, r1, c0, c1) of rect (n, 4) int32 (any values; an empty
+ *              rectangle counts nothing); 0 when rect is NULL
+ * and bbox (n, 4) int32 is OVERWRITTEN with rmin, rmax, cmin, cmax (inclusive), (INT32_MAX, -1, INT32_MAX, -1) for a cell without a pixel.
+ * Integer atomics only: a pure function of (mask, label_to_cell, rect), the same for every launch geometry and every run.  1 <= H, W <= 65535 (so
+ * that sum r^2 stays below 2^63), H W < 2^31, 1 <= L, 1 <= n <= 2^21.  workspace: ribca_mask_morphology_ws_bytes(H, W, n) bytes; 0 for arguments the
+ * entry point refuses.  The piece is RESERVED: 256 bytes today, and the present kernels accumulate in the outputs and neither read nor write
+ * it; a NULL or short workspace is refused all the same, as for every entry point that takes one, so that a later form can use it.  No loop of the kernels waits for another thread.  The entry
+ * point does not synchronise. */
+int64_t ribca_mask_morphology_ws_bytes(int32_t H, int32_t W, int32_t n);
+int ribca_mask_morphology(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, const int32_t* rect,
+                          uint64_t* sums, int32_t* bbox, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

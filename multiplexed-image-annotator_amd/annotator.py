@@ -1114,6 +1114,107 @@ class Annotator(object):
                                 files[0], cells, n_edges, d, t, max_degree, slots, p, seed, graph_ms, perm_ms, draw_ms))
         return None
 
+    # ---- cell morphology: what the cells themselves look like, read off the segmentation mask (steinbock's regionprops, MCMICRO's quantification) --
+    def cell_morphology(self, integrate=True):
+        """The morphology table of every image, built on the GPU from the segmentation mask (ops.mask_morphology, csrc/morphology.hip: integer
+        sums per cell) and finished on the host in fp64 (morphology.features, which states every formula): area, centroid, bounding box, extent,
+        equivalent diameter, major and minor axis, eccentricity, orientation, the 4-neighbourhood perimeter and circularity, the Euler number of
+        the label (1 for one solid blob: a fragmented label or one with holes shows here), the share of the outline that faces other cells,
+        whether the cell touches the image border, and ``patch_coverage``, the share of the cell inside the window its classifiers saw
+        (morphology.patch_rect at the run's patch size).  Pixel units.  Per image it writes ``{batch_id}_morphology_{image number}.csv``
+        (morphology.cells_csv, one line per cell in id order) and two maps painted through ops.colorize with viridis on FIXED scales, background
+        0: ``{batch_id}_morphology_diameter_{image number}.png`` at int(min(equivalent_diameter / (2 cell_size), 1) * 255) and
+        ``{batch_id}_morphology_coverage_{image number}.png`` at int(patch_coverage * 255).  Per group (the batch with ``integrate``, else every
+        image), with stem = ``{batch_id}_integrated_morphology`` or ``{batch_id}_morphology`` and the image number at the end of each name:
+        ``{stem}_summary.csv`` (morphology.summary_csv: n, mean, std, min, quartiles, max per cell type and feature), ``{stem}.csv``
+        (morphology.standardised_means: (mean of the type - mean of all) / std of all) and ``{stem}.png``, that matrix on +- 3; for a single image
+        these two are ``{batch_id}_morphology_means_{image number}.csv`` / ``.png``, since ``{batch_id}_morphology_{image number}.csv`` is its cell
+        table.  Records ``morphology_stats``, one record per group written by this rank; its ``kernel_ms`` is the host's clock around
+        ops.mask_morphology -- the label table, the copies to the device, both kernels and the copy of the sums back -- not the time of the
+        kernels alone (tools/time_consumers.py --morphology times those).  Cell-sharded multi-rank runs: rank 0 computes and
+        writes.  Tile-per-rank: every rank does its own images; for the integrated group one all-reduce of the cell counts and one all-gather of the
+        feature rows, which rank 0 orders by (image number, cell id), so its files are a single-rank run's."""
+        import time
+        from PIL import Image
+        from . import morphology
+        self._check_annotated("No annotations")
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        self.morphology_stats = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        n_local = len(self.annotations)
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        lut = colors.viridis_table()
+        width = 3 + len(morphology.FEATURES)      # image number, cell id, cell type, the features: a row of the tile-per-rank exchange
+        for g, members in enumerate(groups):
+            rows, image_files, kernel_ms, draw_ms = [np.zeros((0, width))], [], 0.0, 0.0
+            for i in members:
+                ids = np.asarray(self.preprocessor.cell_ids[i], dtype=np.int64)
+                mask = self.preprocessor.masks_dev[i]
+                n = len(ids)
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                h, w = (int(v) for v in mask.shape)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                boxes = np.asarray(self.preprocessor.cell_tables[i])[:, :4].reshape(n, 4)      # of the label table: what the crop was centred on
+                got = ops.mask_morphology(mask, ids, morphology.patch_rect(boxes, h, w, self.preprocessor.patch_size))
+                kernel_ms += (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                feat = morphology.features(got["sums"], got["bbox"])
+                number = self._image_number(i)
+                image_files += [f"{self.batch_id}_morphology_{number}.csv", f"{self.batch_id}_morphology_diameter_{number}.png",
+                                f"{self.batch_id}_morphology_coverage_{number}.png"]
+                with open(os.path.join(self.result_dir, image_files[-3]), "w") as f:
+                    f.write(morphology.cells_csv(ids, types, names, feat))
+                for name, idx in ((image_files[-2], morphology.diameter_colour_index(feat["equivalent_diameter"], self.cell_size)),
+                                  (image_files[-1], morphology.coverage_colour_index(feat["patch_coverage"]))):
+                    rgb = lut[idx].reshape(n, 3)
+                    painted = ops.colorize(mask, ids, rgb, rgb, idx)[0].cpu().numpy()
+                    Image.fromarray(painted).save(os.path.join(self.result_dir, name))
+                rows.append(np.concatenate([np.full((n, 1), float(number)), ids.reshape(n, 1).astype(np.float64), types.reshape(n, 1).astype(np.float64),
+                                            morphology.feature_matrix(feat)], axis=1))
+                draw_ms += (time.perf_counter() - t0) * 1e3
+            table = np.concatenate(rows, axis=0)
+            if integrate and self.tile_mode:
+                counts = np.zeros(self.world_size, dtype=np.float64)
+                counts[self.rank] = len(table)
+                counts = dist.all_reduce_sum(torch.from_numpy(counts)).numpy().astype(np.int64)
+                cap = int(counts.max())
+                send = np.zeros((cap, width), dtype=np.float64)
+                send[:len(table)] = table
+                full = dist.all_gather_rows(torch.from_numpy(send), cap * self.world_size).numpy() if cap else send      # equal shards of cap rows
+                table = np.concatenate([full[r * cap:r * cap + int(counts[r])] for r in range(self.world_size)], axis=0)
+                table = table[np.lexsort((table[:, 1], table[:, 0]))]      # by (image number, cell id): the order of a single-rank run
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            types = table[:, 2].astype(np.int64)
+            feat = morphology.from_matrix(table[:, 3:])
+            stem = f"{self.batch_id}_integrated_morphology" if integrate else f"{self.batch_id}_morphology"
+            tail = "" if integrate else f"_{self._image_number(members[0])}"
+            mid = "" if integrate else "_means"      # {batch_id}_morphology_{image number}.csv is the image's cell table
+            files = [stem + "_summary" + tail + ".csv", stem + mid + tail + ".csv"]
+            with open(os.path.join(self.result_dir, files[0]), "w") as f:
+                f.write(morphology.summary_csv(names, morphology.summary(types, t, feat)))
+            z = morphology.standardised_means(types, t, feat)
+            with open(os.path.join(self.result_dir, files[1]), "w") as f:
+                f.write(morphology.matrix_csv(names, z))
+            fig = self._write_table_figure(stem + mid + tail, z, -morphology.Z_LIMIT, morphology.Z_LIMIT, row_names=names, col_names=morphology.FEATURES)
+            files.append(fig["file"])
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            cells = len(table)
+            odd = int((feat["euler"] != 1).sum())
+            cut = int((feat["patch_coverage"] < 1.0).sum())
+            on_edge = int((feat["on_image_edge"] > 0).sum())
+            rec = {"file": files[0], "files": files, "image_files": image_files, "figure": {"file": fig["file"], "limit": morphology.Z_LIMIT, "rect": fig["rect"]},
+                   "n": cells, "T": t, "euler_not_one": odd, "patch_truncated": cut, "on_image_edge": on_edge, "kernel_ms": kernel_ms, "draw_ms": draw_ms}
+            self.morphology_stats.append(rec)
+            self.logger.log("Cell morphology {}: {} cells, {} cell types; {} labels with an Euler number other than 1, {} cells larger than their "
+                            "classifier window, {} on the image border; ops.mask_morphology with its copies {:.1f}, tables and drawing {:.1f} ms.".format(
+                                files[0], cells, t, odd, cut, on_edge, kernel_ms, draw_ms))
+        return None
+
     # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
     def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
         """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as

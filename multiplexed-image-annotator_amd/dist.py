@@ -90,7 +90,8 @@ def all_gather_planes(local: torch.Tensor, n_total: int, group=None) -> torch.Te
 
 def all_gather_rows(local: torch.Tensor, n_total: int, group=None, force_collective: bool = False) -> torch.Tensor:
     """Reassemble a (n_total, K) tensor from each rank's contiguous (n_local, K) shard (``shard_bounds`` layout).
-    Shards are padded to the largest shard so a single fixed-size all_gather (one RCCL call) is enough.
+    Shards are padded to the largest shard so a single fixed-size all_gather (one RCCL call) is enough.  A host tensor under "nccl" is staged
+    through the device and comes back on the host (the feature rows of Annotator.cell_morphology).
     ``force_collective`` issues the collective even in a group of one rank (the single-GPU RCCL test: same call, same buffers)."""
     import torch.distributed as dist
     rank, ws = world()
@@ -99,6 +100,8 @@ def all_gather_rows(local: torch.Tensor, n_total: int, group=None, force_collect
         return local
     if local.is_cuda and dist.get_backend(group) == "gloo":     # rehearsal / CPU-collective runs: stage through host memory
         return all_gather_rows(local.cpu(), n_total, group).to(local.device)
+    if not local.is_cuda and dist.get_backend(group) == "nccl":      # RCCL moves device buffers only: a host table goes through the device
+        return all_gather_rows(local.cuda(), n_total, group, force_collective).cpu()
     k = local.shape[1:]
     cap = max(shard_bounds(n_total, r, ws)[1] - shard_bounds(n_total, r, ws)[0] for r in range(ws))
     send = torch.zeros((cap,) + tuple(k), dtype=local.dtype, device=local.device)

@@ -500,6 +500,42 @@ def edge_perm_counts(src, dst, cell_type: np.ndarray, n_types: int, seed: int, i
     return out
 
 
+def mask_morphology_ws_bytes(h: int, w: int, n: int) -> int:
+    return int(lib().ribca_mask_morphology_ws_bytes(int(h), int(w), int(n)))
+
+
+def mask_morphology(mask: torch.Tensor, ids: np.ndarray, rect: Optional[np.ndarray] = None, ws: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+    """The morphology sums of an (H, W) int32 device mask over the cells ``ids`` (ascending mask labels, cell i = ids[i]; the label -> cell table
+    is built as ``contact_graph`` and ``colorize`` build it, label 0 never a cell).  Returns host arrays: ``sums`` (n, 16) int64 -- area, raw
+    moments, leaving pixel edges, perimeter classes, bit quads and the pixels inside the cell's row ``r0, r1, c0, c1`` of ``rect`` (n, 4) int32,
+    0 without one -- and ``bbox`` (n, 4) int32; include/ribca_hip.h states the columns, morphology.features turns them into the table."""
+    assert mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n = len(ids)
+    if n == 0:
+        return {"sums": np.zeros((0, 16), np.int64), "bbox": np.zeros((0, 4), np.int32)}
+    dev = mask.device
+    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
+    table[ids] = np.arange(n, dtype=np.int32)
+    table[0] = -1      # colorize paints labels > 0 only
+    tab_d = torch.from_numpy(table).to(dev)
+    rect_d = None
+    if rect is not None:
+        rect = np.ascontiguousarray(rect, dtype=np.int32)
+        if rect.shape != (n, 4):
+            raise ValueError(f"mask_morphology takes one rectangle r0, r1, c0, c1 per cell, got {rect.shape} for {n} cells")
+        rect_d = torch.from_numpy(rect).to(dev)
+    mask = mask.contiguous()
+    h, w = mask.shape
+    sums = torch.empty((n, 16), dtype=torch.int64, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if ws is None:
+        ws = _scratch(mask_morphology_ws_bytes(h, w, n), dev)
+    check(lib().ribca_mask_morphology(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, ptr(rect_d), ptr(sums), ptr(bbox), ptr(ws), ws.numel(),
+                                      stream_ptr()), "ribca_mask_morphology")
+    return {"sums": sums.cpu().numpy(), "bbox": bbox.cpu().numpy()}
+
+
 AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
 AUTOCORR_MAX_NEIGHBOURS = 31
 

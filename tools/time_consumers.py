@@ -16,7 +16,9 @@ permutations of the nearest-distance band counts in 16 bands of 30 px, inputs on
 of one type, and the numpy restatement of tests/nearest_numpy.py on the first 10 000 cells, scaled by n^2 (``--nearest``: this section alone); and
 the contact graph of the mask (csrc/contact.hip): the (n, 32) contact table at the reaches 1, 4 and 8 px, mask and label table on the device, then
 1000 label permutations over the directed edges of each at 12 cell types, and the numpy restatement of tests/contact_numpy.py on the top-left
-1024 x 1024 crop of the same mask, scaled by the area (``--contact``: this section alone)."""
+1024 x 1024 crop of the same mask, scaled by the area (``--contact``: this section alone); and the morphology sums of the mask
+(csrc/morphology.hip): the (n, 16) table and the boxes with the crop windows as rectangles, mask, label table and outputs on the device, and the
+numpy restatement of tests/morphology_numpy.py on the same crop, scaled by the area (``--morphology``: this section alone)."""
 import os
 import sys
 import time
@@ -172,6 +174,61 @@ def time_contact():
           f"{host_ms * perms / few / 1e3:.1f} s for {perms}; equal to the GPU counts: {same}")
 
 
+# ---- the morphology sums of the mask (csrc/morphology.hip): the (n, 16) table and the boxes, the crop windows of a 40-px patch as rectangles ----------
+def time_morphology():
+    """mask, label table, rectangles, outputs and workspace on the device before the clock starts: the entry point itself, median of five calls
+    after a warm-up; then the restatement on a crop, checked against the GPU on the same crop"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import morphology_numpy as MN
+    from multiplexed_image_annotator_amd import morphology
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    h, w = mask.shape
+    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
+    table[ids] = np.arange(n, dtype=np.int32)
+    tab_d = torch.from_numpy(table).to(dev)
+    rect = morphology.patch_rect(tab[:, :4], h, w, 40)
+    rect_d = torch.from_numpy(rect).to(dev)
+    sums = torch.empty((n, 16), dtype=torch.int64, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(ops.mask_morphology_ws_bytes(h, w, n), 1), dtype=torch.uint8, device=dev)
+
+    def call():
+        _lib.check(lib().ribca_mask_morphology(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, ptr(rect_d), ptr(sums), ptr(bbox), ptr(ws), ws.numel(),
+                                               stream_ptr()), "morphology")
+
+    call()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    got = sums.cpu().numpy()
+    feat = morphology.features(got, bbox.cpu().numpy())
+    same_boxes = np.array_equal(bbox.cpu().numpy(), tab[:, :4]) and np.array_equal(got[:, 0], tab[:, 6])
+    print(f"morphology sums (init + tiles): median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} of 5 for {n} cells, {h}x{w}; "
+          f"boxes and areas equal to the label table: {same_boxes}; Euler number other than 1: {int((feat['euler'] != 1).sum())} cells, larger than the "
+          f"40-px window: {int((feat['patch_coverage'] < 1.0).sum())}, on the image border: {int(feat['on_image_edge'].sum())}, mean contact fraction "
+          f"{float(np.nanmean(feat['contact_fraction'])):.4f}")
+    t0 = time.perf_counter()
+    morphology.features(got, bbox.cpu().numpy())
+    print(f"morphology.features on the host, {n} cells: {1e3 * (time.perf_counter() - t0):.0f} ms")
+    side = 1024
+    crop = np.ascontiguousarray(mask[:side, :side].cpu().numpy())
+    crop_rect = morphology.patch_rect(MN.sums_arrays(crop, table, n)[1], side, side, 40)
+    t0 = time.perf_counter()
+    want = MN.sums_arrays(crop, table, n, crop_rect)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    g = ops.mask_morphology(torch.from_numpy(crop).to(dev), ids, crop_rect)
+    same = np.array_equal(g["sums"], want[0]) and np.array_equal(g["bbox"], want[1])
+    print(f"numpy restatement, top-left {side}x{side} crop (host): {host_ms:.0f} ms -> {host_ms * (h * w) / (side * side) / 1e3:.1f} s scaled by area to "
+          f"{h}x{w}; equal to the GPU table of the same crop: {same}")
+
+
+if "--morphology" in sys.argv:      # this section alone
+    time_morphology()
+    sys.exit(0)
 if "--nearest" in sys.argv:      # this section alone
     time_nearest()
     sys.exit(0)
@@ -370,3 +427,6 @@ time_nearest()
 
 # ---- the contact graph of the mask: defined above as well -----------------------------------------------------------------------------------------
 time_contact()
+
+# ---- the morphology sums of the mask: defined above as well ----------------------------------------------------------------------------------------
+time_morphology()
