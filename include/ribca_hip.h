@@ -348,6 +348,26 @@ int64_t ribca_mask_morphology_ws_bytes(int32_t H, int32_t W, int32_t n);
 int ribca_mask_morphology(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, const int32_t* rect,
                           uint64_t* sums, int32_t* bbox, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- per-cell marker intensities over the cell's own pixels (csrc/intensities.hip) -------------------------------------
+ * image (C, H, W) fp32, mask (H, W) int32, ids (n) int32 and bbox (n, 4) int32 on the device; q_num (Q) int32 is a HOST array, read before
+ * the launch.  bbox holds rmin, rmax, cmin, cmax, all inclusive, in the form ribca_label_table writes; it is clipped to the image.  The
+ * pixel set S of cell i is the pixels of its clipped box with mask == ids[i], in row-major order; ids[i] <= 0 or an empty box give an empty S
+ * (a box that leaves out pixels of the label leaves them out of S).  With a = |S| and v_0 .. v_{a-1} a channel's values over S widened to fp64,
+ * all three outputs are OVERWRITTEN:
+ *     area  (n) int32          a
+ *     sums  (n, C, 2) fp64     sum, ssd.  Partial p_j, j = 0 .. 255, starts at 0.0 and adds v_j, v_{j+256}, v_{j+512}, ... in that order; then for
+ *                              s = 128, 64, ..., 1: p_j += p_{j+s} for j < s; sum = p_0 and m = sum / a.  ssd is the same tree over
+ *                              (v_j - m) * (v_j - m); every operation is rounded on its own (no fused multiply-add)
+ *     order (n, C, Q, 2) fp32  the values sorted by the total-order key of the fp32 bit pattern (all bits of a negative flipped, the sign bit of
+ *                              the rest set: -0.0 < +0.0, ties are bit-identical); for quantile k with h = (a - 1) q_num[k] in 64-bit integers,
+ *                              lo = h / q_den, hi = lo + (h % q_den != 0): order[i, c, k] = (x_(lo), x_(hi)), bit patterns preserved
+ * a = 0 gives sum = ssd = 0 and the quiet NaN 0x7FC00000 in order.  For finite inputs the outputs are a pure function of the arguments, the same
+ * for every launch geometry and every run (no floating-point atomics; the selection counts in integers); for non-finite values only order is
+ * specified.  1 <= C <= 64, 1 <= Q <= 8, 1 <= q_den, 0 <= q_num[k] <= q_den, 1 <= H, W <= 65535, H W < 2^31, 1 <= n <= 2^21; n == 0 returns 0 and
+ * touches nothing.  No workspace.  No loop of the kernel waits for another thread.  The entry point does not synchronise. */
+int ribca_cell_intensities(const float* image, int32_t C, int32_t H, int32_t W, const int32_t* mask, const int32_t* ids, const int32_t* bbox,
+                           int32_t n, const int32_t* q_num, int32_t Q, int32_t q_den, int32_t* area, double* sums, float* order, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

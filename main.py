@@ -14,7 +14,9 @@ distance of every cell to the nearest cell of each type and the cross-type G fun
 segmentation mask -- which cells lie within D pixels of each other -- with its edge, cell and type-pair tables and a degree map per image, and with
 ``--contact-perms P`` (P > 0) the z-scores of the type pairs against a P-permutation label null (Annotator.contact_analysis); ``--morphology`` the
 per-cell morphology table read off the mask -- area, axes, eccentricity, perimeter, Euler number, the share of the outline that faces other cells,
-the share of the cell inside its classifier window -- with its per-type summary and two maps per image (Annotator.cell_morphology).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+the share of the cell inside its classifier window -- with its per-type summary and two maps per image (Annotator.cell_morphology);
+``--intensities`` the per-cell marker intensities over each cell's own pixels -- mean, std, min, quartiles, max of every channel -- with the per-type
+summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -61,6 +63,8 @@ def parse_args(argv=None):
                     help='label permutations of the null of the contact type pairs; read only with --contact-distance > 0 (0 = no null)')
     ap.add_argument('--morphology', action='store_true',
                     help='per-cell morphology table from the mask (shape, border, Euler number, patch coverage), per-type summary and two maps per image')
+    ap.add_argument('--intensities', action='store_true',
+                    help="per-cell marker intensities over the cell's own mask pixels (mean, std, min, quartiles, max), per-type summary and one map per marker and image")
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument('--image-path', type=str)
     grp.add_argument('--batch-csv', type=str)
@@ -85,7 +89,8 @@ def _setup():
 
 
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
-              nearest_perms=0, morphology=False, contact_distance=0, contact_perms=0):
+              nearest_perms=0, morphology=False, intensities=False, contact_distance=0,
+              contact_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -122,6 +127,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
         annotator.contact_analysis(distance=contact_distance, n_perms=max(contact_perms, 0), integrate=True)
     if morphology:                                  # and what the cells themselves look like: the morphology table of the mask (any number of cells)
         annotator.cell_morphology(integrate=True)
+    if intensities:                                 # and what they express: the marker intensities over each cell's own pixels (any number of cells)
+        annotator.cell_intensities(integrate=True)
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
     annotator.cell_type_composition(integrate=True)
@@ -130,7 +137,7 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, morphology=False, contact_distance=0, contact_perms=0):
+        nearest_bands=0, nearest_perms=0, morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _setup()
@@ -146,7 +153,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
-              morphology=morphology, contact_distance=contact_distance, contact_perms=contact_perms)
+              morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -158,14 +165,15 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, morphology=False, contact_distance=0, contact_perms=0):
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, morphology=False, intensities=False, contact_distance=0,
+              contact_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
-              morphology=morphology, contact_distance=contact_distance, contact_perms=contact_perms)
+              morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
 
 
 def main(argv=None):
@@ -176,7 +184,7 @@ def main(argv=None):
                   cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms,
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
-                  contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology)
+                  contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

@@ -1215,6 +1215,126 @@ class Annotator(object):
                                 files[0], cells, t, odd, cut, on_edge, kernel_ms, draw_ms))
         return None
 
+    # ---- cell intensities: the marker columns of the single-cell table, over each cell's own pixels (steinbock's measure intensities) ------------
+    def cell_intensities(self, integrate=True, maps=True):
+        """The marker intensity table of every image: per cell and image channel the mean, population std, min, quartiles and max over the cell's
+        OWN pixels -- the pixels of its box whose mask value is its id -- from ops.cell_intensities (csrc/intensities.hip: fp64 sums in a fixed
+        order, exact order statistics) finished on the host in fp64 (intensities.features, which states every formula), on the scale of
+        ``preprocessor.intensity_full``.  That table stays what it is, the reference's soft-mask-weighted mean over every labelled pixel of the
+        crop window; this one is the table to export.  Per image it writes ``{batch_id}_intensities_{image number}.csv`` (intensities.cells_csv, one
+        line per cell in id order) and, with ``maps``, one ``{batch_id}_intensity_{marker}_{image number}.png`` per marker painted through
+        ops.colorize with viridis at int(clip(mean, 0, 1) * 255), background 0 (characters of the marker name outside [A-Za-z0-9] become ``_``).
+        Per group (the batch with ``integrate``, else every image), with stem = ``{batch_id}_integrated_intensities`` or ``{batch_id}_intensities``
+        and the image number at the end of each name: ``{stem}_summary.csv`` (intensities.summary_csv: n, mean and median of the per-cell means,
+        median of the per-cell medians per cell type and marker), ``{stem}.csv`` / ``.png`` (intensities.standardised_medians on +- 3; for a single
+        image ``{batch_id}_intensities_medians_{image number}``, since ``{batch_id}_intensities_{image number}.csv`` is its cell table) and, when
+        ``intensity_full`` exists for every member, ``{stem}_vs_window.csv`` (intensities.vs_window: how far the window table is from the exact
+        mask mean).  Keeps the per-cell means as ``self.intensity_mask``, one (n, C) array per local image, and records ``intensity_stats``, one
+        record per group written by this rank; its ``kernel_ms`` is the host's clock around ops.cell_intensities -- the kernel and the copy of
+        its outputs back -- (tools/time_consumers.py --intensities times the kernel alone).  Multi-rank runs as cell_morphology: cell-sharded,
+        rank 0 computes and writes; tile-per-rank, every rank does its own images, and the integrated group takes one all-reduce of the counts and
+        one all-gather of the rows, which rank 0 orders by (image number, cell id), so its files are a single-rank run's."""
+        import time
+        from PIL import Image
+        from . import intensities
+        self._check_annotated("No annotations")
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        self.intensity_stats = []
+        self.intensity_mask = []
+        if self.world_size > 1 and not self.tile_mode and self.rank != 0:
+            return None
+        n_local = len(self.annotations)
+        groups = [list(range(n_local))] if integrate else [[i] for i in range(n_local)]
+        lut = colors.viridis_table()
+        stats = intensities.statistic_names()
+        median = stats.index("median")
+        full = self.preprocessor.intensity_full
+        c_img = int(self.preprocessor.images_dev[0].shape[0]) if n_local else len(self.channel_parser.markers)
+        markers = [str(m) for m in self.channel_parser.markers]
+        markers = (markers + [f"channel {j}" for j in range(len(markers), c_img)])[:c_img]
+        width = 4 + 3 * c_img      # image number, cell id, cell type, area, then the means, the medians and the window table: a row of the exchange
+        for g, members in enumerate(groups):
+            rows, image_files, kernel_ms, draw_ms, missing = [np.zeros((0, width))], [], 0.0, 0.0, 0
+            for i in members:
+                ids = np.asarray(self.preprocessor.cell_ids[i], dtype=np.int64)
+                mask = self.preprocessor.masks_dev[i]
+                image = self.preprocessor.images_dev[i]
+                n = len(ids)
+                if int(image.shape[0]) != c_img:
+                    raise ValueError(f"image {self._image_number(i)} has {int(image.shape[0])} channels, the batch {c_img}")
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                area, sums, order = ops.cell_intensities(image, mask, self.preprocessor.cell_ids_dev[i], self.preprocessor.cell_bbox_dev[i],
+                                                         intensities.Q_NUM, intensities.Q_DEN)
+                kernel_ms += (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                feat = intensities.features(area, sums, order, intensities.Q_NUM, intensities.Q_DEN)
+                self.intensity_mask.append(feat[:, :, 0].copy())
+                number = self._image_number(i)
+                image_files.append(f"{self.batch_id}_intensities_{number}.csv")
+                with open(os.path.join(self.result_dir, image_files[-1]), "w") as f:
+                    f.write(intensities.cells_csv(ids, types, names, area, markers, stats, feat))
+                if maps:
+                    for c, marker in enumerate(markers):
+                        image_files.append(f"{self.batch_id}_intensity_{intensities.file_slug(marker)}_{number}.png")
+                        idx = intensities.colour_index(feat[:, c, 0])
+                        rgb = lut[idx].reshape(n, 3)
+                        painted = ops.colorize(mask, ids, rgb, rgb, idx)[0].cpu().numpy()
+                        Image.fromarray(painted).save(os.path.join(self.result_dir, image_files[-1]))
+                window = full[i] if i < len(full) else None
+                if n == 0:
+                    window = np.zeros((0, c_img))
+                elif window is None or np.asarray(window).shape != (n, c_img):
+                    window, missing = np.full((n, c_img), np.nan), missing + 1
+                rows.append(np.concatenate([np.full((n, 1), float(number)), ids.reshape(n, 1).astype(np.float64), types.reshape(n, 1).astype(np.float64),
+                                            area.reshape(n, 1).astype(np.float64), feat[:, :, 0], feat[:, :, median],
+                                            np.asarray(window, dtype=np.float64)], axis=1))
+                draw_ms += (time.perf_counter() - t0) * 1e3
+            table = np.concatenate(rows, axis=0)
+            if integrate and self.tile_mode:
+                counts = np.zeros(self.world_size + 1, dtype=np.float64)      # the rows of every rank, then the images without a window table
+                counts[self.rank], counts[-1] = len(table), missing
+                counts = dist.all_reduce_sum(torch.from_numpy(counts)).numpy().astype(np.int64)
+                missing, counts = int(counts[-1]), counts[:-1]
+                cap = int(counts.max())
+                send = np.zeros((cap, width), dtype=np.float64)
+                send[:len(table)] = table
+                gathered = dist.all_gather_rows(torch.from_numpy(send), cap * self.world_size).numpy() if cap else send      # equal shards of cap rows
+                table = np.concatenate([gathered[r * cap:r * cap + int(counts[r])] for r in range(self.world_size)], axis=0)
+                table = table[np.lexsort((table[:, 1], table[:, 0]))]      # by (image number, cell id): the order of a single-rank run
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            types = table[:, 2].astype(np.int64)
+            means, medians, window = table[:, 4:4 + c_img], table[:, 4 + c_img:4 + 2 * c_img], table[:, 4 + 2 * c_img:]
+            empty, streamed = int((table[:, 3] == 0).sum()), int((table[:, 3] > ops.INTENSITY_RESIDENT).sum())
+            stem = f"{self.batch_id}_integrated_intensities" if integrate else f"{self.batch_id}_intensities"
+            tail = "" if integrate else f"_{self._image_number(members[0])}"
+            mid = "" if integrate else "_medians"      # {batch_id}_intensities_{image number}.csv is the image's cell table
+            files = [stem + "_summary" + tail + ".csv", stem + mid + tail + ".csv"]
+            with open(os.path.join(self.result_dir, files[0]), "w") as f:
+                f.write(intensities.summary_csv(names, markers, intensities.type_summary(types, t, means, medians)))
+            z = intensities.standardised_medians(types, t, means)
+            with open(os.path.join(self.result_dir, files[1]), "w") as f:
+                f.write(intensities.matrix_csv(names, markers, z))
+            fig = self._write_table_figure(stem + mid + tail, z, -intensities.Z_LIMIT, intensities.Z_LIMIT, row_names=names, col_names=markers)
+            files.append(fig["file"])
+            if not missing:
+                files.append(stem + "_vs_window" + tail + ".csv")
+                with open(os.path.join(self.result_dir, files[-1]), "w") as f:
+                    f.write(intensities.vs_window_csv(markers, intensities.vs_window(means, window)))
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            cells = len(table)
+            rec = {"file": files[0], "files": files, "image_files": image_files, "figure": {"file": fig["file"], "limit": intensities.Z_LIMIT, "rect": fig["rect"]},
+                   "n": cells, "C": c_img, "T": t, "area_zero": empty, "streamed": streamed, "kernel_ms": kernel_ms, "draw_ms": draw_ms}
+            self.intensity_stats.append(rec)
+            self.logger.log("Cell intensities {}: {} cells, {} markers, {} cell types; {} cells without a pixel, {} above {} pixels (streaming form); "
+                            "ops.cell_intensities with its copies {:.1f}, tables and drawing {:.1f} ms.".format(
+                                files[0], cells, c_img, t, empty, streamed, ops.INTENSITY_RESIDENT, kernel_ms, draw_ms))
+        return None
+
     # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
     def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
         """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as

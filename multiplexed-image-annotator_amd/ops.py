@@ -536,6 +536,50 @@ def mask_morphology(mask: torch.Tensor, ids: np.ndarray, rect: Optional[np.ndarr
     return {"sums": sums.cpu().numpy(), "bbox": bbox.cpu().numpy()}
 
 
+INTENSITY_SMALL_BOX = 1024        # csrc/intensities.hip IN_SMALL_BOX: a clipped box of at most this many pixels is one wave's
+INTENSITY_RESIDENT = 4096         # csrc/intensities.hip IN_RESIDENT: in a larger box, a cell of more pixels takes the streaming form
+INTENSITY_MAX_CHANNELS = 64
+INTENSITY_MAX_QUANTILES = 8
+
+
+def cell_intensities(image: torch.Tensor, mask: torch.Tensor, ids, bbox, q_num: Sequence[int] = (0, 1, 2, 3, 4), q_den: int = 4,
+                     out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """Per cell and channel the exact sums and order statistics over the cell's own pixels: ``image`` (C, H, W) fp32 and ``mask`` (H, W) int32 on
+    the device, ``ids`` (n) the mask label of every cell and ``bbox`` (n, 4) its box ``rmin, rmax, cmin, cmax`` (inclusive; host arrays or
+    device tensors, e.g. ImageProcessor.cell_ids_dev / cell_bbox_dev).  Returns host arrays ``area`` (n) int32, ``sums`` (n, C, 2) fp64
+    ``[sum, ssd]`` and ``order`` (n, C, Q, 2) fp32, the order statistics that bracket the quantiles ``q_num[k] / q_den`` (include/ribca_hip.h
+    states the summation order and the ranks; intensities.features turns them into the table).  ``out``: device tensors to fill instead
+    (returned as they are, no copy back, no synchronise)."""
+    assert image.is_cuda and image.dtype == torch.float32 and image.dim() == 3
+    assert mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2 and tuple(mask.shape) == tuple(image.shape[1:])
+    dev = image.device
+    q = np.ascontiguousarray(np.asarray(q_num, dtype=np.int32).reshape(-1))
+    c, h, w = (int(v) for v in image.shape)
+    ids_d = ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1)))
+    bbox_d = bbox if torch.is_tensor(bbox) else torch.from_numpy(np.ascontiguousarray(np.asarray(bbox, dtype=np.int32).reshape(-1, 4)))
+    ids_d = ids_d.to(device=dev, dtype=torch.int32).contiguous()
+    bbox_d = bbox_d.to(device=dev, dtype=torch.int32).contiguous()
+    n = ids_d.numel()
+    if tuple(bbox_d.shape) != (n, 4):
+        raise ValueError(f"cell_intensities takes one box rmin, rmax, cmin, cmax per cell, got {tuple(bbox_d.shape)} for {n} cells")
+    if out is None:
+        area = torch.empty((n,), dtype=torch.int32, device=dev)
+        sums = torch.empty((n, c, 2), dtype=torch.float64, device=dev)
+        order = torch.empty((n, c, len(q), 2), dtype=torch.float32, device=dev)
+    else:
+        area, sums, order = out
+        assert area.is_contiguous() and sums.is_contiguous() and order.is_contiguous()
+        assert area.dtype == torch.int32 and sums.dtype == torch.float64 and order.dtype == torch.float32
+        assert area.numel() == n and sums.numel() == n * c * 2 and order.numel() == n * c * len(q) * 2
+    if n:
+        check(lib().ribca_cell_intensities(ptr(image.contiguous()), c, h, w, ptr(mask.contiguous()), ptr(ids_d), ptr(bbox_d), n,
+                                           q.ctypes.data_as(ctypes.c_void_p), len(q), int(q_den), ptr(area), ptr(sums), ptr(order), stream_ptr()),
+              "ribca_cell_intensities")
+    if out is not None:
+        return out
+    return area.cpu().numpy(), sums.cpu().numpy(), order.cpu().numpy()
+
+
 AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
 AUTOCORR_MAX_NEIGHBOURS = 31
 

@@ -18,7 +18,10 @@ the contact graph of the mask (csrc/contact.hip): the (n, 32) contact table at t
 1000 label permutations over the directed edges of each at 12 cell types, and the numpy restatement of tests/contact_numpy.py on the top-left
 1024 x 1024 crop of the same mask, scaled by the area (``--contact``: this section alone); and the morphology sums of the mask
 (csrc/morphology.hip): the (n, 16) table and the boxes with the crop windows as rectangles, mask, label table and outputs on the device, and the
-numpy restatement of tests/morphology_numpy.py on the same crop, scaled by the area (``--morphology``: this section alone)."""
+numpy restatement of tests/morphology_numpy.py on the same crop, scaled by the area (``--morphology``: this section alone); and the per-cell
+marker intensities (csrc/intensities.hip): the kernel alone on a 15-channel fp32 image of the same tile, device events, for the five quartile
+ranks and for the median alone, the host features, and the numpy restatement of tests/intensities_numpy.py on the same crop, scaled by the area
+(``--intensities``: this section alone)."""
 import os
 import sys
 import time
@@ -226,6 +229,67 @@ def time_morphology():
           f"{h}x{w}; equal to the GPU table of the same crop: {same}")
 
 
+# ---- the per-cell marker intensities (csrc/intensities.hip): sums and order statistics of 15 channels over every cell's own pixels ------------------
+HBM_BYTES_PER_S = 6.29e12      # the measured copy rate of the MI355X: the time to read the image once at it is the floor of this step
+
+
+def time_intensities():
+    """image, mask, ids, boxes and outputs on the device before the clock starts: the entry point itself between two device events, median of
+    five calls after a warm-up, for Q = 5 (min, quartiles, max) and Q = 1 (the median); then the host features and the restatement on a crop,
+    checked against the GPU on the same crop"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import intensities_numpy as IN
+    from multiplexed_image_annotator_amd import intensities
+    h, w = mask.shape
+    c = 15
+    _, raw = synth.make_mask_and_image(h, w, 100000, c, synth.SEED_BASE + 3, device=dev)
+    image = (raw.to(torch.float32) / 32767.5 - 1.0).contiguous()      # the normalised range, with the background's ties
+    del raw
+    ids_d = torch.from_numpy(np.asarray(ids, dtype=np.int32)).to(dev)
+    bbox_d = torch.from_numpy(np.ascontiguousarray(tab[:, :4], dtype=np.int32)).to(dev)
+    floor_ms = 1e3 * image.numel() * 4 / HBM_BYTES_PER_S
+    got = None
+    for q_num, q_den, what in ((intensities.Q_NUM, intensities.Q_DEN, "Q = 5 (min, quartiles, max)"), ((1,), 2, "Q = 1 (median)")):
+        out = (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n, c, 2), dtype=torch.float64, device=dev),
+               torch.empty((n, c, len(q_num), 2), dtype=torch.float32, device=dev))
+        ops.cell_intensities(image, mask, ids_d, bbox_d, q_num, q_den, out=out)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            ops.cell_intensities(image, mask, ids_d, bbox_d, q_num, q_den, out=out)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop))
+        area = out[0].cpu().numpy()
+        print(f"cell intensities, {what}: median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} of 5 (device events) for {n} cells, "
+              f"{c} channels, {h}x{w}; one read of the {image.numel() * 4 / 1e9:.2f} GB image at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: {floor_ms:.2f} ms; areas equal "
+              f"to the label table: {np.array_equal(area, tab[:, 6])}; mean area {area.mean():.0f}, max {area.max()}, above {ops.INTENSITY_RESIDENT} pixels: "
+              f"{int((area > ops.INTENSITY_RESIDENT).sum())}")
+        if got is None:
+            got = tuple(t.cpu().numpy() for t in out)
+    t0 = time.perf_counter()
+    intensities.features(*got)
+    print(f"intensities.features on the host, {n} cells x {c} channels: {1e3 * (time.perf_counter() - t0):.0f} ms")
+    side = 1024
+    crop_mask = np.ascontiguousarray(mask[:side, :side].cpu().numpy())
+    crop_image = np.ascontiguousarray(image[:, :side, :side].cpu().numpy())
+    crop_ids = np.unique(crop_mask[crop_mask > 0]).astype(np.int32)
+    crop_box = IN.boxes_of_all(crop_mask, crop_ids)
+    t0 = time.perf_counter()
+    want = IN.arrays(crop_image, crop_mask, crop_ids, crop_box)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    g = ops.cell_intensities(torch.from_numpy(crop_image).to(dev), torch.from_numpy(crop_mask).to(dev), crop_ids, crop_box)
+    same = np.array_equal(g[0], want[0]) and np.array_equal(g[1].view(np.int64), want[1].view(np.int64)) and np.array_equal(g[2].view(np.int32),
+                                                                                                                   want[2].view(np.int32))
+    print(f"numpy restatement, top-left {side}x{side} crop, {len(crop_ids)} cells (host): {host_ms:.0f} ms -> {host_ms * (h * w) / (side * side) / 1e3:.1f} s scaled by "
+          f"area to {h}x{w}; equal to the GPU outputs of the same crop, byte for byte: {same}")
+
+
+if "--intensities" in sys.argv:      # this section alone
+    time_intensities()
+    sys.exit(0)
 if "--morphology" in sys.argv:      # this section alone
     time_morphology()
     sys.exit(0)
@@ -430,3 +494,6 @@ time_contact()
 
 # ---- the morphology sums of the mask: defined above as well ----------------------------------------------------------------------------------------
 time_morphology()
+
+# ---- the per-cell marker intensities: defined above as well ----------------------------------------------------------------------------------------
+time_intensities()
