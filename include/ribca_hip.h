@@ -368,6 +368,21 @@ int ribca_mask_morphology(const int32_t* mask, int32_t H, int32_t W, const int32
 int ribca_cell_intensities(const float* image, int32_t C, int32_t H, int32_t W, const int32_t* mask, const int32_t* ids, const int32_t* bbox,
                            int32_t n, const int32_t* q_num, int32_t Q, int32_t q_den, int32_t* area, double* sums, float* order, void* stream);
 
+/* ---- growing the labels of a mask by D pixels (csrc/expand.hip) ----------------------------------------------------------
+ * mask (H, W) int32 row-major on the device, e.g. a nuclear segmentation; out (H, W) int32 and, unless NULL, dist2 (H, W) int32 are OVERWRITTEN.
+ * A pixel p is LABELLED when mask[p] > 0: out[p] = mask[p], dist2[p] = 0.  A pixel q with mask[q] <= 0 is GROWN when some labelled pixel lies
+ * within squared Euclidean distance D D of it: with m = the smallest squared distance from q to a labelled pixel, out[q] = the SMALLEST label value
+ * among the labelled pixels at squared distance exactly m, and dist2[q] = m.  A pixel that is neither gets out[q] = mask[q] -- zeros and
+ * negatives pass through -- and dist2[q] = -1.  Nothing outside the image is read.  This is skimage.segmentation.expand_labels(mask, D) but for
+ * the tie rule: scipy's distance transform gives a pixel with several nearest labels the one its scan meets first, a property of the algorithm;
+ * the smallest label is a property of the data, symmetric under flips and transposition.  Integer arithmetic, no atomics: a pure function of
+ * (mask, D), the same for every launch geometry and every run.  1 <= H, W, H W < 2^31, 1 <= D <= 32; labels are any positive int32.  mask, out and
+ * dist2 must not overlap.  ws: ribca_expand_labels_ws_bytes(H, W, D) bytes; 0 for arguments the entry point refuses.  The piece is RESERVED: 256
+ * bytes today, and the kernel neither reads nor writes it; a NULL or short workspace is refused all the same, as for every entry point that takes
+ * one.  No loop of the kernel waits for another thread.  The entry point does not synchronise. */
+int64_t ribca_expand_labels_ws_bytes(int32_t H, int32_t W, int32_t D);
+int ribca_expand_labels(const int32_t* mask, int32_t H, int32_t W, int32_t D, int32_t* out, int32_t* dist2, void* ws, int64_t ws_bytes, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

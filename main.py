@@ -16,7 +16,9 @@ segmentation mask -- which cells lie within D pixels of each other -- with its e
 per-cell morphology table read off the mask -- area, axes, eccentricity, perimeter, Euler number, the share of the outline that faces other cells,
 the share of the cell inside its classifier window -- with its per-type summary and two maps per image (Annotator.cell_morphology);
 ``--intensities`` the per-cell marker intensities over each cell's own pixels -- mean, std, min, quartiles, max of every channel -- with the per-type
-summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities); ``--expand-mask D`` (1 <= D <= 32) grows every label of the mask by D pixels on the GPU
+before anything reads it -- for masks that outline nuclei -- and writes the grown mask and a per-cell expansion table, and with ``--intensities``
+the intensity tables of the nucleus (core) and of the grown ring as well (Annotator(expand_mask=D)).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -65,6 +67,9 @@ def parse_args(argv=None):
                     help='per-cell morphology table from the mask (shape, border, Euler number, patch coverage), per-type summary and two maps per image')
     ap.add_argument('--intensities', action='store_true',
                     help="per-cell marker intensities over the cell's own mask pixels (mean, std, min, quartiles, max), per-type summary and one map per marker and image")
+    ap.add_argument('--expand-mask', type=int, default=0,
+                    help='grow every label of the mask by this many pixels (1 .. 32) on the GPU before anything reads it: for nuclear masks; writes the '
+                         'expanded mask and a per-cell expansion table, and with --intensities the core and ring tables (0 = use the mask as it is)')
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument('--image-path', type=str)
     grp.add_argument('--batch-csv', type=str)
@@ -74,6 +79,8 @@ def parse_args(argv=None):
         ap.error("--mask-path is required when using --image-path")
     if not 0 <= args.contact_distance <= 8:
         ap.error("--contact-distance takes 0 (off) or a reach of 1 .. 8 pixels")
+    if not 0 <= args.expand_mask <= 32:
+        ap.error("--expand-mask takes 0 (off) or a distance of 1 .. 32 pixels")
     return args
 
 
@@ -88,8 +95,14 @@ def _setup():
             dist.init_process_group(os.environ.get("RIBCA_DIST_BACKEND", "nccl"))
 
 
+def _check_expand_mask(expand_mask):
+    """the ValueError of ImageProcessor(expand_mask=...), before anything is built or read"""
+    from multiplexed_image_annotator_amd import ops
+    return ops.check_expand_distance(expand_mask, "expand_mask", allow_zero=True)
+
+
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
-              nearest_perms=0, morphology=False, intensities=False, contact_distance=0,
+              nearest_perms=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
               contact_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
@@ -129,6 +142,9 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
         annotator.cell_morphology(integrate=True)
     if intensities:                                 # and what they express: the marker intensities over each cell's own pixels (any number of cells)
         annotator.cell_intensities(integrate=True)
+        if expand_mask > 0:                         # the mask was grown from nuclei: the same table over the nucleus and over the grown ring
+            annotator.cell_intensities(integrate=True, maps=False, compartment="core")
+            annotator.cell_intensities(integrate=True, maps=False, compartment="ring")
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
     annotator.cell_type_composition(integrate=True)
@@ -137,9 +153,10 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, morphology=False, intensities=False, contact_distance=0, contact_perms=0):
+        nearest_bands=0, nearest_perms=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
+    _check_expand_mask(expand_mask)
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     path_ = os.path.join(main_dir, "images.csv")
@@ -151,9 +168,9 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         import torch.distributed as dist
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
-                          cell_size, cell_type_confidence, n_jobs=n_jobs)
+                          cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
-              morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
+              expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -165,15 +182,16 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, morphology=False, intensities=False, contact_distance=0,
-              contact_perms=0):
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, expand_mask=0, morphology=False, intensities=False,
+              contact_distance=0, contact_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
+    _check_expand_mask(expand_mask)
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
-                          confidence, cell_size, cell_type_confidence, n_jobs=n_jobs)
+                          confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
-              morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
+              expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
 
 
 def main(argv=None):
@@ -184,7 +202,8 @@ def main(argv=None):
                   cell_type_confidence=args.cell_type_confidence, n_jobs=args.n_jobs, enrichment_perms=args.enrichment_perms,
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
-                  contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities)
+                  contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities,
+                  expand_mask=args.expand_mask)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

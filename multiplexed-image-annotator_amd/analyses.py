@@ -674,7 +674,7 @@ class Analyses(object):
                                 files[0], cells, t, odd, cut, on_edge, kernel_ms, draw_ms))
 
     # ---- cell intensities: the marker columns of the single-cell table, over each cell's own pixels (steinbock's measure intensities) ------------
-    def cell_intensities(self, integrate=True, maps=True):
+    def cell_intensities(self, integrate=True, maps=True, compartment="cell"):
         """The marker intensity table of every image: per cell and image channel the mean, population std, min, quartiles and max over the cell's
         OWN pixels -- the pixels of its box whose mask value is its id -- from ops.cell_intensities (csrc/intensities.hip: fp64 sums in a fixed
         order, exact order statistics) finished on the host in fp64 (intensities.features, which states every formula), on the scale of
@@ -689,14 +689,26 @@ class Analyses(object):
         ``intensity_full`` exists for every member, ``{stem}_vs_window.csv`` (intensities.vs_window: how far the window table is from the exact
         mask mean).  Keeps the per-cell means as ``self.intensity_mask``, one (n, C) array per local image, and records ``intensity_stats``, one
         record per group written by this rank; its ``kernel_ms`` is the host's clock around ops.cell_intensities -- the kernel and the copy of
-        its outputs back -- (tools/time_consumers.py --intensities times the kernel alone).  Multi-rank runs as cell_morphology."""
+        its outputs back -- (tools/time_consumers.py --intensities times the kernel alone).  Multi-rank runs as cell_morphology.
+        ``compartment``: ``"cell"`` is all of the above.  In a run with ``expand_mask`` > 0, where the mask was grown from nuclei, ``"core"``
+        measures over the mask as read (``preprocessor.masks_core_dev`` with the boxes of its own label table) and ``"ring"`` over the grown
+        mask with the core's pixels set to 0 and the grown boxes -- what the expansion added: cytoplasm and membrane; a cell whose ring is
+        empty is an empty cell of the table (area 0).  Both put ``_core`` / ``_ring`` after ``intensities`` / ``intensity`` in every file
+        name, write no ``_vs_window.csv``, leave ``intensity_mask`` alone and keep their means as ``self.intensity_core`` /
+        ``self.intensity_ring``; without an expansion they raise ValueError.  Every record of ``intensity_stats`` names its ``compartment``."""
         import time
         from . import intensities
         self._check_annotated("No annotations")
+        if compartment not in ("cell", "core", "ring"):
+            raise ValueError(f"compartment must be 'cell', 'core' or 'ring', got {compartment!r}")
+        if compartment != "cell" and not getattr(self.preprocessor, "expand_mask", 0) > 0:
+            raise ValueError(f"compartment {compartment!r} needs a run with expand_mask > 0: without an expansion the mask has one compartment")
         t = len(self.cell_types)
         names = [str(c) for c in self.cell_types]
         self.intensity_stats = []
-        self.intensity_mask = []
+        sfx = "" if compartment == "cell" else "_" + compartment
+        kept = []      # the per-cell means of this compartment, one (n, C) array per local image
+        setattr(self, "intensity_mask" if compartment == "cell" else "intensity_" + compartment, kept)
         if not self._computes_here():
             return None
         n_local = len(self.annotations)
@@ -711,7 +723,12 @@ class Analyses(object):
             rows, image_files, kernel_ms, draw_ms, missing = [np.zeros((0, width))], [], 0.0, 0.0, 0
             for i in members:
                 ids = np.asarray(self.preprocessor.cell_ids[i], dtype=np.int64)
-                mask = self.preprocessor.masks_dev[i]
+                mask, boxes = self.preprocessor.masks_dev[i], self.preprocessor.cell_bbox_dev[i]
+                if compartment == "core":
+                    mask, boxes = self.preprocessor.masks_core_dev[i], self.preprocessor.core_bbox_dev[i]
+                elif compartment == "ring":
+                    core = self.preprocessor.masks_core_dev[i]
+                    mask = torch.where(core > 0, torch.zeros_like(mask), mask)
                 image = self.preprocessor.images_dev[i]
                 n = len(ids)
                 if int(image.shape[0]) != c_img:
@@ -719,18 +736,17 @@ class Analyses(object):
                 types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                area, sums, order = ops.cell_intensities(image, mask, self.preprocessor.cell_ids_dev[i], self.preprocessor.cell_bbox_dev[i],
-                                                         intensities.Q_NUM, intensities.Q_DEN)
+                area, sums, order = ops.cell_intensities(image, mask, self.preprocessor.cell_ids_dev[i], boxes, intensities.Q_NUM, intensities.Q_DEN)
                 kernel_ms += (time.perf_counter() - t0) * 1e3
                 t0 = time.perf_counter()
                 feat = intensities.features(area, sums, order, intensities.Q_NUM, intensities.Q_DEN)
-                self.intensity_mask.append(feat[:, :, 0].copy())
+                kept.append(feat[:, :, 0].copy())
                 number = self._image_number(i)
-                image_files.append(f"{self.batch_id}_intensities_{number}.csv")
+                image_files.append(f"{self.batch_id}_intensities{sfx}_{number}.csv")
                 self._write_text(image_files[-1], intensities.cells_csv(ids, types, names, area, markers, stats, feat))
                 if maps:
                     for c, marker in enumerate(markers):
-                        image_files.append(f"{self.batch_id}_intensity_{intensities.file_slug(marker)}_{number}.png")
+                        image_files.append(f"{self.batch_id}_intensity{sfx}_{intensities.file_slug(marker)}_{number}.png")
                         idx = intensities.colour_index(feat[:, c, 0])
                         self._paint_map(i, lut[idx], idx, image_files[-1])
                 window = full[i] if i < len(full) else None
@@ -751,7 +767,7 @@ class Analyses(object):
             types = table[:, 2].astype(np.int64)
             means, medians, window = table[:, 4:4 + c_img], table[:, 4 + c_img:4 + 2 * c_img], table[:, 4 + 2 * c_img:]
             empty, streamed = int((table[:, 3] == 0).sum()), int((table[:, 3] > ops.INTENSITY_RESIDENT).sum())
-            stem, tail = self._group_stem("intensities", integrate, members)
+            stem, tail = self._group_stem("intensities" + sfx, integrate, members)
             mid = "" if integrate else "_medians"      # {batch_id}_intensities_{image number}.csv is the image's cell table
             files = [stem + "_summary" + tail + ".csv", stem + mid + tail + ".csv"]
             self._write_text(files[0], intensities.summary_csv(names, markers, intensities.type_summary(types, t, means, medians)))
@@ -759,13 +775,13 @@ class Analyses(object):
             self._write_text(files[1], intensities.matrix_csv(names, markers, z))
             fig = self._write_table_figure(stem + mid + tail, z, -intensities.Z_LIMIT, intensities.Z_LIMIT, row_names=names, col_names=markers)
             files.append(fig["file"])
-            if not missing:
+            if not missing and compartment == "cell":
                 files.append(stem + "_vs_window" + tail + ".csv")
                 self._write_text(files[-1], intensities.vs_window_csv(markers, intensities.vs_window(means, window)))
             draw_ms += (time.perf_counter() - t0) * 1e3
             cells = len(table)
             rec = {"file": files[0], "files": files, "image_files": image_files, "figure": {"file": fig["file"], "limit": intensities.Z_LIMIT, "rect": fig["rect"]},
-                   "n": cells, "C": c_img, "T": t, "area_zero": empty, "streamed": streamed, "kernel_ms": kernel_ms, "draw_ms": draw_ms}
+                   "n": cells, "C": c_img, "T": t, "compartment": compartment, "area_zero": empty, "streamed": streamed, "kernel_ms": kernel_ms, "draw_ms": draw_ms}
             self.intensity_stats.append(rec)
             self.logger.log("Cell intensities {}: {} cells, {} markers, {} cell types; {} cells without a pixel, {} above {} pixels (streaming form); "
                             "ops.cell_intensities with its copies {:.1f}, tables and drawing {:.1f} ms.".format(

@@ -103,7 +103,7 @@ def _load_state_dict(path: str) -> Dict[str, torch.Tensor]:
 
 class Annotator(Analyses):
     def __init__(self, marker_list_path, image_path, device, main_dir='./', batch_id='', strict=True, infer=True, min_cells=-1,
-                 normalize=True, blur=False, amax=1, confidence=0.25, cell_size=30, cell_type_confidence=None, n_jobs=0):
+                 normalize=True, blur=False, amax=1, confidence=0.25, cell_size=30, cell_type_confidence=None, n_jobs=0, expand_mask=0):
         tile_env = tile_mode_env(min_cells)      # refuses RIBCA_TILE_MODE=1 with min_cells > 0 before any file is read
         self.device = device
         self.cell_types = ["B cell", "CD4 T cell", "CD8 T cell", "Dendritic cell", "Regulatory T cell", "Granulocyte cell", "Mast cell",
@@ -123,7 +123,9 @@ class Annotator(Analyses):
         self.channel_parser = MarkerParser(strict=strict, logger=self.logger)
         self.channel_parser.parse(marker_list_path)
         self.preprocessor = ImageProcessor(image_path, self.channel_parser, log_dir, device, batch_id, infer, normalize, blur, amax,
-                                           cell_size, self.logger, n_jobs=n_jobs)
+                                           cell_size, self.logger, n_jobs=n_jobs, expand_mask=expand_mask)
+        self.expand_mask = self.preprocessor.expand_mask      # validated there: 0, or the pixels every label of the mask is grown by
+        self.expansion_stats: List[Dict[str, float]] = []     # per local image of an expanded run: n, D, pixels_grown, cells_unchanged, expand_ms
         # multi-rank runs: whole images per rank when the batch CSV has at least one per rank (reference main.py:39-52 batch_run; BASELINE
         # config 5: replicas only, nothing exchanged, every rank writes the CSVs of its own images under their batch-wide numbers), cells of
         # every image otherwise (contiguous shards, one all-gather per image, rank 0 writes)
@@ -228,12 +230,40 @@ class Annotator(Analyses):
             self._n_images = len(self.preprocessor.image_ids)      # every per-image list below is indexed by LOCAL position
             self.logger.log("rank {} of {}: tile-per-rank mode, images {} of {}".format(rank, ws, self.preprocessor.image_ids,
                                                                                         self.preprocessor._n_images))
+            self._record_expansion()
             return
         if ws > 1 and os.environ.get("RIBCA_NORM_SHARD") == "1":
             self.preprocessor.norm_shard = (rank, ws)
         self.preprocessor.transform(shard_fn=(lambda n: dist.shard_bounds(n, rank, ws)) if ws > 1 else None,
                                     gather_fn=(lambda t, n: dist.all_gather_rows(t, n)) if ws > 1 else None)
         self._n_images = self.preprocessor._n_images
+        self._record_expansion()
+
+    def _record_expansion(self):
+        """With expand_mask = D > 0 the mask every stage reads is the mask of the batch CSV with each label grown by D pixels
+        (ImageProcessor._mask_to_device, ops.expand_labels, csrc/expand.hip; the mask as read stays in ``preprocessor.masks_core_dev``).  Per
+        local image this writes ``{batch_id}_expanded_mask_{image number}.npy`` (int32) and ``{batch_id}_expansion_{image number}.csv``
+        (expand.cells_csv: id, area_core, area_cell, grown and the box of the grown cell, one line per cell in id order, the areas from the two
+        label tables) and records ``expansion_stats``; its ``expand_ms`` is the host's clock around ops.expand_labels, synchronised
+        (tools/time_consumers.py --expand times the kernel alone).  Multi-rank runs: tile-per-rank ranks expand and write their own images;
+        cell-sharded ranks each expand the whole mask -- integers, the same on every rank, no collective -- and rank 0 writes."""
+        from . import expand
+        self.expansion_stats = []
+        pre = self.preprocessor
+        if self.expand_mask == 0:
+            return
+        for i in range(len(pre.masks)):
+            table = expand.rows(pre.cell_ids[i], pre.core_tables[i], pre.cell_tables[i])
+            rec = expand.stats(table, self.expand_mask, pre.expand_ms[i])
+            number = self._image_number(i)
+            rec["files"] = [f"{self.batch_id}_expanded_mask_{number}.npy", f"{self.batch_id}_expansion_{number}.csv"]
+            self.expansion_stats.append(rec)
+            if self._writes_files():
+                np.save(os.path.join(self.result_dir, rec["files"][0]), np.ascontiguousarray(pre.masks[i], dtype=np.int32))
+                with open(os.path.join(self.result_dir, rec["files"][1]), "w") as f:
+                    f.write(expand.cells_csv(table))
+            self.logger.log("Mask expansion {}: {} cells grown by up to {} pixels, {} pixels added, {} cells unchanged; ops.expand_labels {:.1f} ms.".format(
+                rec["files"][1], rec["n"], rec["D"], rec["pixels_grown"], rec["cells_unchanged"], rec["expand_ms"]))
 
     def clear(self):
         self.immune_base_pred, self.immune_extended_pred, self.immune_full_pred = [], [], []

@@ -536,7 +536,43 @@ def mask_morphology(mask: torch.Tensor, ids: np.ndarray, rect: Optional[np.ndarr
     return {"sums": sums.cpu().numpy(), "bbox": bbox.cpu().numpy()}
 
 
-INTENSITY_SMALL_BOX = 1024        # csrc/intensities.hip IN_SMALL_BOX: a clipped box of at most this many pixels is one wave's
+EXPAND_MAX_DISTANCE = 32          # csrc/expand.hip EX_D_MAX: the largest halo of a pixel tile
+EXPAND_TILE = 32                  # csrc/expand.hip EX_TILE
+
+
+def expand_labels_ws_bytes(h: int, w: int, distance: int) -> int:
+    return int(lib().ribca_expand_labels_ws_bytes(int(h), int(w), int(distance)))
+
+
+def check_expand_distance(distance, what: str = "distance", allow_zero: bool = False) -> int:
+    """``distance`` as an int, ValueError unless it is an integer (no bool) in 1 .. EXPAND_MAX_DISTANCE, or 0 where that means "do not expand" """
+    low = 0 if allow_zero else 1
+    if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)) or not low <= int(distance) <= EXPAND_MAX_DISTANCE:
+        raise ValueError(f"{what} must be an integer from {low} to {EXPAND_MAX_DISTANCE} pixels, got {distance!r}")
+    return int(distance)
+
+
+def expand_labels(mask: torch.Tensor, distance: int, want_dist2: bool = False, ws: Optional[torch.Tensor] = None):
+    """Grows the labels of an (H, W) int32 device mask by ``distance`` pixels, what skimage.segmentation.expand_labels does: a pixel <= 0 within
+    Euclidean distance ``distance`` of a labelled pixel (> 0) takes the label of the nearest one -- the smallest label among those at exactly the
+    smallest squared distance, not the one a scan meets first -- and every other pixel keeps its value.  Returns the grown mask, a new device
+    tensor, and with ``want_dist2`` also the (H, W) int32 squared distance to that pixel: 0 on a labelled pixel, -1 where nothing was in reach
+    (include/ribca_hip.h states the contract).  Does not synchronise."""
+    if not torch.is_tensor(mask) or mask.dtype != torch.int32 or mask.dim() != 2 or not mask.is_cuda:
+        raise ValueError("expand_labels takes an (H, W) int32 device mask")
+    d = check_expand_distance(distance)
+    mask = mask.contiguous()
+    h, w = mask.shape
+    dev = mask.device
+    out = torch.empty_like(mask)
+    dist2 = torch.empty_like(mask) if want_dist2 else None
+    if ws is None:
+        ws = _scratch(expand_labels_ws_bytes(h, w, d), dev)
+    check(lib().ribca_expand_labels(ptr(mask), h, w, d, ptr(out), ptr(dist2), ptr(ws), ws.numel(), stream_ptr()), "ribca_expand_labels")
+    return (out, dist2) if want_dist2 else out
+
+
+INTENSITY_SMALL_BOX = 1024       # csrc/intensities.hip IN_SMALL_BOX: a clipped box of at most this many pixels is one wave's
 INTENSITY_RESIDENT = 4096         # csrc/intensities.hip IN_RESIDENT: in a larger box, a cell of more pixels takes the streaming form
 INTENSITY_MAX_CHANNELS = 64
 INTENSITY_MAX_QUANTILES = 8

@@ -356,8 +356,11 @@ class LazyCellPositions(Mapping):
 
 class ImageProcessor(object):
     def __init__(self, csv_path, parser, main_path, device, batch_id='', infer=True, normalization=True, blur=0, amax=100, cell_size=30,
-                 logger=None, n_jobs=0) -> None:
+                 logger=None, n_jobs=0, expand_mask=0) -> None:
         import pandas as pd
+        # 0: the mask outlines whole cells and is used as read.  D in 1 .. 32: the mask outlines nuclei and every label is grown by D pixels on
+        # the device before anything reads it (ops.expand_labels; skimage's expand_labels, the "cell expansion" of steinbock, MCMICRO and QuPath)
+        self.expand_mask = ops.check_expand_distance(expand_mask, "expand_mask", allow_zero=True)
         table = pd.read_csv(csv_path)
         self.image_paths = table['image_path']
         self.mask_paths = table['mask_path']
@@ -397,6 +400,12 @@ class ImageProcessor(object):
         self.patches: List[Optional[torch.Tensor]] = []     # (n_local, C_img, 40, 40) fp32 per image, this rank's cells
         self.cell_ids_dev: List[torch.Tensor] = []          # per image: ascending cell ids int32 [n] / boxes int32 [n, 4] on the device
         self.cell_bbox_dev: List[torch.Tensor] = []
+        # the mask as read -- the nuclei of an expanded run -- with its label table and boxes, per image; with expand_mask = 0 these are the
+        # SAME objects as masks_dev / cell_tables / cell_bbox_dev hold, not copies.  expand_ms: the host clock around ops.expand_labels
+        self.masks_core_dev: List[torch.Tensor] = []
+        self.core_tables: List[np.ndarray] = []
+        self.core_bbox_dev: List[torch.Tensor] = []
+        self.expand_ms: List[float] = []
         # multi-rank runs (set by Annotator.preprocess): image_ids[j] = row of the batch CSV that local position j holds (tile-per-rank mode
         # keeps only this rank's images; every per-image list above is indexed by local position); norm_shard = (rank, world_size) when the
         # whole-image normalisation is split by channel with one all-gather of the planes (cell-sharded mode, RIBCA_NORM_SHARD=1)
@@ -425,9 +434,24 @@ class ImageProcessor(object):
             local = torch.empty((0,) + tuple(img.shape[1:]), dtype=torch.float32, device=_lib.require_gpu())
         return dist.all_gather_planes(local, c)
 
+    def _mask_to_device(self, mask: np.ndarray):
+        """THE upload of a mask: every path that puts a mask on the device goes through here, so that none sees the mask as read when the run
+        expands it.  Returns (the mask every stage uses, on the device; the mask as read, on the device; the host copy of the first; the
+        milliseconds of the expansion).  With expand_mask = 0 the first two are one tensor and the host copy is ``mask`` itself."""
+        import time
+        core_d = torch.from_numpy(mask).to(_lib.require_gpu())
+        if self.expand_mask == 0:
+            return core_d, core_d, mask, 0.0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        grown_d = ops.expand_labels(core_d, self.expand_mask)
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        return grown_d, core_d, grown_d.cpu().numpy(), ms
+
     def _cell_pos_dict(self, mask, n_jobs=0) -> LazyCellPositions:
-        mask_np = np.asarray(mask).astype(np.int32)
-        ids, table = ops.label_table(torch.from_numpy(mask_np).to(_lib.require_gpu()))
+        mask_d, _, mask_np, _ = self._mask_to_device(np.asarray(mask).astype(np.int32))
+        ids, table = ops.label_table(mask_d)
         return LazyCellPositions(mask_np, ids, table)
 
     def _move_image_range(self, image: torch.Tensor):
@@ -462,9 +486,18 @@ class ImageProcessor(object):
                 img_d = self._normalize(image, blur=self.blur, amax=self.amax)
             else:
                 img_d = torch.from_numpy(np.ascontiguousarray(image).astype(np.float32)).to(dev)
+            mask_d, core_d, mask, expand_ms = self._mask_to_device(mask)      # from here on `mask` is the mask every stage uses
             self.masks.append(mask)
-            mask_d = torch.from_numpy(mask).to(dev)
             ids, table, ids_d, bbox_d = ops.label_table(mask_d, with_device=True)
+            if core_d is mask_d:
+                core_table, core_bbox_d = table, bbox_d
+            else:
+                core_ids, core_table, _, core_bbox_d = ops.label_table(core_d, with_device=True)
+                assert np.array_equal(core_ids, ids), "expansion makes and removes no label"
+            self.masks_core_dev.append(core_d)
+            self.core_tables.append(core_table)
+            self.core_bbox_dev.append(core_bbox_d)
+            self.expand_ms.append(expand_ms)
             self.cell_ids_dev.append(ids_d)
             self.cell_bbox_dev.append(bbox_d)
             self.cell_pos_dict.append(LazyCellPositions(mask, ids, table))

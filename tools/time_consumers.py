@@ -21,7 +21,9 @@ the contact graph of the mask (csrc/contact.hip): the (n, 32) contact table at t
 numpy restatement of tests/morphology_numpy.py on the same crop, scaled by the area (``--morphology``: this section alone); and the per-cell
 marker intensities (csrc/intensities.hip): the kernel alone on a 15-channel fp32 image of the same tile, device events, for the five quartile
 ranks and for the median alone, the host features, and the numpy restatement of tests/intensities_numpy.py on the same crop, scaled by the area
-(``--intensities``: this section alone)."""
+(``--intensities``: this section alone); and the expansion of the mask's labels (csrc/expand.hip): the kernel alone at D = 2, 8 and 32, device
+events, mask, outputs and workspace on the device, and as the host yardstick scipy's distance_transform_edt(return_indices=True) on the same mask,
+whose composition at D = 8 is compared with the kernel's output (``--expand``: this section alone)."""
 import os
 import sys
 import time
@@ -287,6 +289,58 @@ def time_intensities():
           f"area to {h}x{w}; equal to the GPU outputs of the same crop, byte for byte: {same}")
 
 
+# ---- growing the labels of the mask (csrc/expand.hip): every background pixel within D pixels of a cell takes the nearest cell's label --------------
+def time_expand():
+    """mask, outputs and workspace on the device before the clock starts: the entry point itself between two device events, median of five calls
+    after a warm-up, with and without the squared distances; then scipy's exact Euclidean distance transform of the same mask on the host, which
+    gives every distance at once, and the comparison of its composition with the kernel at D = 8 (labels may differ on tie pixels only)"""
+    from scipy import ndimage
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    h, w = mask.shape
+    background = int((mask <= 0).sum())
+    out = torch.empty_like(mask)
+    dist2 = torch.empty_like(mask)
+    kept = {}
+    for d in (2, 8, 32):
+        ws = torch.empty(max(ops.expand_labels_ws_bytes(h, w, d), 1), dtype=torch.uint8, device=dev)
+        for what, d2 in (("labels and squared distances", dist2), ("labels alone", None)):
+            def call():
+                _lib.check(lib().ribca_expand_labels(ptr(mask), h, w, d, ptr(out), ptr(d2), ptr(ws), ws.numel(), stream_ptr()), "expand")
+
+            call()
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(5):
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                call()
+                stop.record()
+                torch.cuda.synchronize()
+                times.append(start.elapsed_time(stop))
+            grown = int(((out > 0) & (mask <= 0)).sum())
+            print(f"expand labels, D = {d}, {what}: median {sorted(times)[2]:.3f} ms, min {min(times):.3f}, max {max(times):.3f} of 5 (device events) for {n} "
+                  f"cells, {h}x{w}; {grown} of {background} background pixels grown; read + write of {(2 if d2 is None else 3) * h * w * 4 / 1e9:.2f} GB at "
+                  f"{HBM_BYTES_PER_S / 1e12:.2f} TB/s: {1e3 * (2 if d2 is None else 3) * h * w * 4 / HBM_BYTES_PER_S:.3f} ms")
+        if d == 8:
+            _lib.check(lib().ribca_expand_labels(ptr(mask), h, w, d, ptr(out), ptr(dist2), ptr(ws), ws.numel(), stream_ptr()), "expand")
+            kept = {"out": out.cpu().numpy(), "dist2": dist2.cpu().numpy()}
+    host = mask.cpu().numpy()
+    t0 = time.perf_counter()
+    dist, idx = ndimage.distance_transform_edt(host <= 0, return_indices=True)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    grown = (host <= 0) & (dist <= 8)
+    ref = host.copy()
+    ref[grown] = host[idx[0][grown], idx[1][grown]]
+    same_support = np.array_equal((kept["out"] > 0) & (host <= 0), grown)
+    same_dist = np.array_equal(kept["dist2"][grown], np.rint(dist[grown] ** 2).astype(np.int64))
+    differ = int((kept["out"] != ref).sum())
+    print(f"scipy distance_transform_edt(return_indices=True), {h}x{w} (host): {host_ms:.0f} ms; at D = 8 the grown pixels are the kernel's: {same_support}, "
+          f"the squared distances equal: {same_dist}, labels that differ (tie pixels, scan order against smallest label): {differ} of {int(grown.sum())}")
+
+
+if "--expand" in sys.argv:      # this section alone
+    time_expand()
+    sys.exit(0)
 if "--intensities" in sys.argv:      # this section alone
     time_intensities()
     sys.exit(0)
@@ -497,3 +551,6 @@ time_morphology()
 
 # ---- the per-cell marker intensities: defined above as well ----------------------------------------------------------------------------------------
 time_intensities()
+
+# ---- growing the labels of the mask: defined above as well ------------------------------------------------------------------------------------------
+time_expand()
