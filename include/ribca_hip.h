@@ -383,6 +383,25 @@ int ribca_cell_intensities(const float* image, int32_t C, int32_t H, int32_t W, 
 int64_t ribca_expand_labels_ws_bytes(int32_t H, int32_t W, int32_t D);
 int ribca_expand_labels(const int32_t* mask, int32_t H, int32_t W, int32_t D, int32_t* out, int32_t* dist2, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- connected components of a mask and relabelling by component (csrc/components.hip) ------------------------------------
+ * mask (H, W) int32 row-major on the device, read only; root (H, W) int32 and stats (H W, 4) int32 are OVERWRITTEN, every byte of them.
+ * CLASSES: a pixel with value v > 0 belongs to class v; all pixels <= 0 form the single class "background" (negative values are background, as for
+ * ribca_expand_labels).  COMPONENTS: foreground pixels of one class connect at 8-connectivity, background pixels at 4-connectivity -- the pairing
+ * behind the Euler number of morphology.py, so "one component, no hole" here is euler == 1 there; pixels of different classes never connect.
+ * root[p] = the raster index r W + c of the FIRST pixel of p's component, the smallest index in it: a partition of the whole image, determined
+ * by the mask alone, whatever the launch geometry or the order in which threads arrive.  stats row p is meaningful where root[p] == p and 0
+ * everywhere else: column 0 the area of the component; column 1 is 1 when a pixel of it lies on the image border (row 0 or H - 1, column 0 or
+ * W - 1), else 0; columns 2 and 3 are lo and hi, the smallest and the largest label > 0 among the pixels that are 4-adjacent to a pixel of the
+ * component and of another class, 0 and 0 when there is none.  Integer arithmetic only.  1 <= H, W, H W < 2^31; labels are any int32.  mask,
+ * root, stats and ws must not overlap.  ws: ribca_mask_components_ws_bytes(H, W) bytes; 0 for arguments the entry point refuses.  The piece is
+ * RESERVED: 256 bytes today, and the kernels neither read nor write it; a NULL or short workspace is refused all the same.  No loop of the
+ * kernels waits for another thread.  The entry point does not synchronise.
+ * ribca_mask_relabel: out[p] = new_label[root[p]] for the H W pixels; root as above (a value outside [0, H W) reads nothing and gives 0),
+ * new_label (H W) int32 indexed by raster index, out (H, W) int32 OVERWRITTEN; out must not overlap root or new_label.  Same limits on H, W. */
+int64_t ribca_mask_components_ws_bytes(int32_t H, int32_t W);
+int ribca_mask_components(const int32_t* mask, int32_t H, int32_t W, int32_t* root, int32_t* stats, void* ws, int64_t ws_bytes, void* stream);
+int ribca_mask_relabel(const int32_t* root, const int32_t* new_label, int32_t H, int32_t W, int32_t* out, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

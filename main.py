@@ -18,7 +18,9 @@ the share of the cell inside its classifier window -- with its per-type summary 
 ``--intensities`` the per-cell marker intensities over each cell's own pixels -- mean, std, min, quartiles, max of every channel -- with the per-type
 summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities); ``--expand-mask D`` (1 <= D <= 32) grows every label of the mask by D pixels on the GPU
 before anything reads it -- for masks that outline nuclei -- and writes the grown mask and a per-cell expansion table, and with ``--intensities``
-the intensity tables of the nucleus (core) and of the grown ring as well (Annotator(expand_mask=D)).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+the intensity tables of the nucleus (core) and of the grown ring as well (Annotator(expand_mask=D)); ``--repair-mask A`` (A >= 1) repairs the mask on
+the GPU before the expansion and before anything reads it -- the pieces of a torn label become labels of their own, pieces of fewer than A pixels are
+dropped, holes are filled -- and writes the repaired mask and a per-component table (Annotator(repair_mask=A)).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -70,6 +72,9 @@ def parse_args(argv=None):
     ap.add_argument('--expand-mask', type=int, default=0,
                     help='grow every label of the mask by this many pixels (1 .. 32) on the GPU before anything reads it: for nuclear masks; writes the '
                          'expanded mask and a per-cell expansion table, and with --intensities the core and ring tables (0 = use the mask as it is)')
+    ap.add_argument('--repair-mask', type=int, default=0,
+                    help='repair the mask on the GPU before anything reads it: pieces of a torn label become labels of their own, pieces of fewer than '
+                         'this many pixels are dropped, holes are filled; writes the repaired mask and a per-component table (0 = use the mask as it is)')
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument('--image-path', type=str)
     grp.add_argument('--batch-csv', type=str)
@@ -81,6 +86,8 @@ def parse_args(argv=None):
         ap.error("--contact-distance takes 0 (off) or a reach of 1 .. 8 pixels")
     if not 0 <= args.expand_mask <= 32:
         ap.error("--expand-mask takes 0 (off) or a distance of 1 .. 32 pixels")
+    if not 0 <= args.repair_mask <= 2 ** 31 - 1:
+        ap.error("--repair-mask takes 0 (off) or a smallest area of 1 pixel or more")
     return args
 
 
@@ -99,6 +106,12 @@ def _check_expand_mask(expand_mask):
     """the ValueError of ImageProcessor(expand_mask=...), before anything is built or read"""
     from multiplexed_image_annotator_amd import ops
     return ops.check_expand_distance(expand_mask, "expand_mask", allow_zero=True)
+
+
+def _check_repair_mask(repair_mask):
+    """the ValueError of ImageProcessor(repair_mask=...), before anything is built or read"""
+    from multiplexed_image_annotator_amd import repair
+    return repair.check_min_area(repair_mask, "repair_mask", allow_zero=True)
 
 
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
@@ -153,10 +166,11 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0, contact_perms=0):
+        nearest_bands=0, nearest_perms=0, repair_mask=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _check_expand_mask(expand_mask)
+    _check_repair_mask(repair_mask)
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     path_ = os.path.join(main_dir, "images.csv")
@@ -168,7 +182,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
         import torch.distributed as dist
         dist.barrier()
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
-                          cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask)
+                          cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
     intensity_dict = {}
@@ -182,14 +196,15 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, expand_mask=0, morphology=False, intensities=False,
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, repair_mask=0, expand_mask=0, morphology=False, intensities=False,
               contact_distance=0, contact_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _check_expand_mask(expand_mask)
+    _check_repair_mask(repair_mask)
     _setup()
     from multiplexed_image_annotator_amd.annotator import Annotator
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
-                          confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask)
+                          confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
 
@@ -203,7 +218,7 @@ def main(argv=None):
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
                   contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities,
-                  expand_mask=args.expand_mask)
+                  expand_mask=args.expand_mask, repair_mask=args.repair_mask)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

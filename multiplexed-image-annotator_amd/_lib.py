@@ -67,6 +67,9 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "ribca_expand_labels_ws_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ribca_expand_labels": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_mask_components_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "ribca_mask_components": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_mask_relabel": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ribca_knn_compositions": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "ribca_region_gram_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_region_gram": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

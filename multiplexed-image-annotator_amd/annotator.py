@@ -103,7 +103,7 @@ def _load_state_dict(path: str) -> Dict[str, torch.Tensor]:
 
 class Annotator(Analyses):
     def __init__(self, marker_list_path, image_path, device, main_dir='./', batch_id='', strict=True, infer=True, min_cells=-1,
-                 normalize=True, blur=False, amax=1, confidence=0.25, cell_size=30, cell_type_confidence=None, n_jobs=0, expand_mask=0):
+                 normalize=True, blur=False, amax=1, confidence=0.25, cell_size=30, cell_type_confidence=None, n_jobs=0, expand_mask=0, repair_mask=0):
         tile_env = tile_mode_env(min_cells)      # refuses RIBCA_TILE_MODE=1 with min_cells > 0 before any file is read
         self.device = device
         self.cell_types = ["B cell", "CD4 T cell", "CD8 T cell", "Dendritic cell", "Regulatory T cell", "Granulocyte cell", "Mast cell",
@@ -123,9 +123,11 @@ class Annotator(Analyses):
         self.channel_parser = MarkerParser(strict=strict, logger=self.logger)
         self.channel_parser.parse(marker_list_path)
         self.preprocessor = ImageProcessor(image_path, self.channel_parser, log_dir, device, batch_id, infer, normalize, blur, amax,
-                                           cell_size, self.logger, n_jobs=n_jobs, expand_mask=expand_mask)
+                                           cell_size, self.logger, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
         self.expand_mask = self.preprocessor.expand_mask      # validated there: 0, or the pixels every label of the mask is grown by
         self.expansion_stats: List[Dict[str, float]] = []     # per local image of an expanded run: n, D, pixels_grown, cells_unchanged, expand_ms
+        self.repair_mask = self.preprocessor.repair_mask      # validated there: 0, or the pixels below which a piece of a label is dropped
+        self.repair_stats: List[Dict[str, float]] = []        # per local image of a repairing run: the counts of repair.stats and repair_ms
         # multi-rank runs: whole images per rank when the batch CSV has at least one per rank (reference main.py:39-52 batch_run; BASELINE
         # config 5: replicas only, nothing exchanged, every rank writes the CSVs of its own images under their batch-wide numbers), cells of
         # every image otherwise (contiguous shards, one all-gather per image, rank 0 writes)
@@ -230,6 +232,7 @@ class Annotator(Analyses):
             self._n_images = len(self.preprocessor.image_ids)      # every per-image list below is indexed by LOCAL position
             self.logger.log("rank {} of {}: tile-per-rank mode, images {} of {}".format(rank, ws, self.preprocessor.image_ids,
                                                                                         self.preprocessor._n_images))
+            self._record_repair()
             self._record_expansion()
             return
         if ws > 1 and os.environ.get("RIBCA_NORM_SHARD") == "1":
@@ -237,7 +240,35 @@ class Annotator(Analyses):
         self.preprocessor.transform(shard_fn=(lambda n: dist.shard_bounds(n, rank, ws)) if ws > 1 else None,
                                     gather_fn=(lambda t, n: dist.all_gather_rows(t, n)) if ws > 1 else None)
         self._n_images = self.preprocessor._n_images
+        self._record_repair()
         self._record_expansion()
+
+    def _record_repair(self):
+        """With repair_mask = A > 0 the mask every stage reads is the mask of the batch CSV repaired by the rules of repair.py
+        (ImageProcessor._mask_to_device, ops.repair_labels, csrc/components.hip), before any expansion.  Per local image this writes
+        ``{batch_id}_repaired_mask_{image number}.npy`` (int32, the repaired mask before the expansion) and ``{batch_id}_repair_{image
+        number}.csv`` (repair.cells_csv: one line per foreground component of the mask as read) and records ``repair_stats``; its ``repair_ms``
+        is the host's clock around ops.repair_labels, synchronised (tools/time_consumers.py --repair times the kernel alone).  Multi-rank runs
+        as _record_expansion: cell-sharded ranks each repair the whole mask -- integers, the same on every rank -- and rank 0 writes."""
+        from . import repair
+        self.repair_stats = []
+        pre = self.preprocessor
+        if self.repair_mask == 0:
+            return
+        for i in range(len(pre.masks)):
+            rec = dict(pre.repair_records[i])
+            number = self._image_number(i)
+            rec["files"] = [f"{self.batch_id}_repaired_mask_{number}.npy", f"{self.batch_id}_repair_{number}.csv"]
+            self.repair_stats.append(rec)
+            if self._writes_files():
+                np.save(os.path.join(self.result_dir, rec["files"][0]), pre.masks_core_dev[i].cpu().numpy().astype(np.int32))
+                with open(os.path.join(self.result_dir, rec["files"][1]), "w") as f:
+                    f.write(repair.cells_csv(pre.repair_rows[i]))
+            self.logger.log("Mask repair {}: {} labels in, {} out; {} components split off, {} dropped ({} pixels, {} labels removed entirely); "
+                            "{} holes filled ({} pixels), {} enclosed by several labels left; ops.repair_labels {:.1f} ms.".format(
+                                rec["files"][1], rec["labels_in"], rec["labels_out"], rec["components_split"], rec["components_dropped"],
+                                rec["dropped_pixels"], rec["labels_removed"], rec["holes_filled"], rec["hole_pixels"], rec["holes_left"],
+                                rec["repair_ms"]))
 
     def _record_expansion(self):
         """With expand_mask = D > 0 the mask every stage reads is the mask of the batch CSV with each label grown by D pixels

@@ -572,6 +572,87 @@ def expand_labels(mask: torch.Tensor, distance: int, want_dist2: bool = False, w
     return (out, dist2) if want_dist2 else out
 
 
+COMPONENTS_TILE = 32              # csrc/components.hip CC_TILE
+
+
+def mask_components_ws_bytes(h: int, w: int) -> int:
+    return int(lib().ribca_mask_components_ws_bytes(int(h), int(w)))
+
+
+def _device_mask(mask, who: str) -> torch.Tensor:
+    if not torch.is_tensor(mask) or mask.dtype != torch.int32 or mask.dim() != 2 or not mask.is_cuda or mask.numel() == 0:
+        raise ValueError(f"{who} takes a non-empty (H, W) int32 device mask")
+    return mask.contiguous()
+
+
+def mask_components(mask: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The connected components of an (H, W) int32 device mask: pixels of one label > 0 at 8-connectivity, the pixels <= 0 (the background) at
+    4-connectivity.  Returns ``root`` (H, W) int32, for every pixel the raster index of the first pixel of its component, and ``stats``
+    (H W, 4) int32, at the row of every root the component's area, whether it touches the image border, and the smallest and largest label > 0
+    that is 4-adjacent to it (0, 0 without one); every other row is 0 (include/ribca_hip.h states the contract).  Does not synchronise."""
+    mask = _device_mask(mask, "mask_components")
+    h, w = mask.shape
+    root = torch.empty_like(mask)
+    stats = torch.empty((h * w, 4), dtype=torch.int32, device=mask.device)
+    if ws is None:
+        ws = _scratch(mask_components_ws_bytes(h, w), mask.device)
+    check(lib().ribca_mask_components(ptr(mask), h, w, ptr(root), ptr(stats), ptr(ws), ws.numel(), stream_ptr()), "ribca_mask_components")
+    return root, stats
+
+
+def relabel(root: torch.Tensor, new_label: torch.Tensor) -> torch.Tensor:
+    """``new_label[root]`` as a new (H, W) int32 device tensor: ``root`` as mask_components gives it, ``new_label`` H W int32 values on the
+    device, read at the raster index of every component's first pixel.  Does not synchronise."""
+    root = _device_mask(root, "relabel")
+    h, w = root.shape
+    if not torch.is_tensor(new_label) or new_label.dtype != torch.int32 or new_label.numel() != h * w or new_label.device != root.device:
+        raise ValueError("relabel takes one int32 label per pixel of root, on its device")
+    new_label = new_label.contiguous()
+    out = torch.empty_like(root)
+    check(lib().ribca_mask_relabel(ptr(root), ptr(new_label), h, w, ptr(out), stream_ptr()), "ribca_mask_relabel")
+    return out
+
+
+def _component_rows(mask: torch.Tensor, root: torch.Tensor, stats: torch.Tensor):
+    """the compacted rows of mask_components on the host: (index of the roots on the device, roots, the mask's value there, stats rows), ascending"""
+    idx = torch.nonzero(stats[:, 0] > 0).reshape(-1)
+    roots = idx.cpu().numpy().astype(np.int64)
+    labels = mask.reshape(-1).index_select(0, idx).cpu().numpy().astype(np.int64)
+    rows = stats.index_select(0, idx).cpu().numpy().astype(np.int64)
+    return idx, roots, labels, rows
+
+
+def repair_labels(mask: torch.Tensor, min_area: int):
+    """Repairs an (H, W) int32 device mask by the rules of repair.py: of the pieces of a torn label the largest keeps the label and the others
+    become labels of their own above the largest one, pieces of fewer than ``min_area`` pixels become background, and holes -- enclosed background
+    bordered by one label -- are filled.  Two runs of mask_components with the decisions taken on the host over the component rows between
+    them.  Returns (the repaired mask, a new device tensor whose background is 0; the (n, 7) int64 component rows in the order of
+    repair.COLUMNS, one per foreground component of the mask as read; the record of repair.stats, its ``repair_ms`` left at 0 for the caller's clock).  Synchronises."""
+    from . import repair
+    mask = _device_mask(mask, "repair_labels")
+    a = repair.check_min_area(min_area)
+    h, w = mask.shape
+    dev = mask.device
+    root, stats = mask_components(mask)
+    idx, roots, labels, rows = _component_rows(mask, root, stats)
+    fg = labels > 0
+    action, new_id = repair.decide(roots[fg], labels[fg], rows[fg, 0], a)
+    new = np.zeros(len(roots), dtype=np.int32)
+    new[fg] = new_id
+    table = torch.zeros(h * w, dtype=torch.int32, device=dev)
+    table[idx] = torch.from_numpy(new).to(dev)
+    mid = relabel(root, table)
+    root2, stats2 = mask_components(mid)
+    idx2, _, labels2, rows2 = _component_rows(mid, root2, stats2)
+    new2, hole, left = repair.fill(labels2, rows2[:, 1], rows2[:, 2], rows2[:, 3])
+    table.zero_()
+    table[idx2] = torch.from_numpy(new2.astype(np.int32)).to(dev)
+    out = relabel(root2, table)
+    comps = repair.rows(roots[fg], labels[fg], rows[fg, 0], action, new_id, w, new2[hole], rows2[hole, 0])
+    record = repair.stats(comps, a, int(hole.sum()), int(rows2[hole, 0].sum()), int(left.sum()))
+    return out, comps, record
+
+
 INTENSITY_SMALL_BOX = 1024       # csrc/intensities.hip IN_SMALL_BOX: a clipped box of at most this many pixels is one wave's
 INTENSITY_RESIDENT = 4096         # csrc/intensities.hip IN_RESIDENT: in a larger box, a cell of more pixels takes the streaming form
 INTENSITY_MAX_CHANNELS = 64

@@ -356,11 +356,15 @@ class LazyCellPositions(Mapping):
 
 class ImageProcessor(object):
     def __init__(self, csv_path, parser, main_path, device, batch_id='', infer=True, normalization=True, blur=0, amax=100, cell_size=30,
-                 logger=None, n_jobs=0, expand_mask=0) -> None:
+                 logger=None, n_jobs=0, expand_mask=0, repair_mask=0) -> None:
         import pandas as pd
+        from . import repair
         # 0: the mask outlines whole cells and is used as read.  D in 1 .. 32: the mask outlines nuclei and every label is grown by D pixels on
         # the device before anything reads it (ops.expand_labels; skimage's expand_labels, the "cell expansion" of steinbock, MCMICRO and QuPath)
         self.expand_mask = ops.check_expand_distance(expand_mask, "expand_mask", allow_zero=True)
+        # 0: the mask is used as read.  A >= 1: torn labels are split into labels of their own, pieces of fewer than A pixels dropped and holes
+        # filled on the device before the expansion and before anything reads the mask (ops.repair_labels, repair.py states the rules)
+        self.repair_mask = repair.check_min_area(repair_mask, "repair_mask", allow_zero=True)
         table = pd.read_csv(csv_path)
         self.image_paths = table['image_path']
         self.mask_paths = table['mask_path']
@@ -406,6 +410,10 @@ class ImageProcessor(object):
         self.core_tables: List[np.ndarray] = []
         self.core_bbox_dev: List[torch.Tensor] = []
         self.expand_ms: List[float] = []
+        # a run with repair_mask > 0, per image: the component rows of repair.COLUMNS and the record of repair.stats with its repair_ms, the
+        # host clock around ops.repair_labels; masks_core_dev then holds the REPAIRED mask
+        self.repair_rows: List[np.ndarray] = []
+        self.repair_records: List[Dict[str, float]] = []
         # multi-rank runs (set by Annotator.preprocess): image_ids[j] = row of the batch CSV that local position j holds (tile-per-rank mode
         # keeps only this rank's images; every per-image list above is indexed by local position); norm_shard = (rank, world_size) when the
         # whole-image normalisation is split by channel with one all-gather of the planes (cell-sharded mode, RIBCA_NORM_SHARD=1)
@@ -436,21 +444,32 @@ class ImageProcessor(object):
 
     def _mask_to_device(self, mask: np.ndarray):
         """THE upload of a mask: every path that puts a mask on the device goes through here, so that none sees the mask as read when the run
-        expands it.  Returns (the mask every stage uses, on the device; the mask as read, on the device; the host copy of the first; the
-        milliseconds of the expansion).  With expand_mask = 0 the first two are one tensor and the host copy is ``mask`` itself."""
+        repairs or expands it.  Returns (the mask every stage uses, on the device; the mask before the expansion, on the device; the host copy
+        of the first; the milliseconds of the expansion; None, or with repair_mask > 0 the component rows and the record of the repair).  With
+        repair_mask = 0 and expand_mask = 0 the first two are one tensor and the host copy is ``mask`` itself.  The repair comes first: the
+        expansion grows the repaired labels."""
         import time
         core_d = torch.from_numpy(mask).to(_lib.require_gpu())
+        repaired = None
+        if self.repair_mask > 0:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            core_d, rows, record = ops.repair_labels(core_d, self.repair_mask)
+            torch.cuda.synchronize()
+            record["repair_ms"] = (time.perf_counter() - t0) * 1e3
+            repaired = (rows, record)
+            mask = core_d.cpu().numpy()
         if self.expand_mask == 0:
-            return core_d, core_d, mask, 0.0
+            return core_d, core_d, mask, 0.0, repaired
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         grown_d = ops.expand_labels(core_d, self.expand_mask)
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3
-        return grown_d, core_d, grown_d.cpu().numpy(), ms
+        return grown_d, core_d, grown_d.cpu().numpy(), ms, repaired
 
     def _cell_pos_dict(self, mask, n_jobs=0) -> LazyCellPositions:
-        mask_d, _, mask_np, _ = self._mask_to_device(np.asarray(mask).astype(np.int32))
+        mask_d, _, mask_np, _, _ = self._mask_to_device(np.asarray(mask).astype(np.int32))
         ids, table = ops.label_table(mask_d)
         return LazyCellPositions(mask_np, ids, table)
 
@@ -486,7 +505,7 @@ class ImageProcessor(object):
                 img_d = self._normalize(image, blur=self.blur, amax=self.amax)
             else:
                 img_d = torch.from_numpy(np.ascontiguousarray(image).astype(np.float32)).to(dev)
-            mask_d, core_d, mask, expand_ms = self._mask_to_device(mask)      # from here on `mask` is the mask every stage uses
+            mask_d, core_d, mask, expand_ms, repaired = self._mask_to_device(mask)      # from here on `mask` is the mask every stage uses
             self.masks.append(mask)
             ids, table, ids_d, bbox_d = ops.label_table(mask_d, with_device=True)
             if core_d is mask_d:
@@ -498,6 +517,9 @@ class ImageProcessor(object):
             self.core_tables.append(core_table)
             self.core_bbox_dev.append(core_bbox_d)
             self.expand_ms.append(expand_ms)
+            if repaired is not None:
+                self.repair_rows.append(repaired[0])
+                self.repair_records.append(repaired[1])
             self.cell_ids_dev.append(ids_d)
             self.cell_bbox_dev.append(bbox_d)
             self.cell_pos_dict.append(LazyCellPositions(mask, ids, table))

@@ -23,7 +23,9 @@ marker intensities (csrc/intensities.hip): the kernel alone on a 15-channel fp32
 ranks and for the median alone, the host features, and the numpy restatement of tests/intensities_numpy.py on the same crop, scaled by the area
 (``--intensities``: this section alone); and the expansion of the mask's labels (csrc/expand.hip): the kernel alone at D = 2, 8 and 32, device
 events, mask, outputs and workspace on the device, and as the host yardstick scipy's distance_transform_edt(return_indices=True) on the same mask,
-whose composition at D = 8 is compared with the kernel's output (``--expand``: this section alone)."""
+whose composition at D = 8 is compared with the kernel's output (``--expand``: this section alone); and the repair of the mask
+(csrc/components.hip): the connected components of the same mask with 4000 injected faults, device events, the whole ops.repair_labels on the
+host clock, and scipy.ndimage.label of the same mask on the host (``--repair``: this section alone)."""
 import os
 import sys
 import time
@@ -338,6 +340,75 @@ def time_expand():
           f"the squared distances equal: {same_dist}, labels that differ (tie pixels, scan order against smallest label): {differ} of {int(grown.sum())}")
 
 
+# ---- repairing the mask (csrc/components.hip, repair.py): connected components, torn labels split, specks dropped, holes filled -----------------------
+def time_repair():
+    """the mask with a few thousand injected faults -- 1000 cells given another cell's label, a one-pixel hole at the centroid of 2000 cells, 1000
+    specks of one pixel -- on the device before the clock starts: ribca_mask_components alone between two device events, median of five calls
+    after a warm-up; the whole ops.repair_labels (two component runs, two relabels, the compaction, the copies of the rows and the host's
+    decisions) on the host clock, synchronised; then scipy.ndimage.label on the host, once for the foreground at 8-connectivity and once for
+    the background at 4-connectivity -- one call each, where a per-label repair would call it per label -- and its component count beside the
+    kernel's"""
+    from scipy import ndimage
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    h, w = mask.shape
+    fault_rng = np.random.default_rng(7)
+    picks = fault_rng.permutation(n)[:4000]
+    lut = np.arange(int(ids.max()) + 1, dtype=np.int32)
+    lut[ids[picks[:1000]]] = ids[picks[1000:2000]]      # 1000 labels now name two cells each
+    damaged = torch.from_numpy(lut).to(dev)[mask.long()].contiguous()
+    cr, cc = (tab[:, 4] // tab[:, 6]), (tab[:, 5] // tab[:, 6])
+    holes = picks[2000:4000]
+    damaged[torch.from_numpy(cr[holes]).to(dev), torch.from_numpy(cc[holes]).to(dev)] = 0
+    sr, sc = fault_rng.integers(0, h, 1000), fault_rng.integers(0, w, 1000)
+    damaged[torch.from_numpy(sr).to(dev), torch.from_numpy(sc).to(dev)] = torch.from_numpy(ids[fault_rng.integers(0, n, 1000)].astype(np.int32)).to(dev)
+    root = torch.empty_like(damaged)
+    stats = torch.empty((h * w, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(ops.mask_components_ws_bytes(h, w), 1), dtype=torch.uint8, device=dev)
+
+    def call():
+        _lib.check(lib().ribca_mask_components(ptr(damaged), h, w, ptr(root), ptr(stats), ptr(ws), ws.numel(), stream_ptr()), "components")
+
+    call()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        call()
+        stop.record()
+        torch.cuda.synchronize()
+        times.append(start.elapsed_time(stop))
+    rows = stats[:, 0] > 0
+    comps = int(rows.sum())
+    background = int((rows & (damaged.reshape(-1) <= 0)).sum())
+    floor = 2 * h * w * 4
+    print(f"mask components: median {sorted(times)[2]:.3f} ms, min {min(times):.3f}, max {max(times):.3f} of 5 (device events) for {h}x{w}, {n} cells with "
+          f"4000 injected faults; {comps - background} foreground and {background} background components; one read of the mask and one write of "
+          f"root, {floor / 1e9:.2f} GB at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: {1e3 * floor / HBM_BYTES_PER_S:.3f} ms; the stats rows are {4 * h * w * 4 / 1e9:.2f} GB more")
+    ops.repair_labels(damaged, 3)
+    times = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out, comp_rows, record = ops.repair_labels(damaged, 3)
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"ops.repair_labels(min_area=3), whole: median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} of 5 (host clock, synchronised); "
+          f"{record}")
+    host = damaged.cpu().numpy()
+    t0 = time.perf_counter()
+    _, n_fg = ndimage.label(host > 0, structure=np.ones((3, 3), dtype=int))
+    fg_ms = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    _, n_bg = ndimage.label(host <= 0)
+    bg_ms = 1e3 * (time.perf_counter() - t0)
+    print(f"scipy.ndimage.label, {h}x{w} (host): {fg_ms:.0f} ms for the foreground as one class at 8-connectivity ({n_fg} blobs; the kernel separates "
+          f"labels), {bg_ms:.0f} ms for the background at 4-connectivity; its {n_bg} background components are the kernel's: {n_bg == background}")
+
+
+if "--repair" in sys.argv:      # this section alone
+    time_repair()
+    sys.exit(0)
 if "--expand" in sys.argv:      # this section alone
     time_expand()
     sys.exit(0)
@@ -554,3 +625,4 @@ time_intensities()
 
 # ---- growing the labels of the mask: defined above as well ------------------------------------------------------------------------------------------
 time_expand()
+time_repair()
