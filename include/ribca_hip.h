@@ -402,6 +402,42 @@ int64_t ribca_mask_components_ws_bytes(int32_t H, int32_t W);
 int ribca_mask_components(const int32_t* mask, int32_t H, int32_t W, int32_t* root, int32_t* stats, void* ws, int64_t ws_bytes, void* stream);
 int ribca_mask_relabel(const int32_t* root, const int32_t* new_label, int32_t H, int32_t W, int32_t* out, void* stream);
 
+/* ---- cell outlines: the boundary of every cell of a mask as closed rings of lattice vertices (csrc/outlines.hip) -----------
+ * mask (H, W) int32 row-major on the device, read only.  LATTICE: vertex (r, c), 0 <= r <= H, 0 <= c <= W, is the top-left corner of pixel (r, c);
+ * its raster index is r (W + 1) + c.  OWNERSHIP is the rule of ribca_contact_table: pixel p belongs to cell i = label_to_cell[mask[p]] when
+ * 0 <= mask[p] < L and 0 <= i < n, and to no cell otherwise; nothing outside the image belongs to a cell; a label in several blobs, and several
+ * labels mapped to one cell, are one cell.  BOUNDARY EDGES of cell i: every side of a pixel of i whose pixel across is not of i, as a directed
+ * unit edge with the pixel on the RIGHT of the direction of travel (x = column to the right, y = row downwards): top (r, c) -> (r, c + 1), right
+ * (r, c + 1) -> (r + 1, c + 1), bottom (r + 1, c + 1) -> (r + 1, c), left (r + 1, c) -> (r, c).  SUCCESSOR: where cell i has one outgoing edge
+ * at the vertex an edge ends in, that edge; at a saddle -- the cell holds exactly two diagonally opposite pixels of the four around the vertex and
+ * has two outgoing edges -- the LEFT turn, which joins the two pixels (the 8-connected foreground and 4-connected rest of ribca_mask_components
+ * and of the Euler number of ribca_mask_morphology).  The edges of a cell fall into closed RINGS.
+ * A ring row is six int64: cell; start = the raster index of the ring's smallest vertex (no two rings of one cell share it); vertices = the
+ * number of vertices at which the direction changes (the start is one of them); edges = its length in unit edges; area2 = the sum over
+ * consecutive kept vertices of x_k y_{k+1} - x_{k+1} y_k, positive for an exterior ring and negative for a hole; saddles = the number of times
+ * the ring passes a saddle vertex.  An exterior ring leaves its start going east, a hole ring going south.
+ * ribca_mask_rings: rings (cap, 6) int64 and total (1) int64 are OVERWRITTEN.  total is always the exact number of rings.  With total <= cap the
+ * first total rows are the rings of the mask in an UNSPECIFIED order and every other row is -1; with total > cap only total is defined, the status
+ * is still 0 and the caller calls again.  The SET of rows is a function of (mask, label_to_cell) alone, whatever the launch geometry and the order
+ * in which threads arrive.  ws: ribca_mask_rings_ws_bytes(H, W, n) bytes (0 for arguments the entry point refuses): the owner of every pixel and
+ * the list of candidate starts, 12 bytes per pixel.
+ * ribca_mask_ring_vertices: rings (R, 6) as above in any order the caller chose; first (R + 1) int64 ascending from 0 with first[k + 1] - first[k]
+ * = the vertices of row k; vertices (first[R], 2) int32 = [r, c] and bad (1) int32 are OVERWRITTEN.  Ring k is walked again from its start and
+ * writes its kept vertices, the start first, in the order of the ring, at first[k].  A row that does not fit the mask -- no ring of that cell
+ * starts there, the walk finds another vertex count, first[k + 1] - first[k] is not the row's count -- writes -1 into its own range
+ * [first[k], first[k + 1]) and adds one to bad; a range that is none (descending, negative, past first[R]) adds one to bad and writes nothing.  No
+ * thread writes outside the range of its own ring, whatever the rows say.  first lives on the device, so what is wrong with it is reported in bad,
+ * not in the status.
+ * Both: 1 <= H, W, (H + 1)(W + 1) < 2^31, 1 <= L, 0 <= n <= 2^21, 1 <= cap, 0 <= R; labels are any int32; integer arithmetic only.  n = 0 (and
+ * R = 0) launches no walk: total = 0 and rings = -1, bad = 0.  The buffers must not overlap.  A NULL buffer, a short workspace and arguments out
+ * of range are refused with a status before any HIP call.  No loop of the kernels waits for another thread, and every walk ends after at most
+ * 2 (H + 1)(W + 1) steps, more than a ring has edges.  Neither entry point synchronises. */
+int64_t ribca_mask_rings_ws_bytes(int32_t H, int32_t W, int32_t n);
+int ribca_mask_rings(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, int64_t cap, int64_t* rings,
+                     int64_t* total, void* ws, int64_t ws_bytes, void* stream);
+int ribca_mask_ring_vertices(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, const int64_t* rings,
+                             int32_t R, const int64_t* first, int32_t* vertices, int32_t* bad, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

@@ -20,7 +20,9 @@ summary, the standardised type medians and one map per marker and image (Annotat
 before anything reads it -- for masks that outline nuclei -- and writes the grown mask and a per-cell expansion table, and with ``--intensities``
 the intensity tables of the nucleus (core) and of the grown ring as well (Annotator(expand_mask=D)); ``--repair-mask A`` (A >= 1) repairs the mask on
 the GPU before the expansion and before anything reads it -- the pieces of a torn label become labels of their own, pieces of fewer than A pixels are
-dropped, holes are filled -- and writes the repaired mask and a per-component table (Annotator(repair_mask=A)).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+dropped, holes are filled -- and writes the repaired mask and a per-component table (Annotator(repair_mask=A)); ``--outlines`` every cell of the mask
+the run works on as a polygon with its id, area, cell type, colour and confidence, traced on the GPU, one GeoJSON file (the layout of QuPath's export)
+and one per-cell CSV per image (Annotator.cell_outlines).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -69,6 +71,9 @@ def parse_args(argv=None):
                     help='per-cell morphology table from the mask (shape, border, Euler number, patch coverage), per-type summary and two maps per image')
     ap.add_argument('--intensities', action='store_true',
                     help="per-cell marker intensities over the cell's own mask pixels (mean, std, min, quartiles, max), per-type summary and one map per marker and image")
+    ap.add_argument('--outlines', action='store_true',
+                    help='every cell as a polygon with properties, traced on the GPU from the mask after repair and expansion: one GeoJSON file '
+                         '(QuPath detections: id, area, cell type, colour, confidence) and one per-cell ring table per image')
     ap.add_argument('--expand-mask', type=int, default=0,
                     help='grow every label of the mask by this many pixels (1 .. 32) on the GPU before anything reads it: for nuclear masks; writes the '
                          'expanded mask and a per-cell expansion table, and with --intensities the core and ring tables (0 = use the mask as it is)')
@@ -115,7 +120,7 @@ def _check_repair_mask(repair_mask):
 
 
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
-              nearest_perms=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
+              nearest_perms=0, outlines=False, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
               contact_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
@@ -158,6 +163,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
         if expand_mask > 0:                         # the mask was grown from nuclei: the same table over the nucleus and over the grown ring
             annotator.cell_intensities(integrate=True, maps=False, compartment="core")
             annotator.cell_intensities(integrate=True, maps=False, compartment="ring")
+    if outlines:                                    # and the cells as objects a viewer can load: polygons with properties, per image
+        annotator.cell_outlines()
     annotator.colorize(from_script=True)
     annotator.cell_type_composition()
     annotator.cell_type_composition(integrate=True)
@@ -166,7 +173,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, repair_mask=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0, contact_perms=0):
+        nearest_bands=0, nearest_perms=0, outlines=False, repair_mask=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
+        contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _check_expand_mask(expand_mask)
@@ -184,7 +192,8 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
     annotator = Annotator(marker_list_path, path_, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax, confidence,
                           cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
-              expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
+              expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
+              outlines=outlines)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -196,8 +205,8 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, repair_mask=0, expand_mask=0, morphology=False, intensities=False,
-              contact_distance=0, contact_perms=0):
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, outlines=False, repair_mask=0, expand_mask=0, morphology=False,
+              intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
     _check_expand_mask(expand_mask)
     _check_repair_mask(repair_mask)
@@ -206,7 +215,8 @@ def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, stri
     annotator = Annotator(marker_list_path, image_path, device, main_dir, batch_id, strict, infer, min_cells, normalize, blur, amax,
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
-              expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms)
+              expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
+              outlines=outlines)
 
 
 def main(argv=None):
@@ -218,7 +228,7 @@ def main(argv=None):
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
                   contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities,
-                  expand_mask=args.expand_mask, repair_mask=args.repair_mask)
+                  expand_mask=args.expand_mask, repair_mask=args.repair_mask, outlines=args.outlines)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
     return run(image_path=args.image_path, mask_path=args.mask_path, **common)

@@ -673,6 +673,56 @@ class Analyses(object):
                             "classifier window, {} on the image border; ops.mask_morphology with its copies {:.1f}, tables and drawing {:.1f} ms.".format(
                                 files[0], cells, t, odd, cut, on_edge, kernel_ms, draw_ms))
 
+    # ---- cell outlines: every cell as a polygon with properties, for QuPath, napari and anything that reads GeoJSON ---------------------------------
+    def cell_outlines(self):
+        """The outline of every cell of every image as polygons, traced on the GPU from the segmentation mask the run works on -- after
+        ``repair_mask`` and ``expand_mask`` -- (ops.mask_rings, csrc/outlines.hip: exact closed rings of lattice vertices, exterior rings and
+        holes, pixels that touch only at a corner joined as the Euler number of cell_morphology joins them) and written per image as
+        ``{batch_id}_outlines_{image number}.geojson`` (outlines.geojson: one FeatureCollection in the layout of QuPath's own export, one
+        detection per cell with its id, area and -- after predict() -- cell type, the colour ``colorize`` paints that type and the confidence
+        ``export_annotations`` prints; coordinates are [column, row] lattice vertices in pixel units, vertex (r, c) the top-left corner of
+        pixel (r, c)) and ``{batch_id}_outlines_{image number}.csv`` (outlines.cells_csv: per cell the area, the exterior and hole rings, the
+        vertices, the boundary edges and the saddle passes).  Needs preprocess() only; before predict() the classification and the confidence
+        are absent.  Per image only, no collective: cell-sharded runs write on rank 0, tile-per-rank runs on the rank that owns the image.
+        Records ``outline_stats``, one record per image written by this rank; its ``kernel_ms`` is the host's clock around ops.mask_rings --
+        the label table, both kernels, the sort and the copies back -- (tools/time_consumers.py --outlines times the kernels alone) and
+        ``write_ms`` the polygons, both texts and the files."""
+        import time
+        from . import outlines
+        pre = self.preprocessor
+        if len(pre.masks_dev) == 0 and not (self.tile_mode and pre._n_images > 0):
+            raise ValueError("No masks: call preprocess() first")
+        self.outline_stats = []
+        if not self._computes_here():
+            return None
+        annotated = len(self.annotations) == len(pre.masks_dev) and len(self.annotations) > 0
+        names = [str(c) for c in self.cell_types]
+        for i in range(len(pre.masks_dev)):
+            ids = np.asarray(pre.cell_ids[i], dtype=np.int64)
+            n = len(ids)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = ops.mask_rings(pre.masks_dev[i], ids)
+            kernel_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            types = colours = conf = None
+            if annotated:
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                colours = np.array(self.colors, dtype=np.uint8).reshape(-1, 3)
+                conf = self._confidence_text(i)
+            number = self._image_number(i)
+            files = [f"{self.batch_id}_outlines_{number}.geojson", f"{self.batch_id}_outlines_{number}.csv"]
+            self._write_text(files[0], outlines.geojson(got["rings"], got["first"], got["vertices"], ids, types, names, colours, conf))
+            self._write_text(files[1], outlines.cells_csv(got["rings"], ids, types, names))
+            write_ms = (time.perf_counter() - t0) * 1e3
+            rec = {"file": files[0], "files": files, "annotated": annotated, "calls": int(got["calls"]), "kernel_ms": kernel_ms, "write_ms": write_ms}
+            rec.update(outlines.image_stats(got["rings"], n))
+            self.outline_stats.append(rec)
+            self.logger.log("Cell outlines {}: {} cells, {} rings ({} holes, {} cells in several parts), {} vertices, {} saddle passes, longest ring {} "
+                            "edges; ops.mask_rings with its copies {:.1f} ({} call(s)), polygons and files {:.1f} ms.".format(
+                                files[0], n, rec["rings"], rec["holes"], rec["multi_part"], rec["vertices"], rec["saddles"], rec["longest_ring"],
+                                kernel_ms, rec["calls"], write_ms))
+
     # ---- cell intensities: the marker columns of the single-cell table, over each cell's own pixels (steinbock's measure intensities) ------------
     def cell_intensities(self, integrate=True, maps=True, compartment="cell"):
         """The marker intensity table of every image: per cell and image channel the mean, population std, min, quartiles and max over the cell's

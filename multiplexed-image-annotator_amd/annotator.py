@@ -572,22 +572,10 @@ class Annotator(Analyses):
         for i in range(len(self.annotations)):
             path = os.path.join(self.result_dir, f"{self.batch_id}_annotation_{self._image_number(i)}.csv")
             ids = self.preprocessor.cell_ids[i]
-            conf = self.confidence[i]
             x, y = self._centroids(i)
             rows, cols = np.round(y, 2), np.round(x, 2)
             regions = getattr(self, "tissue_regions", None)
-            # The reference prints ``round(np.float32, 3)`` through an f-string (the float32 widened to double, e.g.
-            # 0.5360000133514404) and the int -1 of a thresholded cell as "-1".  Same text, rounded and widened in one numpy call
-            # instead of 100 k Python round() calls when the confidences are still the float32 table predict() produced.
-            arr = self._conf_arrays[i] if i < len(getattr(self, "_conf_arrays", [])) and len(self._conf_arrays[i]) == len(conf) else None
-            # ``confidence`` is public state (the reference's own _find_extra_cell_types edits it after predict()): the cached table is
-            # only used while it still says the same thing
-            if arr is not None and not np.array_equal(arr, np.asarray(conf, dtype=np.float32)):
-                arr = None
-            if arr is not None:
-                conf_txt = ["-1" if v == -1.0 else repr(v) for v in np.round(arr, 3).tolist()]
-            else:
-                conf_txt = [f"{round(c, 3)}" for c in conf]
+            conf_txt = self._confidence_text(i)
             keys, labs, rl, cl = ids.tolist(), self.annotations[i], rows.tolist(), cols.tolist()
             with open(path, "w") as f:
                 f.write("Cell Index,Cell Type,Confidence,Row,Column,Tissue Region\n")
@@ -597,6 +585,21 @@ class Annotator(Analyses):
                     reg = regions[i]
                     f.write("".join([f"{k},{l},{c},{r},{cc},Region {reg[k]}\n" for k, l, c, r, cc in zip(keys, labs, conf_txt, rl, cl)]))
             self.logger.log(f"Exported annotations for image {i} to {path}")
+
+    def _confidence_text(self, i: int) -> List[str]:
+        """the ``Confidence`` column of local image i as export_annotations prints it, one string per cell"""
+        conf = self.confidence[i]
+        # The reference prints ``round(np.float32, 3)`` through an f-string (the float32 widened to double, e.g.
+        # 0.5360000133514404) and the int -1 of a thresholded cell as "-1".  Same text, rounded and widened in one numpy call
+        # instead of 100 k Python round() calls when the confidences are still the float32 table predict() produced.
+        arr = self._conf_arrays[i] if i < len(getattr(self, "_conf_arrays", [])) and len(self._conf_arrays[i]) == len(conf) else None
+        # ``confidence`` is public state (the reference's own _find_extra_cell_types edits it after predict()): the cached table is
+        # only used while it still says the same thing
+        if arr is not None and not np.array_equal(arr, np.asarray(conf, dtype=np.float32)):
+            arr = None
+        if arr is not None:
+            return ["-1" if v == -1.0 else repr(v) for v in np.round(arr, 3).tolist()]
+        return [f"{round(c, 3)}" for c in conf]
 
     def min_cells_per_image(self) -> int:
         """fewest cells in any image of the batch (what the reference's k-NN calls need to exceed); in tile-per-rank mode the minimum over

@@ -653,6 +653,68 @@ def repair_labels(mask: torch.Tensor, min_area: int):
     return out, comps, record
 
 
+OUTLINES_TILE = 32                # csrc/outlines.hip OL_TILE
+OUTLINES_SPARE_ROWS = 1024        # rows of the first attempt beyond two per cell
+RING_COLUMNS = ("cell", "start", "vertices", "edges", "area2", "saddles")
+
+
+def mask_rings_ws_bytes(h: int, w: int, n: int) -> int:
+    return int(lib().ribca_mask_rings_ws_bytes(int(h), int(w), int(n)))
+
+
+def mask_rings(mask: torch.Tensor, ids: np.ndarray, ws: Optional[torch.Tensor] = None, first_cap: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """The outlines of the cells ``ids`` (ascending mask labels, cell i = ids[i]; the label -> cell table is built as ``contact_graph`` builds
+    it, label 0 never a cell) of an (H, W) int32 device mask as closed rings of lattice vertices, traced on the GPU (csrc/outlines.hip;
+    include/ribca_hip.h states the lattice, the saddle rule and the ring row).  Returns host arrays: ``rings`` (R, 6) int64 -- cell, start,
+    vertices, edges, area2, saddles (RING_COLUMNS) -- sorted by (cell, start); ``first`` (R + 1) int64, the prefix sum of the vertex counts;
+    ``vertices`` (first[R], 2) int32 = [r, c], the vertices of ring k at which the direction changes from first[k] on, the start first, in the
+    order of the ring (exterior rings clockwise on the screen, holes counter-clockwise); and ``calls``, how often ribca_mask_rings ran: once
+    with room for ``first_cap`` rings (None: 2 n + 1024), a second time with the exact number when the mask has more.  RibcaError when a ring the first kernel reported
+    does not trace again.  Synchronises."""
+    mask = _device_mask(mask, "mask_rings")
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n = len(ids)
+    empty = {"rings": np.zeros((0, 6), np.int64), "first": np.zeros(1, np.int64), "vertices": np.zeros((0, 2), np.int32), "calls": 0}
+    if n == 0:
+        return empty
+    dev = mask.device
+    h, w = mask.shape
+    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
+    table[ids] = np.arange(n, dtype=np.int32)
+    table[0] = -1      # colorize paints labels > 0 only
+    tab_d = torch.from_numpy(table).to(dev)
+    if ws is None:
+        ws = _scratch(mask_rings_ws_bytes(h, w, n), dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    cap, calls = (2 * n + OUTLINES_SPARE_ROWS if first_cap is None else max(int(first_cap), 1)), 0
+    while True:
+        rings = torch.empty((cap, 6), dtype=torch.int64, device=dev)
+        check(lib().ribca_mask_rings(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, cap, ptr(rings), ptr(total), ptr(ws), ws.numel(), stream_ptr()),
+              "ribca_mask_rings")
+        calls += 1
+        found = int(total.item())
+        if found <= cap:
+            break
+        if calls == 2:
+            raise _lib.RibcaError(f"ribca_mask_rings: {found} rings after a call that counted {cap}")
+        cap = found
+    if found == 0:
+        empty["calls"] = calls
+        return empty
+    rings = rings[:found]
+    order = torch.argsort(rings[:, 0] * ((h + 1) * (w + 1)) + rings[:, 1])      # (cell, start): no two rings of a cell share a start
+    rings = rings.index_select(0, order).contiguous()
+    first = torch.zeros(found + 1, dtype=torch.int64, device=dev)
+    first[1:] = torch.cumsum(rings[:, 2], 0)
+    vertices = torch.empty((int(first[-1].item()), 2), dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().ribca_mask_ring_vertices(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, ptr(rings), found, ptr(first), ptr(vertices), ptr(bad),
+                                         stream_ptr()), "ribca_mask_ring_vertices")
+    if int(bad.item()) != 0:
+        raise _lib.RibcaError(f"ribca_mask_ring_vertices: {int(bad.item())} of {found} rings did not trace again")
+    return {"rings": rings.cpu().numpy(), "first": first.cpu().numpy(), "vertices": vertices.cpu().numpy(), "calls": calls}
+
+
 INTENSITY_SMALL_BOX = 1024       # csrc/intensities.hip IN_SMALL_BOX: a clipped box of at most this many pixels is one wave's
 INTENSITY_RESIDENT = 4096         # csrc/intensities.hip IN_RESIDENT: in a larger box, a cell of more pixels takes the streaming form
 INTENSITY_MAX_CHANNELS = 64

@@ -1,0 +1,165 @@
+"""Annotator.cell_outlines end to end on the two-image batch of the cell-type plots: after preprocess() alone both files of each image are
+text-equal to outlines.geojson and outlines.cells_csv over the rings tests/outlines_numpy.py traces from the mask file, without a classification;
+after predict() they carry the cell types and confidences of the annotation CSV and the colours of the colorized PNG; with repair_mask and
+expand_mask set the polygons of the file fill exactly the repaired and expanded mask the run wrote; outline_stats is filled; a run without the
+call writes no outline file."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import outlines_numpy as ON
+from multiplexed_image_annotator_amd import outlines
+from test_gpu_celltype_plots import two_image_case
+from test_gpu_extra_cell_types import _weights
+from test_gpu_repair_e2e import paint_faults
+
+pytestmark = pytest.mark.gpu
+
+
+def _annotator(root, out, **kw):
+    from multiplexed_image_annotator_amd.annotator import Annotator
+    a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", out, "x", False, False, -1, True, 0.3, 99.8, 0.0, 30, None,
+                  **kw)
+    a.set_weights(_weights())
+    return a
+
+
+def _outline_files(out):
+    res = os.path.join(out, "results")
+    return {f: open(os.path.join(res, f)).read() for f in sorted(os.listdir(res)) if "outlines" in f}
+
+
+@pytest.fixture(scope="module")
+def runs(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("outlines")
+    root = str(tmp / "case")
+    os.makedirs(root)
+    two_image_case(root)
+    masks = [np.load(os.path.join(root, d, "mask.npy")).astype(np.int32) for d in ("a", "b")]
+    traced = []
+    for m in masks:
+        table, ids = ON.label_table(m)
+        traced.append((ids,) + ON.trace(m, table, len(ids)))
+    a = _annotator(root, str(tmp / "plain"))
+    with pytest.raises(ValueError):
+        a.cell_outlines()                      # before preprocess()
+    a.preprocess()
+    assert _outline_files(str(tmp / "plain")) == {}
+    a.cell_outlines()
+    before = _outline_files(str(tmp / "plain"))
+    stats_before = list(a.outline_stats)
+    a.predict(16)
+    a.export_annotations()
+    a.colorize(from_script=True)
+    a.cell_outlines()
+    after = _outline_files(str(tmp / "plain"))
+    # the same batch with faults painted in, repaired and grown; preprocess() only
+    damaged = str(tmp / "damaged")
+    os.makedirs(damaged)
+    two_image_case(damaged)
+    for d in ("a", "b"):
+        path = os.path.join(damaged, d, "mask.npy")
+        np.save(path, paint_faults(np.load(path).astype(np.int32))[0])
+    b = _annotator(damaged, str(tmp / "both"), repair_mask=3, expand_mask=2)
+    b.preprocess()
+    b.cell_outlines()
+    # and a run that never calls it
+    c = _annotator(root, str(tmp / "without"))
+    c.preprocess()
+    c.predict(16)
+    c.export_annotations()
+    c.colorize(from_script=True)
+    return {"tmp": str(tmp), "a": a, "b": b, "masks": masks, "traced": traced, "before": before, "after": after, "stats_before": stats_before}
+
+
+def test_after_preprocess_alone_the_files_are_the_restated_rings_without_a_classification(runs):
+    assert sorted(runs["before"]) == ["x_outlines_0.csv", "x_outlines_0.geojson", "x_outlines_1.csv", "x_outlines_1.geojson"]
+    for i in range(2):
+        ids, rings, first, vertices = runs["traced"][i]
+        assert len(rings) >= len(ids) > 100
+        assert runs["before"][f"x_outlines_{i}.geojson"] == outlines.geojson(rings, first, vertices, ids)
+        assert runs["before"][f"x_outlines_{i}.csv"] == outlines.cells_csv(rings, ids)
+        doc = json.loads(runs["before"][f"x_outlines_{i}.geojson"])
+        assert len(doc["features"]) == len(ids)
+        assert all("classification" not in f["properties"] and "confidence" not in f["properties"]["measurements"] for f in doc["features"])
+        rec = runs["stats_before"][i]
+        assert rec["files"] == [f"x_outlines_{i}.geojson", f"x_outlines_{i}.csv"] and rec["annotated"] is False
+
+
+def test_after_predict_the_files_carry_the_types_confidences_and_colours_of_the_other_outputs(runs):
+    from PIL import Image
+    a = runs["a"]
+    res = os.path.join(runs["tmp"], "plain", "results")
+    for i in range(2):
+        ids, rings, first, vertices = runs["traced"][i]
+        rows = [r.split(",") for r in open(os.path.join(res, f"x_annotation_{i}.csv")).read().strip().split("\n")[1:]]
+        assert [int(r[0]) for r in rows] == ids.tolist()
+        names = [str(c) for c in a.cell_types]
+        types = np.array([names.index(r[1]) for r in rows])
+        conf = [r[2] for r in rows]
+        text = runs["after"][f"x_outlines_{i}.geojson"]
+        assert text == outlines.geojson(rings, first, vertices, ids, types, names, np.array(a.colors), conf)
+        assert runs["after"][f"x_outlines_{i}.csv"] == outlines.cells_csv(rings, ids, types, names)
+        assert text != runs["before"][f"x_outlines_{i}.geojson"]
+        painted = np.array(Image.open(os.path.join(res, f"x_colorized_annotation_{i}.png")))
+        feats = json.loads(text)["features"]
+        assert len(feats) == len(ids) and len({f["properties"]["classification"]["name"] for f in feats}) > 1
+        for f, row in zip(feats, rows):
+            props = f["properties"]
+            assert props["name"] == row[0] and props["classification"]["name"] == row[1] and props["measurements"]["confidence"] == float(row[2])
+            ring = f["geometry"]["coordinates"][0] if f["geometry"]["type"] == "Polygon" else f["geometry"]["coordinates"][0][0]
+            c, r = ring[0]                     # an exterior ring's first vertex is the top-left corner of a pixel of the cell
+            assert runs["masks"][i][r, c] == int(row[0]) and painted[r, c].tolist() == props["classification"]["color"]
+    assert [r["annotated"] for r in a.outline_stats] == [True, True]
+
+
+def _fill(text, h, w):
+    """the id image of a GeoJSON text: every feature's rings filled by the even-odd rule, 0 where no feature lies"""
+    out = np.zeros((h, w), dtype=np.int64)
+    for f in json.loads(text)["features"]:
+        g = f["geometry"]
+        polys = [g["coordinates"]] if g["type"] == "Polygon" else g["coordinates"]
+        fill = np.zeros((h, w), dtype=bool)
+        for poly in polys:
+            for ring in poly:
+                for (c0, r0), (c1, r1) in zip(ring[:-1], ring[1:]):
+                    if c0 == c1:
+                        fill[min(r0, r1):max(r0, r1), c0:] ^= True
+        assert (out[fill] == 0).all() and fill.sum() == f["properties"]["measurements"]["area"]
+        out[fill] = f["properties"]["measurements"]["id"]
+    return out
+
+
+def test_with_repair_and_expansion_the_polygons_fill_the_mask_the_run_wrote(runs):
+    b = runs["b"]
+    res = os.path.join(runs["tmp"], "both", "results")
+    for i in range(2):
+        repaired = np.load(os.path.join(res, f"x_repaired_mask_{i}.npy"))
+        grown = np.load(os.path.join(res, f"x_expanded_mask_{i}.npy"))
+        assert (grown != repaired).any() and np.array_equal(b.preprocessor.masks_dev[i].cpu().numpy(), grown)
+        text = open(os.path.join(res, f"x_outlines_{i}.geojson")).read()
+        assert np.array_equal(_fill(text, *grown.shape), grown)
+        table, ids = ON.label_table(grown)
+        rings, first, vertices = ON.trace(grown, table, len(ids))
+        assert text == outlines.geojson(rings, first, vertices, ids)
+        assert open(os.path.join(res, f"x_outlines_{i}.csv")).read() == outlines.cells_csv(rings, ids)
+
+
+def test_outline_stats_and_the_log(runs):
+    a = runs["a"]
+    assert len(a.outline_stats) == 2 and len(runs["stats_before"]) == 2
+    for i, rec in enumerate(a.outline_stats):
+        ids, rings, first, vertices = runs["traced"][i]
+        want = outlines.image_stats(rings, len(ids))
+        assert {k: rec[k] for k in want} == want and rec["n"] == len(ids) and rec["rings"] == len(rings) and rec["vertices"] == int(first[-1])
+        assert rec["file"] == f"x_outlines_{i}.geojson" and rec["calls"] == 1 and rec["kernel_ms"] > 0.0 and rec["write_ms"] > 0.0
+        assert rec["longest_ring"] == int(rings[:, 3].max())
+    log = open(a.logger.log_file_path).read()
+    assert log.count("Cell outlines x_outlines_0.geojson: ") == 2 and log.count("Cell outlines x_outlines_1.geojson: ") == 2
+
+
+def test_a_run_without_the_call_writes_no_outline_file(runs):
+    res = os.path.join(runs["tmp"], "without", "results")
+    assert len(os.listdir(res)) > 4 and not [f for f in os.listdir(res) if "outline" in f]

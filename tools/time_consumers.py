@@ -25,7 +25,9 @@ ranks and for the median alone, the host features, and the numpy restatement of 
 events, mask, outputs and workspace on the device, and as the host yardstick scipy's distance_transform_edt(return_indices=True) on the same mask,
 whose composition at D = 8 is compared with the kernel's output (``--expand``: this section alone); and the repair of the mask
 (csrc/components.hip): the connected components of the same mask with 4000 injected faults, device events, the whole ops.repair_labels on the
-host clock, and scipy.ndimage.label of the same mask on the host (``--repair``: this section alone)."""
+host clock, and scipy.ndimage.label of the same mask on the host (``--repair``: this section alone); and the cell outlines
+(csrc/outlines.hip): ribca_mask_rings and ribca_mask_ring_vertices on the same mask, device events, the whole ops.mask_rings and the GeoJSON text
+on the host clock, and the restatement of tests/outlines_numpy.py on a crop, scaled by boundary edges (``--outlines``: this section alone)."""
 import os
 import sys
 import time
@@ -406,6 +408,93 @@ def time_repair():
           f"labels), {bg_ms:.0f} ms for the background at 4-connectivity; its {n_bg} background components are the kernel's: {n_bg == background}")
 
 
+# ---- the cell outlines (csrc/outlines.hip, outlines.py): rings of the mask, their vertices, polygons and GeoJSON ------------------------------------
+def time_outlines():
+    """mask, label table, outputs and workspace on the device before the clock starts: ribca_mask_rings and ribca_mask_ring_vertices each between
+    two device events, median of five calls after a warm-up (the vertices over the sorted rows of the rings call); the whole ops.mask_rings -- the
+    label table, both kernels, the sort, the prefix sum and the copies back -- and outlines.geojson / cells_csv on the host clock; then the
+    restatement of tests/outlines_numpy.py on a crop, checked against the GPU on the same crop and scaled by boundary edges.  scikit-image and
+    OpenCV, whose contour tracers a host pipeline would use, are not installed here: the restatement is the only host yardstick."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import outlines_numpy as ON
+    from multiplexed_image_annotator_amd import outlines
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    h, w = mask.shape
+    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
+    table[ids] = np.arange(n, dtype=np.int32)
+    tab_d = torch.from_numpy(table).to(dev)
+    cap = 2 * n + ops.OUTLINES_SPARE_ROWS
+    rings = torch.empty((cap, 6), dtype=torch.int64, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(ops.mask_rings_ws_bytes(h, w, n), 1), dtype=torch.uint8, device=dev)
+
+    def rings_call():
+        _lib.check(lib().ribca_mask_rings(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, cap, ptr(rings), ptr(total), ptr(ws), ws.numel(), stream_ptr()),
+                   "rings")
+
+    def events(call):
+        call()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            call()
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop))
+        return f"median {sorted(times)[2]:.3f} ms, min {min(times):.3f}, max {max(times):.3f} of 5 (device events)"
+
+    text = events(rings_call)
+    found = int(total.item())
+    rows = rings[:found]
+    rows = rows.index_select(0, torch.argsort(rows[:, 0] * ((h + 1) * (w + 1)) + rows[:, 1])).contiguous()
+    first = torch.zeros(found + 1, dtype=torch.int64, device=dev)
+    first[1:] = torch.cumsum(rows[:, 2], 0)
+    vertices = torch.empty((int(first[-1].item()), 2), dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    edges = int(rows[:, 3].sum().item())
+    floor = h * w * 4
+    print(f"mask rings (init + tiles + walkers): {text} for {h}x{w}, {n} cells; {found} rings, {int((rows[:, 4] < 0).sum())} of them holes, {edges} boundary "
+          f"edges, longest ring {int(rows[:, 3].max())} edges, {int(rows[:, 5].sum())} saddle passes; workspace {ws.numel() / 1e6:.0f} MB; one read of the "
+          f"mask, {floor / 1e9:.3f} GB at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: {1e3 * floor / HBM_BYTES_PER_S:.3f} ms")
+
+    def vertices_call():
+        _lib.check(lib().ribca_mask_ring_vertices(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, ptr(rows), found, ptr(first), ptr(vertices), ptr(bad),
+                                                  stream_ptr()), "ring vertices")
+
+    text = events(vertices_call)
+    print(f"mask ring vertices (one thread per ring): {text}; {vertices.shape[0]} vertices, bad = {int(bad.item())}")
+    ops.mask_rings(mask, ids)
+    times = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = ops.mask_rings(mask, ids)
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"ops.mask_rings, whole: median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} of 5 (host clock; it ends synchronised), "
+          f"{got['calls']} call(s) of the rings kernel")
+    t0 = time.perf_counter()
+    doc = outlines.geojson(got["rings"], got["first"], got["vertices"], ids)
+    t1 = time.perf_counter()
+    csv = outlines.cells_csv(got["rings"], ids)
+    print(f"outlines.geojson on the host, {n} cells: {1e3 * (t1 - t0):.0f} ms for {len(doc) / 1e6:.1f} MB of text; outlines.cells_csv: "
+          f"{1e3 * (time.perf_counter() - t1):.0f} ms for {len(csv) / 1e6:.1f} MB")
+    side = 512
+    crop = np.ascontiguousarray(mask[:side, :side].cpu().numpy())
+    t0 = time.perf_counter()
+    want = ON.trace(crop, table, n)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    g = ops.mask_rings(torch.from_numpy(crop).to(dev), ids)
+    same = all(np.array_equal(g[k], v) for k, v in zip(("rings", "first", "vertices"), want))
+    crop_edges = int(want[0][:, 3].sum())
+    print(f"numpy restatement, top-left {side}x{side} crop (host): {host_ms:.0f} ms for {crop_edges} boundary edges -> "
+          f"{host_ms * edges / max(crop_edges, 1) / 1e3:.1f} s scaled by boundary edges to {h}x{w}; equal to the GPU rings and vertices of the same crop: {same}")
+
+
+if "--outlines" in sys.argv:      # this section alone
+    time_outlines()
+    sys.exit(0)
 if "--repair" in sys.argv:      # this section alone
     time_repair()
     sys.exit(0)
@@ -626,3 +715,4 @@ time_intensities()
 # ---- growing the labels of the mask: defined above as well ------------------------------------------------------------------------------------------
 time_expand()
 time_repair()
+time_outlines()
