@@ -119,6 +119,16 @@ int ribca_test_cell_mlp(const uint16_t* xa, int32_t ldx, const uint16_t* projw, 
 int32_t ribca_test_cls_attention_cell_tile(void);
 int ribca_test_cls_attention(const uint16_t* z_ps, int32_t ld, const uint16_t* W, int32_t ldw, const float* bias2, const float* rowstat,
                              int32_t cells, int32_t D, float* g, float* ybar, uint16_t* out, int32_t ldo, void* stream);
+/* ribca_test_qkv_attention / ribca_test_qkv_attention_fold with the head count H and the token count T as parameters (M = cells * T rows):
+ * the imputer's geometries (D, H) = (768, 12) and (512, 8) with T = 2 .. 16 run the one-tile attention kernel, whose V operand is the
+ * transposed, key-permuted layout [cell][head][round16(hd)][2 * KP].  fold 0: a_or_z_ps = LayerNorm output rows, bias_or_bias2 = the bias,
+ * csum / rowstat unused; fold 1: the residual rows, bias2, csum and rowstat of fold_weight / row_stats.  q, k: cells * H * TP * 2 * round8(hd)
+ * uint16 (TP = T rounded up to 16), vt: ribca_test_attention_v_elems(D, H, T, cells) uint16 whose pad keys must be zero on entry.
+ * Non-zero return: NULL buffer, cells < 0, or no attention kernel for (D, H, T). */
+int ribca_test_qkv_attention_tokens(int32_t fold, const uint16_t* a_or_z_ps, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D, int32_t H,
+                                    int32_t T, int32_t Kp, const float* bias_or_bias2, const float* csum, const float* rowstat, uint16_t* q, uint16_t* k,
+                                    uint16_t* vt, uint16_t* out, int32_t ldo, void* stream);
+int64_t ribca_test_attention_v_elems(int32_t D, int32_t H, int32_t T, int32_t cells);
 int32_t ribca_gemm_padded_n(int32_t N);
 
 #pragma GCC visibility pop

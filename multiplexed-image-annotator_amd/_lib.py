@@ -187,6 +187,9 @@ TEST_SIGNATURES = {
     "ribca_test_cls_attention_cell_tile": (c_int32, []),
     "ribca_test_cls_attention": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                            c_int32, c_void_p]),
+    "ribca_test_qkv_attention_tokens": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "ribca_test_attention_v_elems": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ribca_gemm_padded_n": (c_int32, [c_int32]),
 }
 

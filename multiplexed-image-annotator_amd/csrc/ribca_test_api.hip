@@ -336,5 +336,32 @@ int ribca_test_qkv_attention(const uint16_t* A, int32_t lda, const uint16_t* W, 
   RIBCA_FINISH();
   return 0;
 }
+// qkv product + attention with the head count and the TOKEN COUNT as parameters: the imputer's geometries (768 / 12 and 512 / 8, T = 2 .. 16:
+// attention_kernel<64, 1>, V in the transposed key-permuted layout) besides the classifiers'.  fold 0: launch_gemm_qkv (a_or_z_ps = LayerNorm
+// output rows, bias_or_bias2 = the bias; csum / rowstat unused), fold 1: launch_gemm_qkv_ln (residual rows, bias2, csum, rowstat) -- each with the
+// arguments the blocks of ribca_mae_impute pass (no fragment-order weight: the two-workgroups form takes row-major V only).
+int64_t ribca_test_attention_v_elems(int32_t D, int32_t H, int32_t T, int32_t cells) {
+  if (table() == nullptr || H <= 0 || T <= 0 || cells < 0) return 0;
+  return (int64_t)attention_v_elems(make_attn_geom(D, H, T), cells);
+}
+int ribca_test_qkv_attention_tokens(int32_t fold, const uint16_t* a_or_z_ps, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D, int32_t H,
+                                    int32_t T, int32_t Kp, const float* bias_or_bias2, const float* csum, const float* rowstat, uint16_t* q, uint16_t* k,
+                                    uint16_t* vt, uint16_t* out, int32_t ldo, void* stream) {
+  RIBCA_NEED_TABLE();
+  if (fold != 0 && fold != 1) return fail("ribca_test_qkv_attention_tokens: fold must be 0 or 1");
+  if (cells < 0) return fail("ribca_test_qkv_attention_tokens: cells < 0");
+  if (!a_or_z_ps || !W || !bias_or_bias2 || !q || !k || !vt || !out || (fold && (!csum || !rowstat))) return fail("ribca_test_qkv_attention_tokens: NULL buffer");
+  if (H <= 0 || T <= 0 || D <= 0 || D % H != 0) return fail("ribca_test_qkv_attention_tokens: need H > 0, T > 0 and D a multiple of H");
+  const AttnGeom a = make_attn_geom(D, H, T);
+  if (!attention_supported(a)) return fail("ribca_test_qkv_attention_tokens: no attention kernel for this (D, H, T)");
+  hipStream_t s = (hipStream_t)stream;
+  const float scale = 1.0f / sqrtf((float)a.hd);
+  GemmArgs g{a_or_z_ps, lda, W, ldw, cells * T, 3 * D, Kp, bias_or_bias2};
+  if (fold) launch_gemm_qkv_ln(g, reinterpret_cast<const float2*>(rowstat), csum, q, k, vt, a, scale, s, 0, 0, 1);
+  else launch_gemm_qkv(g, q, k, vt, a, scale, s);
+  launch_attention(q, k, vt, out, ldo, cells, a, s, 0);
+  RIBCA_FINISH();
+  return 0;
+}
 
 }  // extern "C"
