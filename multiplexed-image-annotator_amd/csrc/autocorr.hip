@@ -1,10 +1,7 @@
 // Spatial autocorrelation of the markers (Annotator.spatial_autocorrelation; squidpy's spatial_autocorr): the numerators of Moran's I and Geary's C
 // of every channel over the fixed k-NN list of ribca_knn_neighbours, observed and under a permutation null in which whole rows of the (n, C) table
-// move with the keyed bijection sigma_p of ribca_perm.h.  include/ribca_hip.h states the arithmetic; tests/autocorr_numpy.py restates it.
-//   perm_rows    one workgroup per (chunk of AC_CHUNK cells, permutation of the batch): a thread per cell walks sigma, then the workgroup copies the
-//                chunk's rows, zp[j][i] = z[sigma_{p0 + j}(i)] -- one random row read per cell, coalesced writes -- into rows of L >= C doubles that
-//                never straddle a 128-byte line (row_ld).  The rows of a batch are sized to stay inside the Infinity Cache for the gathers that
-//                follow (AC_ROW_BYTES).
+// move with the keyed bijection sigma_p of ribca_perm.h, whose launch_perm_rows copies them.  include/ribca_hip.h states the arithmetic;
+// tests/autocorr_numpy.py restates it.  The rows of a batch are sized to stay inside the Infinity Cache for the gathers that follow (AC_ROW_BYTES).
 //   chunk_stats  one workgroup per (chunk, permutation, tile of AC_COLS channels).  The neighbour lists of the chunk go through LDS once.  The
 //                thread (g, c) owns channel c of the AC_LEAF consecutive cells [4 g, 4 g + 4) of the chunk: per cell it adds the neighbours in
 //                list order (the AC_COLS lanes of a cell read one 128-byte line of every neighbour's row), and its (a, g) pairs meet in the first
@@ -30,7 +27,7 @@ namespace {
 constexpr int AC_N_MAX = 1 << 30;
 constexpr int AC_C_MAX = 64;
 constexpr int AC_M_MAX = 31;
-constexpr int AC_CHUNK = 256;                 // cells of one chunk of THE tree: eight rounds of adjacent pairs
+constexpr int AC_CHUNK = kCellChunk;          // cells of one chunk of THE tree: eight rounds of adjacent pairs
 constexpr int AC_COLS = 16;                   // channels of one workgroup of chunk_stats
 constexpr int AC_LEAF_ROUNDS = 2;             // rounds of the tree one thread does in registers ...
 constexpr int AC_LEAF = 1 << AC_LEAF_ROUNDS;  // ... over this many consecutive cells
@@ -39,28 +36,13 @@ constexpr long long AC_ROW_BYTES = 64ll << 20;      // ... and the bytes of rows
 
 constexpr int AC_THREADS = AC_COLS * (AC_CHUNK / AC_LEAF);      // chunk_stats: one thread per (group of AC_LEAF cells, channel)
 
+static_assert(AC_CHUNK == 256, "eight rounds of adjacent pairs");
 static_assert(AC_THREADS <= 1024 && AC_THREADS % 64 == 0, "a workgroup of whole waves");
 static_assert(AC_CHUNK * AC_M_MAX * 4 + 2 * AC_THREADS * 8 <= 64 * 1024, "static LDS of chunk_stats_kernel: the lists of the chunk and the two trees");
 
 int fail(const char* msg) { return api_fail(msg); }
 
 struct Pair { double a, g; };
-
-// zp[j][i][0 .. C) = z[sigma_{p0 + j}(i)][:] in rows of ld doubles (+0.0 if the walk ever reported no cell): grid (chunks, batch)
-__global__ __launch_bounds__(256) void perm_rows_kernel(const double* __restrict__ z, int n, int C, int ld, int h, uint64_t image_key, uint64_t p0,
-                                                        double* __restrict__ zp) {
-  __shared__ uint32_t src[AC_CHUNK];
-  const int first = blockIdx.x * AC_CHUNK;
-  const int cells = min(AC_CHUNK, n - first);
-  if ((int)threadIdx.x < cells) src[threadIdx.x] = feistel_walk(perm_key(image_key, p0 + blockIdx.y), (uint32_t)(first + threadIdx.x), (uint32_t)n, h);
-  __syncthreads();
-  double* __restrict__ out = zp + ((size_t)blockIdx.y * n + first) * ld;
-  for (int e = threadIdx.x; e < cells * C; e += 256) {
-    const int cell = e / C, c = e % C;
-    const uint32_t s = src[cell];
-    out[cell * ld + c] = s < (uint32_t)n ? z[(size_t)s * C + c] : 0.0;
-  }
-}
 
 // the (a_i, g_i) of cell i and channel c over rows of ld doubles; idx: the lists of the cells from i0 on; a cell past the end of the table is the
 // +0.0 padding of its chunk
@@ -138,22 +120,8 @@ __global__ __launch_bounds__(AC_THREADS) void chunk_stats_kernel(const double* _
 
 bool sizes_ok(int n, int C) { return n >= 1 && n <= AC_N_MAX && C >= 1 && C <= AC_C_MAX; }
 
-int chunks_of_cells(int n) { return (n + AC_CHUNK - 1) / AC_CHUNK; }
-
-// L, the doubles from one copied row to the next: the power of two >= C up to 16, a multiple of 16 above, so that a row of up to 16 channels lies in
-// one 128-byte line and no tile of 16 channels straddles one (the padding is never written and never read)
-int row_ld(int C) {
-  if (C > 16) return (C + 15) / 16 * 16;
-  int ld = 1;
-  while (ld < C) ld *= 2;
-  return ld;
-}
-
 // B = min(P, 32, max(1, 64 MiB / (8 n L)))
-int perm_batch(int n, int C, int P) {
-  const long long by_bytes = std::max(1ll, AC_ROW_BYTES / (8ll * n * row_ld(C)));
-  return (int)std::min<long long>(std::min(P, AC_BATCH), by_bytes);
-}
+int batch_of(int n, int C, int P) { return perm_batch(P, AC_BATCH, 8ll * n * row_ld(C), AC_ROW_BYTES); }
 
 struct AutocorrWs {
   double* rows;      // (batch, n, L): the permuted rows; none for the observed statistic
@@ -204,7 +172,7 @@ int ribca_autocorr_observed(const double* z, const int32_t* idx, int32_t n, int3
 int64_t ribca_autocorr_perm_ws_bytes(int32_t n, int32_t C, int32_t P) {
   if (!sizes_ok(n, C) || P < 1) return 0;
   Carver cv(nullptr);
-  carve_autocorr(cv, n, C, perm_batch(n, C, P), true);
+  carve_autocorr(cv, n, C, batch_of(n, C, P), true);
   return (int64_t)cv.off;
 }
 
@@ -214,18 +182,17 @@ int ribca_autocorr_perm(const double* z, const int32_t* idx, int32_t n, int32_t 
   if (n < 1 || n > AC_N_MAX) return fail("ribca_autocorr_perm: needs 1 <= n <= 2^30");
   if (C < 1 || C > AC_C_MAX) return fail("ribca_autocorr_perm: needs 1 <= C <= 64");
   if (m < 1 || m > AC_M_MAX) return fail("ribca_autocorr_perm: needs 1 <= m <= 31");
-  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31)) return fail("ribca_autocorr_perm: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (perm_range_check("ribca_autocorr_perm", image, p0, P)) return 1;
   if (ws_bytes < ribca_autocorr_perm_ws_bytes(n, C, P)) return fail("ribca_autocorr_perm: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int B = perm_batch(n, C, P);
+  const int B = batch_of(n, C, P);
   Carver cv(ws);
   const AutocorrWs w = carve_autocorr(cv, n, C, B, true);
-  const int h = perm_half_bits(n), ld = row_ld(C);
-  const uint64_t image_key = perm_image_key(seed, image);
+  const int ld = row_ld(C);
+  const PermKeys k(n, seed, image);
   for (int64_t j0 = 0; j0 < P; j0 += B) {      // the batches follow one another on the stream: rows and partials are reused
     const int batch = (int)std::min<int64_t>(B, P - j0);
-    hipLaunchKernelGGL(perm_rows_kernel, dim3((unsigned)chunks_of_cells(n), (unsigned)batch), dim3(256), 0, s, z, n, C, ld, h, image_key,
-                       (uint64_t)(p0 + j0), w.rows);
+    launch_perm_rows(z, n, C, ld, k.h, k.image_key, (uint64_t)(p0 + j0), batch, w.rows, nullptr, s);
     launch_stats(w.rows, (size_t)n * ld, ld, idx, n, C, m, batch, w, out + (size_t)j0 * 2 * C, s);
   }
   RIBCA_FINISH();

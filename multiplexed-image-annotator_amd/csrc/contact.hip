@@ -14,7 +14,7 @@
 //                    keys whatever the arrival order, so it overflows exactly when its degree exceeds S.  No loop waits for another thread.
 //   contact_rows     one wave per row: the keys to LDS, every entry finds its rank among the row's keys (they are distinct) and goes to that
 //                    slot of the output; degree = the number of keys.  Slot positions depend on the arrival order, ranks and integer sums do not.
-//   edge_labels      the shuffled labels of a batch of permutations, one byte per cell (the rows of enrichment.hip, which stays as it is).
+//   the null         the shuffled labels of a batch of permutations are the byte rows of ribca_perm.h (launch_perm_labels).
 //   edge_count       one thread per directed edge of a slab, a [T][T] LDS histogram of at most 16 KiB, one 64-bit atomic per non-zero entry.
 // Measured forms: DESIGN.md section 19.
 #include <limits.h>
@@ -46,13 +46,13 @@ constexpr int EP_N_MAX = 1 << 30;
 constexpr int EP_BATCH = 128;                // permutations whose label rows the workspace holds at most
 constexpr long long EP_ROW_BYTES = 64ll << 20;      // ... and the bytes of them (one row when a single one is larger)
 constexpr int EP_SLAB = 4096;                // edges of one counting workgroup
-constexpr uint8_t EP_SKIP = 255;
 
 static_assert(1 << CT_HASH_BITS == CT_HASH, "the LDS table is indexed by the top bits of a 32-bit hash");
 static_assert(CT_TILE * CT_TILE % 256 == 0, "whole rounds of a 256-thread workgroup");
 static_assert(CT_SIDE * CT_SIDE * 4 + CT_HASH * 12 <= 32 * 1024, "LDS of contact_stencil");
 static_assert(CT_ROWS * CT_S_MAX * 4 <= 16 * 1024, "LDS of contact_rows");
 static_assert(EP_T_MAX * EP_T_MAX * 4 <= 16 * 1024, "the LDS histogram");
+static_assert(kPermSkip >= EP_T_MAX, "a skipped byte never indexes the histogram");
 
 int fail(const char* msg) { return api_fail(msg); }
 
@@ -206,20 +206,6 @@ __global__ __launch_bounds__(64 * CT_ROWS) void contact_rows_kernel(const int32_
   if (blockIdx.x == 0 && threadIdx.x == 0 && over[0] == 0) over[1] = -1;      // nobody else touches over in this launch
 }
 
-// labels[j][i] = (uint8) cell_type[sigma_{p0 + j}(i)], EP_SKIP where that is outside [0, T): grid (ceil(n / 256), batch)
-__global__ __launch_bounds__(256) void edge_labels_kernel(const int32_t* __restrict__ cell_type, int n, int T, int h, uint64_t image_key, uint64_t p0,
-                                                          uint8_t* __restrict__ labels) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t s = feistel_walk(perm_key(image_key, p0 + blockIdx.y), (uint32_t)i, (uint32_t)n, h);
-  uint8_t lab = EP_SKIP;
-  if (s < (uint32_t)n) {
-    const int32_t t = cell_type[s];
-    if ((unsigned)t < (unsigned)T) lab = (uint8_t)t;
-  }
-  labels[(size_t)blockIdx.y * n + i] = lab;
-}
-
 // counts[j][label(src[e])][label(dst[e])] += 1 over the slab's edges: grid (ceil(E / EP_SLAB), batch)
 __global__ __launch_bounds__(256) void edge_count_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ dst, long long E,
                                                          const uint8_t* __restrict__ labels, int n, int T, unsigned long long* __restrict__ counts) {
@@ -267,9 +253,6 @@ ContactWs carve_contact(Carver& cv, int n, int S) {
   return w;
 }
 
-// B = min(P, 128, max(1, 64 MiB / n))
-int edge_batch(int n, int P) { return (int)std::min<long long>(std::min(P, EP_BATCH), std::max(1ll, EP_ROW_BYTES / n)); }
-
 bool edge_sizes_ok(int n, int P) { return n >= 1 && n <= EP_N_MAX && P >= 1; }
 
 }  // namespace
@@ -313,7 +296,7 @@ int ribca_contact_table(const int32_t* mask, int32_t H, int32_t W, const int32_t
 int64_t ribca_edge_perm_counts_ws_bytes(int32_t n, int32_t P) {
   if (!edge_sizes_ok(n, P)) return 0;
   Carver cv(nullptr);
-  cv.take<uint8_t>((size_t)edge_batch(n, P) * (size_t)n);
+  cv.take<uint8_t>((size_t)perm_batch(P, EP_BATCH, n, EP_ROW_BYTES) * (size_t)n);
   return (int64_t)cv.off;
 }
 
@@ -323,19 +306,17 @@ int ribca_edge_perm_counts(const int32_t* src, const int32_t* dst, int64_t E, co
   if (E < 1 || E >= (1ll << 31)) return fail("ribca_edge_perm_counts: needs 1 <= E < 2^31");
   if (n < 1 || n > EP_N_MAX) return fail("ribca_edge_perm_counts: needs 1 <= n <= 2^30");
   if (T < 1 || T > EP_T_MAX) return fail("ribca_edge_perm_counts: needs 1 <= T <= 64");
-  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31)) return fail("ribca_edge_perm_counts: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (perm_range_check("ribca_edge_perm_counts", image, p0, P)) return 1;
   if (ws_bytes < ribca_edge_perm_counts_ws_bytes(n, P)) return fail("ribca_edge_perm_counts: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int batch_max = edge_batch(n, P);
+  const int batch_max = perm_batch(P, EP_BATCH, n, EP_ROW_BYTES);
   Carver cv(ws);
   uint8_t* labels = cv.take<uint8_t>((size_t)batch_max * (size_t)n);
-  const int h = perm_half_bits(n);
-  const uint64_t image_key = perm_image_key(seed, image);
+  const PermKeys k(n, seed, image);
   unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
   for (int64_t j0 = 0; j0 < P; j0 += batch_max) {      // the batches follow one another on the stream: the label rows are reused
     const int batch = (int)std::min<int64_t>(batch_max, P - j0);
-    hipLaunchKernelGGL(edge_labels_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, s, cell_type, n, T, h, image_key,
-                       (uint64_t)(p0 + j0), labels);
+    launch_perm_labels(cell_type, n, T, k.h, k.image_key, (uint64_t)(p0 + j0), batch, labels, s);
     hipLaunchKernelGGL(edge_count_kernel, dim3((unsigned)((E + EP_SLAB - 1) / EP_SLAB), (unsigned)batch), dim3(256), 0, s, src, dst, (long long)E,
                        labels, n, T, out + (size_t)j0 * T * T);
   }

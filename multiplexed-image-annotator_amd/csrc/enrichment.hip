@@ -1,12 +1,9 @@
 // The permutation null of the neighbourhood co-occurrence counts (Annotator.neighborhood_enrichment; histoCAT / squidpy's nhood_enrichment): the
 // k-NN graph of ribca_knn_neighbours stays fixed, the cell-type labels are shuffled within the image P times and the type pairs recounted.
-//   sigma_p          the keyed bijection of [0, n) of ribca_perm.h (include/ribca_hip.h states it; tests/enrichment_numpy.py restates it).
-//   perm_labels      one thread per (cell, permutation of the batch): row j of the workspace = the n shuffled labels as bytes (255 = a label
-//                    outside [0, T): skipped later).  A row of 1e5 cells is 100 KB and stays in L2 for the gathers that follow.
+// sigma_p and the byte rows of shuffled labels (launch_perm_labels; kPermSkip = a label outside [0, T): skipped here) are ribca_perm.h's.
 //   perm_count       one workgroup per (slab of EN_SLAB cells, permutation): each thread reads its cell's byte, gathers the bytes of its m neighbours
 //                    and counts the pairs into a T x T LDS histogram (<= 16 KiB) with integer atomics; then one 64-bit global atomic per non-zero
 //                    entry.  Integer sums: the result is independent of the order and of the launch geometry.
-// Evaluating sigma for every neighbour instead of once per cell would cost m + 1 times the hashing; the byte rows cost n bytes per permutation.
 #include <algorithm>
 
 #include "../../include/ribca_hip.h"
@@ -23,27 +20,12 @@ constexpr int EN_T_MAX = 64;
 constexpr int EN_N_MAX = 1 << 30;
 constexpr int EN_BATCH = 128;        // permutations whose label rows the workspace holds at once (gridDim.y of both kernels)
 constexpr int EN_SLAB = 4096;        // cells of one counting workgroup: 16 per thread, so a flush of T * T entries is paid once per 4096 * m counts
-constexpr uint8_t EN_SKIP = 255;     // no label: never indexes the histogram (T <= 64)
 
 static_assert(EN_T_MAX * EN_T_MAX * 4 <= 16 * 1024, "the LDS histogram");
+static_assert(kPermSkip >= EN_T_MAX, "a skipped byte never indexes the histogram");
 static_assert((long long)EN_SLAB * EN_M_MAX < (1ll << 32), "a 32-bit LDS count cannot wrap within one slab");
 
 int fail(const char* msg) { return api_fail(msg); }
-
-// labels[j][i] = (uint8) cell_type[sigma_{p0 + j}(i)], EN_SKIP where that is outside [0, T): grid (ceil(n / 256), batch)
-__global__ __launch_bounds__(256) void perm_labels_kernel(const int32_t* __restrict__ cell_type, int n, int T, int h, uint64_t image_key, uint64_t p0,
-                                                          uint8_t* __restrict__ labels) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t key = perm_key(image_key, p0 + blockIdx.y);
-  const uint32_t src = feistel_walk(key, (uint32_t)i, (uint32_t)n, h);
-  uint8_t lab = EN_SKIP;
-  if (src < (uint32_t)n) {
-    const int32_t t = cell_type[src];
-    if ((unsigned)t < (unsigned)T) lab = (uint8_t)t;
-  }
-  labels[(size_t)blockIdx.y * n + i] = lab;
-}
 
 // counts[j][a][b] += the pairs (label(i), label(idx[i][q])) of the slab's cells: grid (ceil(n / EN_SLAB), batch)
 __global__ __launch_bounds__(256) void perm_count_kernel(const int32_t* __restrict__ idx, const uint8_t* __restrict__ labels, int n, int m, int T,
@@ -75,7 +57,7 @@ __global__ __launch_bounds__(256) void perm_count_kernel(const int32_t* __restri
 
 bool perm_sizes_ok(int n, int P) { return n >= 1 && n <= EN_N_MAX && P >= 1; }
 
-uint8_t* carve_perm(Carver& cv, int n, int P) { return cv.take<uint8_t>((size_t)std::min(P, EN_BATCH) * (size_t)n); }
+uint8_t* carve_perm(Carver& cv, int n, int P) { return cv.take<uint8_t>((size_t)perm_batch(P, EN_BATCH) * (size_t)n); }
 
 }  // namespace
 }  // namespace ribca
@@ -97,18 +79,16 @@ int ribca_nhood_perm_counts(const int32_t* idx, const int32_t* cell_type, int32_
   if (n < 1 || n > EN_N_MAX) return fail("ribca_nhood_perm_counts: needs 1 <= n <= 2^30");
   if (m < 1 || m > EN_M_MAX) return fail("ribca_nhood_perm_counts: needs 1 <= m <= 31");
   if (T < 1 || T > EN_T_MAX) return fail("ribca_nhood_perm_counts: needs 1 <= T <= 64");
-  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31)) return fail("ribca_nhood_perm_counts: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (perm_range_check("ribca_nhood_perm_counts", image, p0, P)) return 1;
   if (ws_bytes < ribca_nhood_perm_counts_ws_bytes(n, P)) return fail("ribca_nhood_perm_counts: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   Carver cv(ws);
   uint8_t* labels = carve_perm(cv, n, P);
-  const int h = perm_half_bits(n);
-  const uint64_t image_key = perm_image_key(seed, image);
+  const PermKeys k(n, seed, image);
   unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
   for (int64_t j0 = 0; j0 < P; j0 += EN_BATCH) {      // the batches follow one another on the stream: the label rows are reused
     const int batch = (int)std::min<int64_t>(EN_BATCH, P - j0);
-    hipLaunchKernelGGL(perm_labels_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, s, cell_type, n, T, h, image_key,
-                       (uint64_t)(p0 + j0), labels);
+    launch_perm_labels(cell_type, n, T, k.h, k.image_key, (uint64_t)(p0 + j0), batch, labels, s);
     hipLaunchKernelGGL(perm_count_kernel, dim3((unsigned)((n + EN_SLAB - 1) / EN_SLAB), (unsigned)batch), dim3(256), 0, s, idx, labels, n, m, T,
                        out + (size_t)j0 * T * T);
   }

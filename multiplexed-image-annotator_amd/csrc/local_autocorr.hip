@@ -4,10 +4,8 @@
 // One pair of counts serves local Moran's I and Getis-Ord Gi*: with z_i fixed the lag is their only random part.  include/ribca_hip.h states the
 // arithmetic; tests/local_autocorr_numpy.py restates it.
 //   local_lag    one thread per (cell, channel): the neighbours added in list order.
-//   perm_rows    as in autocorr.hip (restated here: that file's kernels are pinned by its tests): zp[b][i] = z[sigma_{p0 + b}(i)] in rows of L
-//                doubles that never straddle a 128-byte line, and beside them the INVERSE, inv[b][sigma(i)] = i -- a scatter of one int32 per
-//                cell.  With it "sigma(j) == i" is "j == inv[i]": the counting thread reads one coalesced word per permutation and no
-//                source index per neighbour.
+//   perm_rows    launch_perm_rows of ribca_perm.h with the INVERSE beside the rows, inv[b][sigma(i)] = i.  With it "sigma(j) == i" is
+//                "j == inv[i]": the counting thread reads one coalesced word per permutation and no source index per neighbour.
 //   perm_counts  one workgroup per (chunk of LA_CHUNK cells, tile of LA_COLS channels); the chunk's lists go through LDS once.  The thread (g, c)
 //                owns channel c of LA_LEAF consecutive cells with z_i, lag_i and the two counters of each in registers; per permutation of the
 //                batch and per cell it adds the neighbours in list order -- the cell's own value for j == i, zp[i] for j == inv[i], zp[j]
@@ -31,7 +29,7 @@ namespace {
 constexpr int LA_N_MAX = 1 << 30;
 constexpr int LA_C_MAX = 64;
 constexpr int LA_M_MAX = 31;
-constexpr int LA_CHUNK = 256;                 // cells of one workgroup of perm_counts (and of perm_rows)
+constexpr int LA_CHUNK = kCellChunk;          // cells of one workgroup of perm_counts
 constexpr int LA_COLS = 16;                   // channels of one workgroup of perm_counts: one 128-byte line of a copied row
 constexpr int LA_LEAF = 4;                    // consecutive cells one thread owns
 constexpr int LA_BATCH = 32;                  // permutations whose rows the workspace holds at most
@@ -56,27 +54,6 @@ __global__ __launch_bounds__(256) void local_lag_kernel(const double* __restrict
     if ((unsigned)j < (unsigned)n) s = s + z[(size_t)j * C + c];
   }
   lag[e] = s;
-}
-
-// zp[b][i][0 .. C) = z[sigma_{p0 + b}(i)][:] in rows of ld doubles and inv[b][sigma_{p0 + b}(i)] = i: grid (chunks, batch).  sigma is a bijection of
-// [0, n), so every word of inv has exactly one writer; a walk that reported no cell (it cannot) leaves a +0.0 row and writes no word.
-__global__ __launch_bounds__(256) void local_perm_rows_kernel(const double* __restrict__ z, int n, int C, int ld, int h, uint64_t image_key, uint64_t p0,
-                                                              double* __restrict__ zp, int32_t* __restrict__ inv) {
-  __shared__ uint32_t src[LA_CHUNK];
-  const int first = blockIdx.x * LA_CHUNK;
-  const int cells = min(LA_CHUNK, n - first);
-  if ((int)threadIdx.x < cells) {
-    const uint32_t s = feistel_walk(perm_key(image_key, p0 + blockIdx.y), (uint32_t)(first + threadIdx.x), (uint32_t)n, h);
-    src[threadIdx.x] = s;
-    if (s < (uint32_t)n) inv[(size_t)blockIdx.y * n + s] = first + (int)threadIdx.x;
-  }
-  __syncthreads();
-  double* __restrict__ out = zp + ((size_t)blockIdx.y * n + first) * ld;
-  for (int e = threadIdx.x; e < cells * C; e += 256) {
-    const int cell = e / C, c = e % C;
-    const uint32_t s = src[cell];
-    out[cell * ld + c] = s < (uint32_t)n ? z[(size_t)s * C + c] : 0.0;
-  }
 }
 
 // ge[i][c] += the permutations b of the batch with s_b[i][c] >= lag[i][c], le likewise with <=: grid (chunks, channel tiles)
@@ -143,21 +120,8 @@ __global__ __launch_bounds__(LA_THREADS) void local_perm_counts_kernel(const dou
 
 bool sizes_ok(int n, int C) { return n >= 1 && n <= LA_N_MAX && C >= 1 && C <= LA_C_MAX; }
 
-int chunks_of_cells(int n) { return (n + LA_CHUNK - 1) / LA_CHUNK; }
-
-// L, the doubles from one copied row to the next: the rule of ribca_autocorr_perm
-int row_ld(int C) {
-  if (C > 16) return (C + 15) / 16 * 16;
-  int ld = 1;
-  while (ld < C) ld *= 2;
-  return ld;
-}
-
 // B = min(P, 32, max(1, 64 MiB / (8 n L)))
-int perm_batch(int n, int C, int P) {
-  const long long by_bytes = std::max(1ll, LA_ROW_BYTES / (8ll * n * row_ld(C)));
-  return (int)std::min<long long>(std::min(P, LA_BATCH), by_bytes);
-}
+int batch_of(int n, int C, int P) { return perm_batch(P, LA_BATCH, 8ll * n * row_ld(C), LA_ROW_BYTES); }
 
 struct LocalWs {
   double* rows;      // (batch, n, L): the permuted rows
@@ -192,7 +156,7 @@ int ribca_local_lag(const double* z, const int32_t* idx, int32_t n, int32_t C, i
 int64_t ribca_local_perm_counts_ws_bytes(int32_t n, int32_t C, int32_t P) {
   if (!sizes_ok(n, C) || P < 1) return 0;
   Carver cv(nullptr);
-  carve_local(cv, n, C, perm_batch(n, C, P));
+  carve_local(cv, n, C, batch_of(n, C, P));
   return (int64_t)cv.off;
 }
 
@@ -202,21 +166,19 @@ int ribca_local_perm_counts(const double* z, const int32_t* idx, const double* l
   if (n < 1 || n > LA_N_MAX) return fail("ribca_local_perm_counts: needs 1 <= n <= 2^30");
   if (C < 1 || C > LA_C_MAX) return fail("ribca_local_perm_counts: needs 1 <= C <= 64");
   if (m < 1 || m > LA_M_MAX) return fail("ribca_local_perm_counts: needs 1 <= m <= 31");
-  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31))
-    return fail("ribca_local_perm_counts: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (perm_range_check("ribca_local_perm_counts", image, p0, P)) return 1;
   if (ws_bytes < ribca_local_perm_counts_ws_bytes(n, C, P)) return fail("ribca_local_perm_counts: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int B = perm_batch(n, C, P);
+  const int B = batch_of(n, C, P);
   Carver cv(ws);
   const LocalWs w = carve_local(cv, n, C, B);
-  const int h = perm_half_bits(n), ld = row_ld(C), chunks = chunks_of_cells(n);
-  const uint64_t image_key = perm_image_key(seed, image);
+  const int ld = row_ld(C), chunks = chunks_of_cells(n);
+  const PermKeys k(n, seed, image);
   HIP_TRY(hipMemsetAsync(ge, 0, (size_t)n * C * sizeof(uint32_t), s));      // OVERWRITTEN: the batches add to zero
   HIP_TRY(hipMemsetAsync(le, 0, (size_t)n * C * sizeof(uint32_t), s));
   for (int64_t j0 = 0; j0 < P; j0 += B) {      // the batches follow one another on the stream: rows, inverse and the counts' owners are reused
     const int batch = (int)std::min<int64_t>(B, P - j0);
-    hipLaunchKernelGGL(local_perm_rows_kernel, dim3((unsigned)chunks, (unsigned)batch), dim3(256), 0, s, z, n, C, ld, h, image_key,
-                       (uint64_t)(p0 + j0), w.rows, w.inv);
+    launch_perm_rows(z, n, C, ld, k.h, k.image_key, (uint64_t)(p0 + j0), batch, w.rows, w.inv, s);
     hipLaunchKernelGGL(local_perm_counts_kernel, dim3((unsigned)chunks, (unsigned)((C + LA_COLS - 1) / LA_COLS)), dim3(LA_THREADS), 0, s, z, lag, idx,
                        w.rows, w.inv, n, C, ld, m, batch, ge, le);
   }

@@ -18,7 +18,7 @@
 //                 its slot lies in.  No (n, T) table: the minimum finds its band by the branch-free search of cooccurrence.hip and is counted
 //                 into an LDS histogram [B][T] -- the target type is the workgroup's, so B T <= 2048 counters always fit -- flushed with one
 //                 64-bit integer atomic per non-zero entry.  Integer atomics only.
-// Permutations are batched through the workspace as local_autocorr.hip batches them.  Measured forms: DESIGN.md section 18.
+// Permutations are batched through the workspace by the rule of ribca_perm.h.  Measured forms: DESIGN.md section 18.
 #include <math.h>
 
 #include <algorithm>
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void nearest_perm_scatter_kernel(const double*
                                                                    double2* __restrict__ pxy) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint32_t s = feistel_walk(perm_key(image_key, p0 + blockIdx.y), (uint32_t)i, (uint32_t)n, h);
+  const uint32_t s = perm_sigma(image_key, p0 + blockIdx.y, (uint32_t)i, (uint32_t)n, h);
   if (s < (uint32_t)n) pxy[(size_t)blockIdx.y * n + rank[s]] = make_double2(x[i], y[i]);
 }
 
@@ -218,10 +218,7 @@ __global__ __launch_bounds__(256) void nearest_perm_counts_kernel(const double2*
 int sort_chunks(int n) { return (n + NR_SORT - 1) / NR_SORT; }
 
 // B = min(P, 32, max(1, 64 MiB / (16 n)))
-int perm_batch(int n, int P) {
-  const long long by_bytes = std::max(1ll, NR_COPY_BYTES / (16ll * n));
-  return (int)std::min<long long>(std::min(P, NR_BATCH), by_bytes);
-}
+int batch_of(int n, int P) { return perm_batch(P, NR_BATCH, 16ll * n, NR_COPY_BYTES); }
 
 struct NearestWs {
   int32_t* hist;         // (chunks, NR_BINS): the counting sort
@@ -283,7 +280,7 @@ int ribca_nearest_by_type(const double* x, const double* y, const int32_t* cell_
 int64_t ribca_nearest_perm_counts_ws_bytes(int32_t n, int32_t T, int32_t P) {
   if (n < 1 || n > NR_N_MAX || T < 1 || T > NR_T_PERM || P < 1) return 0;
   Carver cv(nullptr);
-  carve_nearest(cv, n, T, perm_batch(n, P));
+  carve_nearest(cv, n, T, batch_of(n, P));
   return (int64_t)cv.off;
 }
 
@@ -301,20 +298,19 @@ int ribca_nearest_perm_counts(const double* x, const double* y, const int32_t* c
       return fail("ribca_nearest_perm_counts: the squared radii must be finite, non-negative and strictly increasing");
     edges.r2[b] = r;
   }
-  if (image < 0 || p0 < 0 || P < 1 || p0 + (int64_t)P > (1ll << 31))
-    return fail("ribca_nearest_perm_counts: needs image >= 0, p0 >= 0, 1 <= P, p0 + P <= 2^31");
+  if (perm_range_check("ribca_nearest_perm_counts", image, p0, P)) return 1;
   if (ws_bytes < ribca_nearest_perm_counts_ws_bytes(n, T, P)) return fail("ribca_nearest_perm_counts: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int batch_max = perm_batch(n, P);
+  const int batch_max = batch_of(n, P);
   Carver cv(ws);
   const NearestWs w = carve_nearest(cv, n, T, batch_max);
   launch_sort(x, y, cell_type, n, T, w, false, s);
-  const int h = perm_half_bits(n), chunks = (n + 255) / 256;
-  const uint64_t image_key = perm_image_key(seed, image);
+  const int chunks = (n + 255) / 256;
+  const PermKeys k(n, seed, image);
   unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
   for (int64_t j0 = 0; j0 < P; j0 += batch_max) {      // the batches follow one another on the stream: the copies are reused
     const int batch = (int)std::min<int64_t>(batch_max, P - j0);
-    hipLaunchKernelGGL(nearest_perm_scatter_kernel, dim3((unsigned)chunks, (unsigned)batch), dim3(256), 0, s, x, y, w.rank, n, h, image_key,
+    hipLaunchKernelGGL(nearest_perm_scatter_kernel, dim3((unsigned)chunks, (unsigned)batch), dim3(256), 0, s, x, y, w.rank, n, k.h, k.image_key,
                        (uint64_t)(p0 + j0), w.xy);
     hipLaunchKernelGGL(nearest_perm_counts_kernel, dim3((unsigned)chunks, (unsigned)T, (unsigned)batch), dim3(256), 0, s, w.xy, w.seg, w.slot_bin, n,
                        T, B, edges, out + (size_t)j0 * B * T * T);

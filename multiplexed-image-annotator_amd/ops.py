@@ -71,10 +71,67 @@ def workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
     return cur
 
 
+def _workspace_ptr(nbytes: int, device, slot: int = 0) -> int:
+    """the address of ``nbytes`` on a 256-byte boundary inside the (device, slot) workspace, which keeps the memory alive"""
+    return (workspace(nbytes + 256, device, slot).data_ptr() + 255) & ~255
+
+
 def _scratch(nbytes: int, device) -> torch.Tensor:
     """The ``ws is None`` default of a wrapper: what the library's own ``*_ws_bytes`` query asks for.  Never empty, so that arguments the
     library refuses (query = 0) reach its range message and not its NULL check."""
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _ws(ws: Optional[torch.Tensor], nbytes: int, device, who: str) -> torch.Tensor:
+    """A wrapper's ``ws`` argument: ``_scratch(nbytes)`` for None, else the caller's buffer once it is what the library is handed -- bytes,
+    contiguous, on ``device`` (its size is the library's to refuse)."""
+    if ws is None:
+        return _scratch(nbytes, device)
+    if ws.dtype != torch.uint8 or ws.device != device or not ws.is_contiguous():
+        raise ValueError(f"{who}: ws must be a contiguous uint8 tensor on the device of its inputs")
+    return ws
+
+
+def _u64(seed: int) -> int:
+    """a Python int as the uint64_t seed of the ABI: wrapped, not refused"""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _cell_table(ids, device=None):
+    """The label -> cell table of the ascending mask labels ``ids`` (cell i = ids[i]) as int32 [max label + 1], -1 for a label that is no cell;
+    label 0 is never one (the background; colorize paints labels > 0 only).  One entry, -1, for no ids.  On ``device``; the numpy array for None."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    table = np.full(int(ids.max()) + 1 if len(ids) else 1, -1, dtype=np.int32)
+    table[ids] = np.arange(len(ids), dtype=np.int32)
+    table[0] = -1
+    return table if device is None else torch.from_numpy(table).to(device)
+
+
+def _points(x, y, cell_type, device, who: str):
+    """(x, y, labels) on the device as fp64, fp64 and int32 -- labels None for ``cell_type`` None -- after the check that they are n coordinates
+    and n labels: the kernels read all three at every index below n"""
+    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(device)
+    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(device)
+    td = None if cell_type is None else torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(device)
+    if xd.dim() != 1 or yd.shape != xd.shape or (td is not None and td.shape != xd.shape):
+        shapes = ", ".join(str(tuple(t.shape)) for t in (xd, yd, td) if t is not None)
+        raise ValueError(f"{who} takes n coordinates" + (" and n labels" if td is not None else "") + f", got {shapes}")
+    return xd, yd, td
+
+
+def _radii2(radii) -> np.ndarray:
+    """the radii squared once in fp64, a contiguous 1-D array: what the kernels compare fp64 squared distances with"""
+    r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    return np.ascontiguousarray(r * r)
+
+
+def _counts_out(out: Optional[torch.Tensor], shape, device, who: str) -> torch.Tensor:
+    """the ``out`` of an accumulating counter: zeros of ``shape`` for None, else the caller's tensor once it is what the kernel adds into"""
+    if out is None:
+        return torch.zeros(shape, dtype=torch.int64, device=device)
+    if out.dtype != torch.int64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{who}: out must be a contiguous int64 tensor of shape {tuple(shape)} on the device of its inputs")
+    return out
 
 
 # ------------------------------------------------------------------------------------------- pre-processing
@@ -217,10 +274,7 @@ def colorize(mask: torch.Tensor, ids: np.ndarray, type_rgb: np.ndarray, conf_rgb
     assert type_rgb.shape == (n, 3) and conf_rgb.shape == (n, 3) and type_idx.shape == (n,)
     h, w = mask.shape
     dev = mask.device
-    top = int(ids.max()) + 1 if n else 1
-    table = np.full(top, -1, dtype=np.int32)
-    table[np.asarray(ids, dtype=np.int64)] = np.arange(n, dtype=np.int32)
-    tab_d = torch.from_numpy(table).to(dev)
+    tab_d = _cell_table(ids, dev)
     a = torch.from_numpy(np.ascontiguousarray(type_rgb, dtype=np.uint8)).to(dev) if n else torch.zeros((1, 3), dtype=torch.uint8, device=dev)
     b = torch.from_numpy(np.ascontiguousarray(conf_rgb, dtype=np.uint8)).to(dev) if n else torch.zeros((1, 3), dtype=torch.uint8, device=dev)
     c = torch.from_numpy(np.ascontiguousarray(type_idx, dtype=np.uint8)).to(dev) if n else torch.zeros((1,), dtype=torch.uint8, device=dev)
@@ -228,7 +282,7 @@ def colorize(mask: torch.Tensor, ids: np.ndarray, type_rgb: np.ndarray, conf_rgb
     out_c = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
     out_i = torch.empty((h, w), dtype=torch.uint8, device=dev)
     mask_c = mask.contiguous()
-    check(lib().ribca_colorize(ptr(mask_c), h * w, ptr(tab_d), top, ptr(a), ptr(b), ptr(c), ptr(out_t), ptr(out_c), ptr(out_i),
+    check(lib().ribca_colorize(ptr(mask_c), h * w, ptr(tab_d), tab_d.numel(), ptr(a), ptr(b), ptr(c), ptr(out_t), ptr(out_c), ptr(out_i),
                                stream_ptr()), "ribca_colorize")
     return out_t, out_c, out_i
 
@@ -241,11 +295,8 @@ def knn_cooccurrence(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_type
     n = len(x)
     if n_neighbors > n:      # what scikit-learn's kneighbors raises inside the reference
         raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {n_neighbors}, n_samples_fit = {n}")
-    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
-    td = torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(dev)
-    if out is None:
-        out = torch.zeros((n_types, n_types), dtype=torch.int64, device=dev)
+    xd, yd, td = _points(x, y, cell_type, dev, "knn_cooccurrence")
+    out = _counts_out(out, (int(n_types), int(n_types)), xd.device, "knn_cooccurrence")
     check(lib().ribca_knn_cooccurrence(ptr(xd), ptr(yd), ptr(td), n, int(n_neighbors), int(n_types), ptr(out), stream_ptr()),
           "ribca_knn_cooccurrence")
     return out
@@ -258,8 +309,7 @@ def knn_neighbours(x: np.ndarray, y: np.ndarray, n_neighbors: int, device=None) 
     n = len(x)
     if n_neighbors > n:
         raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {n_neighbors}, n_samples_fit = {n}")
-    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
+    xd, yd, _ = _points(x, y, None, dev, "knn_neighbours")
     idx = torch.empty((n, max(int(n_neighbors) - 1, 0)), dtype=torch.int32, device=dev)
     check(lib().ribca_knn_neighbours(ptr(xd), ptr(yd), n, int(n_neighbors), ptr(idx), stream_ptr()), "ribca_knn_neighbours")
     return idx
@@ -289,16 +339,10 @@ def nhood_perm_counts(idx: torch.Tensor, cell_type: np.ndarray, n_types: int, se
     idx = idx.contiguous()
     td = torch.from_numpy(labels).to(idx.device)
     shape = (max(int(n_perms), 0), max(int(n_types), 0), max(int(n_types), 0))
-    if out is None:
-        out = torch.zeros(shape, dtype=torch.int64, device=idx.device)
-    elif out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != idx.device:
-        raise ValueError(f"nhood_perm_counts: out must be an int64 tensor of shape {shape} on the device of idx")
-    if ws is None:
-        ws = _scratch(nhood_perm_counts_ws_bytes(n, n_perms), idx.device)
-    elif ws.dtype != torch.uint8 or ws.device != idx.device or not ws.is_contiguous():
-        raise ValueError("nhood_perm_counts: ws must be a contiguous uint8 tensor on the device of idx")
-    check(lib().ribca_nhood_perm_counts(ptr(idx), ptr(td), n, m, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0), int(n_perms), ptr(out),
-                                        ptr(ws), ws.numel(), stream_ptr()), "ribca_nhood_perm_counts")
+    out = _counts_out(out, shape, idx.device, "nhood_perm_counts")
+    ws = _ws(ws, nhood_perm_counts_ws_bytes(n, n_perms), idx.device, "nhood_perm_counts")
+    check(lib().ribca_nhood_perm_counts(ptr(idx), ptr(td), n, m, int(n_types), _u64(seed), int(image), int(p0), int(n_perms), ptr(out), ptr(ws),
+                                        ws.numel(), stream_ptr()), "ribca_nhood_perm_counts")
     return out
 
 
@@ -317,17 +361,10 @@ def radial_pair_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_ty
     ``radii`` in pixels, finite, non-negative and strictly increasing, at most RADIAL_MAX_BANDS of them; they are squared once in fp64 here and
     the kernel compares fp64 squared distances with them.  Accumulates into ``out`` when given (the images of a group)."""
     dev = device or _lib.require_gpu()
-    n = len(x)
-    r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
-    r2 = np.ascontiguousarray(r * r)
-    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
-    td = torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(dev)
-    shape = (len(r2), max(int(n_types), 0), max(int(n_types), 0))
-    if out is None:
-        out = torch.zeros(shape, dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"radial_pair_counts: out must be a contiguous int64 tensor of shape {shape}")
+    xd, yd, td = _points(x, y, cell_type, dev, "radial_pair_counts")
+    n = xd.numel()
+    r2 = _radii2(radii)
+    out = _counts_out(out, (len(r2), max(int(n_types), 0), max(int(n_types), 0)), xd.device, "radial_pair_counts")
     ws = _scratch(radial_pair_counts_ws_bytes(n, n_types, len(r2)), dev)
     check(lib().ribca_radial_pair_counts(ptr(xd), ptr(yd), ptr(td), n, int(n_types), r2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(r2),
                                          ptr(out), ptr(ws), ws.numel(), stream_ptr()), "ribca_radial_pair_counts")
@@ -347,27 +384,17 @@ def nearest_perm_counts_ws_bytes(n: int, n_types: int, n_perms: int) -> int:
     return int(lib().ribca_nearest_perm_counts_ws_bytes(int(n), int(n_types), int(n_perms)))
 
 
-def _nearest_inputs(x, y, cell_type, dev):
-    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
-    td = torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(dev)
-    if xd.dim() != 1 or yd.shape != xd.shape or td.shape != xd.shape:
-        raise ValueError(f"the nearest-cell search takes n coordinates and n labels, got {tuple(xd.shape)}, {tuple(yd.shape)}, {tuple(td.shape)}")
-    return xd, yd, td
-
-
 def nearest_by_type(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_types: int, ws: Optional[torch.Tensor] = None,
                     device=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(near2, arg): (n, n_types) fp64 and int32 device tensors, per cell and cell type the squared distance to the nearest OTHER cell of that
     type (+inf where there is none) and the lowest index that attains it (-1 where there is none); a label outside [0, n_types) is never a
     target, its cell still has a row.  fp64 brute force, csrc/nearest.hip; include/ribca_hip.h states every comparison."""
     dev = device or _lib.require_gpu()
-    xd, yd, td = _nearest_inputs(x, y, cell_type, dev)
+    xd, yd, td = _points(x, y, cell_type, dev, "nearest_by_type")
     n = xd.numel()
     near2 = torch.empty((n, max(int(n_types), 0)), dtype=torch.float64, device=dev)
     arg = torch.empty((n, max(int(n_types), 0)), dtype=torch.int32, device=dev)
-    if ws is None:
-        ws = _scratch(nearest_by_type_ws_bytes(n, n_types), dev)
+    ws = _ws(ws, nearest_by_type_ws_bytes(n, n_types), xd.device, "nearest_by_type")
     check(lib().ribca_nearest_by_type(ptr(xd), ptr(yd), ptr(td), n, int(n_types), ptr(near2), ptr(arg), ptr(ws), ws.numel(), stream_ptr()),
           "ribca_nearest_by_type")
     return near2, arg
@@ -380,20 +407,14 @@ def nearest_perm_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, n_t
     in the band radii[k - 1] < distance <= radii[k] (band 0 from distance 0; beyond the last radius: not counted).  ``radii`` in pixels, squared
     once in fp64 here as ``radial_pair_counts`` squares them.  Accumulates into ``out`` when given (the images of a group)."""
     dev = device or _lib.require_gpu()
-    xd, yd, td = _nearest_inputs(x, y, cell_type, dev)
+    xd, yd, td = _points(x, y, cell_type, dev, "nearest_perm_counts")
     n = xd.numel()
-    r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
-    r2 = np.ascontiguousarray(r * r)
-    shape = (max(int(n_perms), 0), len(r2), max(int(n_types), 0), max(int(n_types), 0))
-    if out is None:
-        out = torch.zeros(shape, dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"nearest_perm_counts: out must be a contiguous int64 tensor of shape {shape}")
-    if ws is None:
-        ws = _scratch(nearest_perm_counts_ws_bytes(n, n_types, n_perms), dev)
+    r2 = _radii2(radii)
+    out = _counts_out(out, (max(int(n_perms), 0), len(r2), max(int(n_types), 0), max(int(n_types), 0)), xd.device, "nearest_perm_counts")
+    ws = _ws(ws, nearest_perm_counts_ws_bytes(n, n_types, n_perms), xd.device, "nearest_perm_counts")
     check(lib().ribca_nearest_perm_counts(ptr(xd), ptr(yd), ptr(td), n, int(n_types), r2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(r2),
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0), int(n_perms), ptr(out), ptr(ws), ws.numel(),
-                                          stream_ptr()), "ribca_nearest_perm_counts")
+                                          _u64(seed), int(image), int(p0), int(n_perms), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+          "ribca_nearest_perm_counts")
     return out
 
 
@@ -427,8 +448,7 @@ def contact_table(mask: torch.Tensor, label_to_cell: torch.Tensor, n: int, d: in
     pairs = torch.empty((rows, cols), dtype=torch.int64, device=dev)
     degree = torch.empty((rows,), dtype=torch.int32, device=dev)
     over = torch.empty((2,), dtype=torch.int32, device=dev)
-    if ws is None:
-        ws = _scratch(contact_table_ws_bytes(h, w, n, slots), dev)
+    ws = _ws(ws, contact_table_ws_bytes(h, w, n, slots), dev, "contact_table")
     check(lib().ribca_contact_table(ptr(mask), h, w, ptr(table), table.numel(), int(n), int(d), int(slots), ptr(nbr), ptr(pairs), ptr(degree),
                                     ptr(over), ptr(ws), ws.numel(), stream_ptr()), "ribca_contact_table")
     return nbr, pairs, degree, over
@@ -447,10 +467,7 @@ def contact_graph(mask: torch.Tensor, ids: np.ndarray, d: int, first_slots: int 
     if n == 0:
         return {"src": np.zeros(0, np.int32), "dst": np.zeros(0, np.int32), "pairs": np.zeros(0, np.int64), "degree": np.zeros(0, np.int32),
                 "slots": int(first_slots)}
-    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
-    table[ids] = np.arange(n, dtype=np.int32)
-    table[0] = -1      # colorize paints labels > 0 only
-    tab_d = torch.from_numpy(table).to(mask.device)
+    tab_d = _cell_table(ids, mask.device)
     slots = int(first_slots)
     while True:
         nbr, pairs, degree, over = contact_table(mask, tab_d, n, d, slots)
@@ -486,17 +503,10 @@ def edge_perm_counts(src, dst, cell_type: np.ndarray, n_types: int, seed: int, i
     labels = np.ascontiguousarray(cell_type, dtype=np.int32).reshape(-1)
     n = len(labels)
     td = torch.from_numpy(labels).to(dev)
-    shape = (max(int(n_perms), 0), max(int(n_types), 0), max(int(n_types), 0))
-    if out is None:
-        out = torch.zeros(shape, dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != sd.device:
-        raise ValueError(f"edge_perm_counts: out must be a contiguous int64 tensor of shape {shape} on the device of the edges")
-    if ws is None:
-        ws = _scratch(edge_perm_counts_ws_bytes(n, n_perms), dev)
-    elif ws.dtype != torch.uint8 or ws.device != sd.device or not ws.is_contiguous():
-        raise ValueError("edge_perm_counts: ws must be a contiguous uint8 tensor on the device of the edges")
-    check(lib().ribca_edge_perm_counts(ptr(sd), ptr(dd), sd.numel(), ptr(td), n, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0),
-                                       int(n_perms), ptr(out), ptr(ws), ws.numel(), stream_ptr()), "ribca_edge_perm_counts")
+    out = _counts_out(out, (max(int(n_perms), 0), max(int(n_types), 0), max(int(n_types), 0)), sd.device, "edge_perm_counts")
+    ws = _ws(ws, edge_perm_counts_ws_bytes(n, n_perms), sd.device, "edge_perm_counts")
+    check(lib().ribca_edge_perm_counts(ptr(sd), ptr(dd), sd.numel(), ptr(td), n, int(n_types), _u64(seed), int(image), int(p0), int(n_perms), ptr(out),
+                                       ptr(ws), ws.numel(), stream_ptr()), "ribca_edge_perm_counts")
     return out
 
 
@@ -515,10 +525,7 @@ def mask_morphology(mask: torch.Tensor, ids: np.ndarray, rect: Optional[np.ndarr
     if n == 0:
         return {"sums": np.zeros((0, 16), np.int64), "bbox": np.zeros((0, 4), np.int32)}
     dev = mask.device
-    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
-    table[ids] = np.arange(n, dtype=np.int32)
-    table[0] = -1      # colorize paints labels > 0 only
-    tab_d = torch.from_numpy(table).to(dev)
+    tab_d = _cell_table(ids, dev)
     rect_d = None
     if rect is not None:
         rect = np.ascontiguousarray(rect, dtype=np.int32)
@@ -529,8 +536,7 @@ def mask_morphology(mask: torch.Tensor, ids: np.ndarray, rect: Optional[np.ndarr
     h, w = mask.shape
     sums = torch.empty((n, 16), dtype=torch.int64, device=dev)
     bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    if ws is None:
-        ws = _scratch(mask_morphology_ws_bytes(h, w, n), dev)
+    ws = _ws(ws, mask_morphology_ws_bytes(h, w, n), dev, "mask_morphology")
     check(lib().ribca_mask_morphology(ptr(mask), h, w, ptr(tab_d), tab_d.numel(), n, ptr(rect_d), ptr(sums), ptr(bbox), ptr(ws), ws.numel(),
                                       stream_ptr()), "ribca_mask_morphology")
     return {"sums": sums.cpu().numpy(), "bbox": bbox.cpu().numpy()}
@@ -566,8 +572,7 @@ def expand_labels(mask: torch.Tensor, distance: int, want_dist2: bool = False, w
     dev = mask.device
     out = torch.empty_like(mask)
     dist2 = torch.empty_like(mask) if want_dist2 else None
-    if ws is None:
-        ws = _scratch(expand_labels_ws_bytes(h, w, d), dev)
+    ws = _ws(ws, expand_labels_ws_bytes(h, w, d), dev, "expand_labels")
     check(lib().ribca_expand_labels(ptr(mask), h, w, d, ptr(out), ptr(dist2), ptr(ws), ws.numel(), stream_ptr()), "ribca_expand_labels")
     return (out, dist2) if want_dist2 else out
 
@@ -594,8 +599,7 @@ def mask_components(mask: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tu
     h, w = mask.shape
     root = torch.empty_like(mask)
     stats = torch.empty((h * w, 4), dtype=torch.int32, device=mask.device)
-    if ws is None:
-        ws = _scratch(mask_components_ws_bytes(h, w), mask.device)
+    ws = _ws(ws, mask_components_ws_bytes(h, w), mask.device, "mask_components")
     check(lib().ribca_mask_components(ptr(mask), h, w, ptr(root), ptr(stats), ptr(ws), ws.numel(), stream_ptr()), "ribca_mask_components")
     return root, stats
 
@@ -679,12 +683,8 @@ def mask_rings(mask: torch.Tensor, ids: np.ndarray, ws: Optional[torch.Tensor] =
         return empty
     dev = mask.device
     h, w = mask.shape
-    table = np.full(int(ids.max()) + 1, -1, dtype=np.int32)
-    table[ids] = np.arange(n, dtype=np.int32)
-    table[0] = -1      # colorize paints labels > 0 only
-    tab_d = torch.from_numpy(table).to(dev)
-    if ws is None:
-        ws = _scratch(mask_rings_ws_bytes(h, w, n), dev)
+    tab_d = _cell_table(ids, dev)
+    ws = _ws(ws, mask_rings_ws_bytes(h, w, n), dev, "mask_rings")
     total = torch.empty(1, dtype=torch.int64, device=dev)
     cap, calls = (2 * n + OUTLINES_SPARE_ROWS if first_cap is None else max(int(first_cap), 1)), 0
     while True:
@@ -771,13 +771,11 @@ def autocorr_perm_ws_bytes(n: int, c: int, n_perms: int) -> int:
     return int(lib().ribca_autocorr_perm_ws_bytes(int(n), int(c), int(n_perms)))
 
 
-def _autocorr_args(what: str, z: torch.Tensor, idx: torch.Tensor, ws: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+def _autocorr_args(what: str, z: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     if z.dtype != torch.float64 or z.dim() != 2 or idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != z.shape[0]:
         raise ValueError(f"{what} takes an (n, C) float64 table of centred values and an (n, m) int32 neighbour list")
     if idx.device != z.device:
         raise ValueError(f"{what}: the table and the neighbour list must be on the same device")
-    if ws is not None and (ws.dtype != torch.uint8 or ws.device != z.device or not ws.is_contiguous()):
-        raise ValueError(f"{what}: ws must be a contiguous uint8 tensor on the device of z")
     if not bool(torch.isfinite(z).all()):
         raise ValueError(f"{what}: the table holds values that are not finite")
     return z.contiguous(), idx.contiguous()
@@ -788,11 +786,10 @@ def autocorr_observed(z: torch.Tensor, idx: torch.Tensor, ws: Optional[torch.Ten
     Geary's C (row 1: the sum of the squared differences to the neighbours) of every column of the (n, C) fp64 device table ``z`` of CENTRED
     values over the fixed (n, m) int32 device neighbour list ``idx``.  A pure function of its inputs: include/ribca_hip.h states the order of
     every addition.  Values that are not finite raise before any launch."""
-    z, idx = _autocorr_args("autocorr_observed", z, idx, ws)
+    z, idx = _autocorr_args("autocorr_observed", z, idx)
     n, c = z.shape
     out = torch.empty((2, c), dtype=torch.float64, device=z.device)
-    if ws is None:
-        ws = _scratch(autocorr_observed_ws_bytes(n, c), z.device)
+    ws = _ws(ws, autocorr_observed_ws_bytes(n, c), z.device, "autocorr_observed")
     check(lib().ribca_autocorr_observed(ptr(z), ptr(idx), n, c, idx.shape[1], ptr(out), ptr(ws), ws.numel(), stream_ptr()), "ribca_autocorr_observed")
     return out
 
@@ -801,13 +798,12 @@ def autocorr_perm(z: torch.Tensor, idx: torch.Tensor, seed: int, image: int, p0:
     """(n_perms, 2, C) fp64 device tensor: the numerators of ``autocorr_observed`` under the permutations p0 .. p0 + n_perms - 1 of (seed, image)
     -- cell i carries the whole row z[sigma_p(i)], one bijection for all channels (the sigma of ``nhood_perm_counts``, keyed the same way).
     Slice j depends on (z, idx, seed, image, p0 + j) alone."""
-    z, idx = _autocorr_args("autocorr_perm", z, idx, ws)
+    z, idx = _autocorr_args("autocorr_perm", z, idx)
     n, c = z.shape
     out = torch.empty((max(int(n_perms), 0), 2, c), dtype=torch.float64, device=z.device)
-    if ws is None:
-        ws = _scratch(autocorr_perm_ws_bytes(n, c, n_perms), z.device)
-    check(lib().ribca_autocorr_perm(ptr(z), ptr(idx), n, c, idx.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0), int(n_perms), ptr(out),
-                                    ptr(ws), ws.numel(), stream_ptr()), "ribca_autocorr_perm")
+    ws = _ws(ws, autocorr_perm_ws_bytes(n, c, n_perms), z.device, "autocorr_perm")
+    check(lib().ribca_autocorr_perm(ptr(z), ptr(idx), n, c, idx.shape[1], _u64(seed), int(image), int(p0), int(n_perms), ptr(out), ptr(ws), ws.numel(),
+                                    stream_ptr()), "ribca_autocorr_perm")
     return out
 
 
@@ -819,7 +815,7 @@ def local_lag(z: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """(n, C) fp64 device tensor: per cell and channel the sum of the neighbours' values of the (n, C) fp64 device table ``z`` of CENTRED values
     over the (n, m) int32 device neighbour list ``idx``, added in list order (csrc/local_autocorr.hip).  Values that are not finite raise
     before any launch."""
-    z, idx = _autocorr_args("local_lag", z, idx, None)
+    z, idx = _autocorr_args("local_lag", z, idx)
     n, c = z.shape
     lag = torch.empty((n, c), dtype=torch.float64, device=z.device)
     check(lib().ribca_local_lag(ptr(z), ptr(idx), n, c, idx.shape[1], ptr(lag), stream_ptr()), "ribca_local_lag")
@@ -831,17 +827,16 @@ def local_perm_counts(z: torch.Tensor, idx: torch.Tensor, lag: torch.Tensor, see
     """(ge, le), two (n, C) int64 device tensors: how many of the conditional permutations p0 .. p0 + n_perms - 1 of (seed, image) -- cell i
     keeps its row, the others move around it with the sigma of ``nhood_perm_counts`` -- give cell i a neighbour sum at or above / at or below
     ``lag`` (the output of ``local_lag``).  Counts of adjoining ranges of permutations add up entry by entry."""
-    z, idx = _autocorr_args("local_perm_counts", z, idx, ws)
+    z, idx = _autocorr_args("local_perm_counts", z, idx)
     n, c = z.shape
     if lag.dtype != torch.float64 or tuple(lag.shape) != (n, c) or lag.device != z.device:
         raise ValueError("local_perm_counts takes the (n, C) float64 lag of local_lag on the device of z")
     lag = lag.contiguous()
     ge = torch.empty((n, c), dtype=torch.int32, device=z.device)      # the library's uint32, widened below: a count may reach 2^31
     le = torch.empty((n, c), dtype=torch.int32, device=z.device)
-    if ws is None:
-        ws = _scratch(local_perm_counts_ws_bytes(n, c, n_perms), z.device)
-    check(lib().ribca_local_perm_counts(ptr(z), ptr(idx), ptr(lag), n, c, idx.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(p0),
-                                        int(n_perms), ptr(ge), ptr(le), ptr(ws), ws.numel(), stream_ptr()), "ribca_local_perm_counts")
+    ws = _ws(ws, local_perm_counts_ws_bytes(n, c, n_perms), z.device, "local_perm_counts")
+    check(lib().ribca_local_perm_counts(ptr(z), ptr(idx), ptr(lag), n, c, idx.shape[1], _u64(seed), int(image), int(p0), int(n_perms), ptr(ge), ptr(le),
+                                        ptr(ws), ws.numel(), stream_ptr()), "ribca_local_perm_counts")
     return ge.to(torch.int64) & 0xFFFFFFFF, le.to(torch.int64) & 0xFFFFFFFF
 
 
@@ -857,9 +852,7 @@ def knn_composition_counts(x: np.ndarray, y: np.ndarray, cell_type: np.ndarray, 
     n = len(x)
     if max(sizes) + 1 > n:
         raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {max(sizes) + 1}, n_samples_fit = {n}")
-    xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
-    td = torch.from_numpy(np.ascontiguousarray(cell_type, dtype=np.int32)).to(dev)
+    xd, yd, td = _points(x, y, cell_type, dev, "knn_composition_counts")
     sd = torch.tensor(list(sizes), dtype=torch.int32, device=dev)
     counts = torch.empty((n, len(sizes), n_types), dtype=torch.int16, device=dev)
     check(lib().ribca_knn_compositions(ptr(xd), ptr(yd), ptr(td), n, int(n_types), ptr(sd), len(sizes), ptr(counts), stream_ptr()),
@@ -889,8 +882,7 @@ def region_gram(counts: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tupl
     n, f = counts.shape
     colsum = torch.empty(f, dtype=torch.int64, device=counts.device)
     gram = torch.empty((f, f), dtype=torch.int64, device=counts.device)
-    if ws is None:
-        ws = _scratch(region_gram_ws_bytes(n, f), counts.device)
+    ws = _ws(ws, region_gram_ws_bytes(n, f), counts.device, "region_gram")
     check(lib().ribca_region_gram(ptr(counts), n, f, ptr(colsum), ptr(gram), ptr(ws), ws.numel(), stream_ptr()), "ribca_region_gram")
     return colsum, gram
 
@@ -917,8 +909,7 @@ def kmeans_trials(y: torch.Tensor, cand: torch.Tensor, closest: Optional[torch.T
     m = int(cand.numel())
     cand_d2 = torch.empty((m, n), dtype=torch.float64, device=y.device)
     pot = torch.empty(m, dtype=torch.float64, device=y.device)
-    if ws is None:
-        ws = _scratch(kmeans_trials_ws_bytes(n, m), y.device)
+    ws = _ws(ws, kmeans_trials_ws_bytes(n, m), y.device, "kmeans_trials")
     check(lib().ribca_kmeans_trials(ptr(y), n, d, ptr(cand), m, ptr(closest), ptr(cand_d2), ptr(pot), ptr(ws), ws.numel(), stream_ptr()),
           "ribca_kmeans_trials")
     return cand_d2, pot
@@ -992,11 +983,9 @@ def umap_optimize(emb: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor
     """n_epochs of umap's layout SGD on emb (n, dim <= 8) fp32 in place (deterministic Jacobi epochs, hashed negative samples)."""
     n, dim = emb.shape
     nnz = int(indices.numel())
-    if ws is None:
-        ws = _scratch(umap_optimize_ws_bytes(n, dim, nnz), emb.device)
+    ws = _ws(ws, umap_optimize_ws_bytes(n, dim, nnz), emb.device, "umap_optimize")
     check(lib().ribca_umap_optimize(ptr(emb), n, dim, ptr(indptr), ptr(indices), ptr(rev), ptr(eps), float(a), float(b), float(gamma),
-                                    float(alpha0), float(neg_rate), int(n_epochs), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ws), ws.numel(),
-                                    stream_ptr()), "ribca_umap_optimize")
+                                    float(alpha0), float(neg_rate), int(n_epochs), _u64(seed), ptr(ws), ws.numel(), stream_ptr()), "ribca_umap_optimize")
     return emb
 
 
@@ -1041,8 +1030,7 @@ def spectral_gram(u: torch.Tensor, v: torch.Tensor, ws: Optional[torch.Tensor] =
         raise ValueError("spectral_gram: u and v differ in rows")
     q = v.shape[1]
     g = torch.empty((p, q), dtype=torch.float64, device=u.device)
-    if ws is None:
-        ws = _scratch(spectral_gram_ws_bytes(n, p, q), u.device)
+    ws = _ws(ws, spectral_gram_ws_bytes(n, p, q), u.device, "spectral_gram")
     check(lib().ribca_spectral_gram(ptr(u), ptr(v), n, p, q, ptr(g), ptr(ws), ws.numel(), stream_ptr()), "ribca_spectral_gram")
     return g
 
@@ -1092,8 +1080,7 @@ def scatter_raster(points: torch.Tensor, rgb: torch.Tensor, height: int, width: 
         raise ValueError("scatter_raster takes (n, 2) float32 points and (n, 3) uint8 colours")
     ax, bx, ay, by = (float(v) for v in affine)
     out = torch.empty((int(height), int(width), 3), dtype=torch.uint8, device=points.device)
-    if ws is None:
-        ws = _scratch(lib().ribca_scatter_raster_ws_bytes(int(height), int(width)), points.device)
+    ws = _ws(ws, lib().ribca_scatter_raster_ws_bytes(int(height), int(width)), points.device, "scatter_raster")
     skipped = ctypes.c_int64(0)
     n = points.shape[0]
     check(lib().ribca_scatter_raster(ptr(points) if n else None, ptr(rgb) if n else None, n, ax, bx, ay, by, int(height), int(width), int(radius),
@@ -1121,8 +1108,7 @@ def group_sums(x: torch.Tensor, group: torch.Tensor, groups: int, ws: Optional[t
     n, c = x.shape
     sums = torch.empty((max(int(groups), 0), c), dtype=torch.float64, device=x.device)
     counts = torch.empty(max(int(groups), 0), dtype=torch.int64, device=x.device)
-    if ws is None:
-        ws = _scratch(group_sums_ws_bytes(n, c, groups), x.device)
+    ws = _ws(ws, group_sums_ws_bytes(n, c, groups), x.device, "group_sums")
     skipped = ctypes.c_int64(0)
     check(lib().ribca_group_sums(ptr(x) if n else None, ptr(group) if n else None, n, c, int(groups), ptr(sums), ptr(counts), ctypes.byref(skipped),
                                  ptr(ws), ws.numel(), stream_ptr()), "ribca_group_sums")
@@ -1139,8 +1125,7 @@ def heatmap_raster(sums: torch.Tensor, counts: torch.Tensor, lut: torch.Tensor, 
     sums, counts, lut = sums.contiguous(), counts.contiguous(), lut.contiguous()
     t, c = sums.shape
     out = torch.empty((t * max(int(cell), 0), c * max(int(cell), 0), 3), dtype=torch.uint8, device=sums.device)
-    if ws is None:
-        ws = _scratch(lib().ribca_heatmap_raster_ws_bytes(t, c, int(cell), int(gap)), sums.device)
+    ws = _ws(ws, lib().ribca_heatmap_raster_ws_bytes(t, c, int(cell), int(gap)), sums.device, "heatmap_raster")
     vmin, vmax = ctypes.c_double(0.0), ctypes.c_double(0.0)
     check(lib().ribca_heatmap_raster(ptr(sums), ptr(counts), t, c, ptr(lut), int(cell), int(gap), ptr(out), ctypes.byref(vmin), ctypes.byref(vmax),
                                      ptr(ws), ws.numel(), stream_ptr()), "ribca_heatmap_raster")
@@ -1183,8 +1168,7 @@ def core_distance(x: torch.Tensor, min_samples: int, ws: Optional[torch.Tensor] 
     x = x.contiguous()
     n, dim = x.shape
     core2 = torch.empty(n, dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = _scratch(core_distance_ws_bytes(n, dim, int(min_samples)), x.device)
+    ws = _ws(ws, core_distance_ws_bytes(n, dim, int(min_samples)), x.device, "core_distance")
     check(lib().ribca_core_distance(ptr(x), n, dim, int(min_samples), ptr(core2), ptr(ws), ws.numel(), stream_ptr()), "ribca_core_distance")
     return core2
 
@@ -1203,8 +1187,7 @@ def mreach_mst(x: torch.Tensor, core2: torch.Tensor, ws: Optional[torch.Tensor] 
     u = torch.empty(m, dtype=torch.int32, device=x.device)
     v = torch.empty(m, dtype=torch.int32, device=x.device)
     w = torch.empty(m, dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = _scratch(mreach_mst_ws_bytes(n), x.device)
+    ws = _ws(ws, mreach_mst_ws_bytes(n), x.device, "mreach_mst")
     check(lib().ribca_mreach_mst(ptr(x), n, dim, ptr(core2.contiguous()), ptr(u), ptr(v), ptr(w), ptr(ws), ws.numel(), stream_ptr()),
           "ribca_mreach_mst")
     return u, v, w
@@ -1557,8 +1540,7 @@ class VitModel:
         n_chunks = (n + chunk - 1) // chunk
         nseg = max(1, min(int(streams), n_chunks))
         if nseg == 1:
-            ws = workspace(nbytes + 256, patches.device, ws_slot)
-            aligned = (ws.data_ptr() + 255) & ~255
+            aligned = _workspace_ptr(nbytes, patches.device, ws_slot)
             check(fwd(self._h, ptr(patches), c_img, ptr(src), n, ptr(probs), aligned, nbytes, chunk, stream_ptr()), "ribca_vit_forward")
             return probs
         main = torch.cuda.current_stream(patches.device)
@@ -1570,8 +1552,7 @@ class VitModel:
             lo, hi = c0 * chunk, min(c1 * chunk, n)
             if hi <= lo:
                 continue
-            ws = workspace(nbytes + 256, patches.device, (ws_slot + 1) * 64 + i)
-            aligned = (ws.data_ptr() + 255) & ~255
+            aligned = _workspace_ptr(nbytes, patches.device, (ws_slot + 1) * 64 + i)
             st.wait_event(ready)
             with torch.cuda.stream(st):
                 check(fwd(self._h, ptr(patches[lo:hi]), c_img, ptr(src), hi - lo, ptr(probs[lo:hi]), aligned, nbytes, chunk, stream_ptr()),
@@ -1693,8 +1674,7 @@ class MaeModel:
         nbytes = lib().ribca_mae_workspace_bytes(handle, chunk, len(pres))
         if nbytes <= 0:
             raise ValueError("need at least one present and one missing channel")
-        ws = workspace(nbytes + 256, patches.device)
-        aligned = (ws.data_ptr() + 255) & ~255
+        aligned = _workspace_ptr(nbytes, patches.device)
         arr = (ctypes.c_int32 * len(pres))(*pres)
         check(lib().ribca_mae_impute(handle, ptr(patches), arr, len(pres), n, aligned, nbytes, chunk, stream_ptr()), "ribca_mae_impute")
         return patches
