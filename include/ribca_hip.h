@@ -438,6 +438,35 @@ int ribca_mask_rings(const int32_t* mask, int32_t H, int32_t W, const int32_t* l
 int ribca_mask_ring_vertices(const int32_t* mask, int32_t H, int32_t W, const int32_t* label_to_cell, int32_t L, int32_t n, const int64_t* rings,
                              int32_t R, const int64_t* first, int32_t* vertices, int32_t* bad, void* stream);
 
+/* ---- matching a second mask to the cells: the sparse contingency table of two label images (csrc/overlap.hip) -------------
+ * mask_a and mask_b (H, W) int32 row-major, a_to_cell (La) int32 and b_to_obj (Lb) int32 on the device, all read only.  OWNERSHIP is the rule of
+ * ribca_contact_table, applied to each mask with its own table: cell(p) = a_to_cell[mask_a[p]] when 0 <= mask_a[p] < La and the result lies in
+ * [0, n), "none" otherwise; obj(p) likewise from mask_b, b_to_obj, Lb and m.  A label in several blobs is one cell (or one object).
+ *     area_a[i] = #{ p : cell(p) = i }      area_b[j] = #{ p : obj(p) = j }      w(i, j) = #{ p : cell(p) = i and obj(p) = j }
+ * ribca_mask_overlap: partner (n, S) int32, inter (n, S) uint64, degree (n) int32, area_a (n) int32, area_b (m) int32 and over (2) int32 are all
+ * OVERWRITTEN (the library initialises them and its workspace itself).  over[0] == 0: degree[i] = the number of j with w(i, j) > 0;
+ * partner[i][0 .. degree[i]) holds those j in ASCENDING order with w(i, .) beside them in inter; the rest of either row is -1 / 0; over[1] = -1.
+ * over[0] > 0: that many cells overlap more than S objects, over[1] is the lowest such cell index, area_a and area_b are still exact, the other
+ * outputs are unspecified -- call again with a larger S.  The result is a pure function of (mask_a, mask_b, both tables): the same for every S
+ * that fits, every launch geometry and every run (integer atomics only; the rows are sorted by rank, as those of ribca_contact_table).
+ * 1 <= H, W, H W < 2^31, 1 <= La, Lb, 1 <= n, m <= 2^21, S a power of two in 8 .. 1024.  ws: ribca_mask_overlap_ws_bytes(H, W, n, S) bytes, the
+ * three pieces of ribca_contact_table_ws_bytes (4 n S bytes of keys, 8 n S bytes of sums, 4 n bytes of overflow flags, each rounded up to 256
+ * bytes); 0 for arguments the entry point refuses.  The outputs and ws must not overlap each other or the inputs; the inputs may share memory
+ * (mask_a == mask_b is allowed).
+ * ribca_mask_compartments: owner (m) int32 on the device: the cell index that owns object j, or -1 (any other value owns nothing).  inner and
+ * outer (H, W) int32 are OVERWRITTEN, every byte: inner[p] = mask_a[p] when cell(p) = i is a cell, obj(p) = j is an object and owner[j] == i,
+ * else 0; outer[p] = mask_a[p] when cell(p) is a cell and inner[p] == 0, else 0.  inner and outer must not overlap each other or the inputs.  The
+ * same limits on H, W, La, Lb, n, m; no workspace.
+ * Both: a NULL buffer, sizes out of range, a NULL or short workspace and overlapping outputs are refused with a status that names the entry point,
+ * before any HIP call.  No loop of any kernel waits for another thread: every probe sequence ends after at most S slots.  Neither entry point
+ * synchronises. */
+int64_t ribca_mask_overlap_ws_bytes(int32_t H, int32_t W, int32_t n, int32_t S);
+int ribca_mask_overlap(const int32_t* mask_a, const int32_t* mask_b, int32_t H, int32_t W, const int32_t* a_to_cell, int32_t La, int32_t n,
+                       const int32_t* b_to_obj, int32_t Lb, int32_t m, int32_t S, int32_t* partner, uint64_t* inter, int32_t* degree,
+                       int32_t* area_a, int32_t* area_b, int32_t* over, void* ws, int64_t ws_bytes, void* stream);
+int ribca_mask_compartments(const int32_t* mask_a, const int32_t* mask_b, int32_t H, int32_t W, const int32_t* a_to_cell, int32_t La, int32_t n,
+                            const int32_t* b_to_obj, int32_t Lb, int32_t m, const int32_t* owner, int32_t* inner, int32_t* outer, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

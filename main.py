@@ -22,7 +22,11 @@ the intensity tables of the nucleus (core) and of the grown ring as well (Annota
 the GPU before the expansion and before anything reads it -- the pieces of a torn label become labels of their own, pieces of fewer than A pixels are
 dropped, holes are filled -- and writes the repaired mask and a per-component table (Annotator(repair_mask=A)); ``--outlines`` every cell of the mask
 the run works on as a polygon with its id, area, cell type, colour and confidence, traced on the GPU, one GeoJSON file (the layout of QuPath's export)
-and one per-cell CSV per image (Annotator.cell_outlines).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
+and one per-cell CSV per image (Annotator.cell_outlines); ``--match-masks`` matches a second mask of every image -- ``--second-mask-path`` beside
+``--mask-path``, or the column ``second_mask_path`` of ``--batch-csv``: nuclei beside whole cells, or another tool's segmentation -- to the cells on the
+GPU: which object belongs to which cell, the nuclear fraction, the IoU of every pair and the agreement of the two masks at IoU 0.5 .. 0.95, with
+``--match-intensities`` the marker intensities inside and outside the owned objects and with ``--match-save-masks`` the two compartment masks
+(Annotator.mask_matching).  Multi-GPU: launch under ``python -m torch.distributed.run --nproc-per-node N main.py ...``.
 """
 import argparse
 import os
@@ -74,6 +78,15 @@ def parse_args(argv=None):
     ap.add_argument('--outlines', action='store_true',
                     help='every cell as a polygon with properties, traced on the GPU from the mask after repair and expansion: one GeoJSON file '
                          '(QuPath detections: id, area, cell type, colour, confidence) and one per-cell ring table per image')
+    ap.add_argument('--match-masks', action='store_true',
+                    help='match a second mask of every image (--second-mask-path, or the column second_mask_path of --batch-csv) to the cells: per-cell, '
+                         'per-object and pair tables, a nuclear-fraction map, and the agreement of the two masks at IoU 0.5 .. 0.95')
+    ap.add_argument('--second-mask-path', type=str, default=None, help='the second mask of --image-path; read only with --match-masks')
+    ap.add_argument('--match-min-overlap', type=int, default=50,
+                    help='percent (1 .. 100) of an object that must lie in its cell for the cell to own it; read only with --match-masks')
+    ap.add_argument('--match-intensities', action='store_true',
+                    help='with --match-masks: the per-cell marker intensities inside the owned objects and over the rest of the cell')
+    ap.add_argument('--match-save-masks', action='store_true', help='with --match-masks: write the inner and outer compartment masks as .npy')
     ap.add_argument('--expand-mask', type=int, default=0,
                     help='grow every label of the mask by this many pixels (1 .. 32) on the GPU before anything reads it: for nuclear masks; writes the '
                          'expanded mask and a per-cell expansion table, and with --intensities the core and ring tables (0 = use the mask as it is)')
@@ -87,6 +100,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.image_path and not args.mask_path:
         ap.error("--mask-path is required when using --image-path")
+    if args.match_masks and args.image_path and not args.second_mask_path:
+        ap.error("--match-masks needs --second-mask-path beside --mask-path (or the column second_mask_path in --batch-csv)")
+    if not 1 <= args.match_min_overlap <= 100:
+        ap.error("--match-min-overlap takes a percent of 1 .. 100")
     if not 0 <= args.contact_distance <= 8:
         ap.error("--contact-distance takes 0 (off) or a reach of 1 .. 8 pixels")
     if not 0 <= args.expand_mask <= 32:
@@ -120,7 +137,7 @@ def _check_repair_mask(repair_mask):
 
 
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
-              nearest_perms=0, outlines=False, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
+              nearest_perms=0, match=None, outlines=False, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
               contact_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
@@ -163,6 +180,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
         if expand_mask > 0:                         # the mask was grown from nuclei: the same table over the nucleus and over the grown ring
             annotator.cell_intensities(integrate=True, maps=False, compartment="core")
             annotator.cell_intensities(integrate=True, maps=False, compartment="ring")
+    if match is not None:                           # and how a second mask of the same images -- nuclei, another tool's cells -- sits in the cells
+        annotator.mask_matching(integrate=True, **match)
     if outlines:                                    # and the cells as objects a viewer can load: polygons with properties, per image
         annotator.cell_outlines()
     annotator.colorize(from_script=True)
@@ -173,8 +192,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, outlines=False, repair_mask=0, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
-        contact_perms=0):
+        nearest_bands=0, nearest_perms=0, match=None, second_mask_path=None, outlines=False, repair_mask=0, expand_mask=0, morphology=False,
+        intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _check_expand_mask(expand_mask)
@@ -185,7 +204,10 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
     if int(os.environ.get("RANK", "0")) == 0:
         os.makedirs(main_dir, exist_ok=True)
         with open(path_, "w") as f:
-            f.write("image_path,mask_path\n%s,%s\n" % (image_path, mask_path))
+            if match is not None and second_mask_path:
+                f.write("image_path,mask_path,second_mask_path\n%s,%s,%s\n" % (image_path, mask_path, second_mask_path))
+            else:
+                f.write("image_path,mask_path\n%s,%s\n" % (image_path, mask_path))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
         dist.barrier()
@@ -193,7 +215,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
                           cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
-              outlines=outlines)
+              outlines=outlines, match=match)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -205,9 +227,9 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, outlines=False, repair_mask=0, expand_mask=0, morphology=False,
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, match=None, outlines=False, repair_mask=0, expand_mask=0, morphology=False,
               intensities=False, contact_distance=0, contact_perms=0):
-    """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path."""
+    """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path (and second_mask_path for ``match``)."""
     _check_expand_mask(expand_mask)
     _check_repair_mask(repair_mask)
     _setup()
@@ -216,7 +238,7 @@ def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, stri
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
-              outlines=outlines)
+              outlines=outlines, match=match)
 
 
 def main(argv=None):
@@ -229,9 +251,11 @@ def main(argv=None):
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
                   contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities,
                   expand_mask=args.expand_mask, repair_mask=args.repair_mask, outlines=args.outlines)
+    if args.match_masks:      # the arguments of Annotator.mask_matching; None: nothing of it is read or written
+        common["match"] = dict(min_overlap=args.match_min_overlap, intensities=args.match_intensities, save_masks=args.match_save_masks)
     if args.batch_csv:
         return batch_run(image_path=args.batch_csv, **common)
-    return run(image_path=args.image_path, mask_path=args.mask_path, **common)
+    return run(image_path=args.image_path, mask_path=args.mask_path, second_mask_path=args.second_mask_path, **common)
 
 
 if __name__ == "__main__":

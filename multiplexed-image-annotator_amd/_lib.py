@@ -74,6 +74,11 @@ SIGNATURES = {
     "ribca_mask_rings": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ribca_mask_ring_vertices": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "ribca_mask_overlap_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ribca_mask_overlap": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ribca_mask_compartments": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
     "ribca_knn_compositions": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "ribca_region_gram_ws_bytes": (c_int64, [c_int32, c_int32]),
     "ribca_region_gram": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

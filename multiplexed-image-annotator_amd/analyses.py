@@ -723,6 +723,157 @@ class Analyses(object):
                                 files[0], n, rec["rings"], rec["holes"], rec["multi_part"], rec["vertices"], rec["saddles"], rec["longest_ring"],
                                 kernel_ms, rec["calls"], write_ms))
 
+    # ---- mask matching: a second mask of the same images -- nuclei, another tool's cells -- against the cells -----------------------------------------
+    def _second_masks(self, second_masks):
+        """The second mask of every LOCAL image as (H, W) int32 host arrays, read and checked before ``mask_matching`` changes anything:
+        ``second_masks`` (one entry per row of the batch CSV: a path for preprocess.read_image or an (H, W) integer array) or, for None, the
+        column ``second_mask_path`` of the batch CSV.  ValueError without either, for an entry that is missing or no integer image, and for a
+        shape other than that of the image's mask."""
+        from .preprocess import read_image
+        pre = self.preprocessor
+        source = second_masks if second_masks is not None else getattr(pre, "second_mask_paths", None)
+        if source is None:
+            raise ValueError("mask_matching needs a second mask per image: pass second_masks or add the column second_mask_path to the batch CSV")
+        source = list(source)
+        if len(source) != pre._n_images:
+            raise ValueError(f"mask_matching takes one second mask per row of the batch CSV, got {len(source)} for {pre._n_images} images")
+        out = []
+        for i in range(len(pre.masks_dev)):
+            number = self._image_number(i)
+            entry = source[number]
+            if entry is None or (isinstance(entry, float) and entry != entry):
+                raise ValueError(f"mask_matching: image {number} has no second mask")
+            mask = read_image(entry) if isinstance(entry, (str, os.PathLike)) else np.asarray(entry)
+            if mask.ndim == 3 and isinstance(entry, (str, os.PathLike)):
+                mask = mask[:, :, 0]                      # as the first mask is read: the first channel holds the labels
+            want = tuple(int(v) for v in pre.masks_dev[i].shape)
+            if mask.ndim != 2 or not (np.issubdtype(mask.dtype, np.integer) or isinstance(entry, (str, os.PathLike))) or tuple(mask.shape) != want:
+                raise ValueError(f"mask_matching: the second mask of image {number} must be an integer image of shape {want}, got {mask.dtype} {tuple(mask.shape)}")
+            out.append(np.ascontiguousarray(mask.astype(np.int32)))
+        return out
+
+    def mask_matching(self, second_masks=None, min_overlap=50, intensities=False, save_masks=False, integrate=True):
+        """Matches a SECOND mask of every image to the cells.  Mask A is the mask the run works on (``preprocessor.masks_dev``, after
+        ``repair_mask`` and ``expand_mask``), its cells the run's cells; mask B is ``second_masks[row of the batch CSV]`` -- a path or an (H, W)
+        integer array -- or, for None, the file in the column ``second_mask_path`` of the batch CSV, used as read (neither repaired nor
+        expanded), its OBJECTS the labels of ops.label_table(B): nuclei beside whole cells, or another tool's segmentation of the same image.
+        The pixels every (cell, object) pair shares are counted on the GPU (ops.overlap_pairs, csrc/overlap.hip: exact integers), the rules
+        are matching.py's, in int64 and fp64: an object is OWNED by the cell that holds most of it when that is at least ``min_overlap``
+        percent (1 .. 100) of the object, else it is an orphan.  Needs preprocess() only; after predict() the tables carry the cell types.
+        Per image it writes ``{batch_id}_matching_cells_{k}.csv`` (matching.cells_csv: area, owned objects, nuclear fraction, status none /
+        single / multi), ``{batch_id}_matching_objects_{k}.csv`` (matching.objects_csv: owner, share inside it, status matched / split /
+        orphan), ``{batch_id}_matching_pairs_{k}.csv`` (every overlapping pair with its intersection, union and IoU) and
+        ``{batch_id}_matching_fraction_{k}.png``, the cells painted through ops.colorize with viridis at int(clip(inner_fraction, 0, 1) * 255);
+        with ``save_masks`` the two compartments of ops.mask_compartments as ``{batch_id}_matching_inner_{k}.npy`` / ``_outer_{k}.npy`` (int32:
+        the cell's label on its pixels inside an owned object / on its other pixels); with ``intensities`` ``{batch_id}_intensities_inner_{k}.csv``
+        / ``_outer_{k}.csv``, ops.cell_intensities over those two masks with the cells' own ids and boxes through intensities.features and
+        intensities.cells_csv (no maps, no ``_vs_window``), the per-cell means kept as ``self.intensity_inner`` / ``self.intensity_outer``.
+        Per group (the batch with ``integrate``, else every image), stem from ``_group_stem("matching", ...)``: ``{stem}_agreement.csv``
+        (matching.agreement_table: true positives, precision, recall, F1, mean matched IoU and panoptic quality at IoU 0.5 .. 0.95, the counts and
+        IoU sums of the images added in image order) and ``{stem}_summary.csv`` (matching.type_summary per cell type and over all cells).
+        Every ValueError -- no masks, a bad ``min_overlap``, no second mask, a second mask of another shape -- is raised BEFORE anything is
+        written or any state changes.  Records ``matching_stats``, one record per group written by this rank; its ``kernel_ms`` is the host's
+        clock around the ops calls (tools/time_consumers.py --matching times the kernels alone).  Multi-rank runs as cell_morphology: the
+        integrated group of a tile-per-rank run takes two ``_gather_rows`` exchanges, the per-cell rows and one row per image."""
+        import time
+        from . import intensities as cell_stats
+        from . import matching
+        pre = self.preprocessor
+        if len(pre.masks_dev) == 0 and not (self.tile_mode and pre._n_images > 0):
+            raise ValueError("No masks: call preprocess() first")
+        percent = matching.check_min_overlap(min_overlap)
+        seconds = self._second_masks(second_masks)
+        self.matching_stats = []
+        kept = {"inner": [], "outer": []}
+        if intensities:
+            self.intensity_inner, self.intensity_outer = kept["inner"], kept["outer"]
+        if not self._computes_here():
+            return None
+        n_local = len(pre.masks_dev)
+        annotated = len(self.annotations) == n_local and n_local > 0
+        names = [str(c) for c in self.cell_types] if annotated or n_local == 0 else []
+        t = len(names)
+        lut = colors.viridis_table()
+        stats = cell_stats.statistic_names()
+        k_thr = len(matching.THRESHOLDS)
+        cell_width, image_width = 5, 6 + 4 * k_thr      # image number, cell id, type, status, inner fraction / image number, 0, m, pairs, orphans, slots, counts, IoU sums
+        for members in _groups(integrate, n_local):
+            cell_rows, image_rows, image_files, kernel_ms, draw_ms = [np.zeros((0, cell_width))], [np.zeros((0, image_width))], [], 0.0, 0.0
+            for i in members:
+                ids = np.asarray(pre.cell_ids[i], dtype=np.int64)
+                n = len(ids)
+                mask_a = pre.masks_dev[i]
+                types = self._cell_type_ints(i) if annotated and n else np.full(n, -1, dtype=np.int64)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                mask_b = torch.from_numpy(seconds[i]).to(mask_a.device)
+                ids_b = ops.label_table(mask_b)[0]
+                got = ops.overlap_pairs(mask_a, ids, mask_b, ids_b)
+                kernel_ms += (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                cell, obj, inter = got["cell"], got["obj"], got["inter"]
+                owner, inside = matching.owners(cell, obj, inter, got["area_b"], percent)
+                cells = matching.cell_rows(cell, obj, inter, got["area_a"], ids_b, owner)
+                objects = matching.object_rows(cell, obj, inter, got["area_b"], ids, owner, inside)
+                union, iou = matching.pair_rows(cell, obj, inter, got["area_a"], got["area_b"])
+                counts, sums = matching.agreement_counts(cell, obj, inter, got["area_a"], got["area_b"])
+                number = self._image_number(i)
+                files = [f"{self.batch_id}_matching_{what}_{number}.csv" for what in ("cells", "objects", "pairs")]
+                self._write_text(files[0], matching.cells_csv(ids, cells, types, names))
+                self._write_text(files[1], matching.objects_csv(ids_b, objects))
+                self._write_text(files[2], matching.pairs_csv(ids, ids_b, cell, obj, inter, union, iou))
+                files.append(f"{self.batch_id}_matching_fraction_{number}.png")
+                idx = matching.fraction_colour_index(cells["inner_fraction"])
+                self._paint_map(i, lut[idx], idx, files[-1])
+                draw_ms += (time.perf_counter() - t0) * 1e3
+                if save_masks or intensities:
+                    t0 = time.perf_counter()
+                    parts = dict(zip(("inner", "outer"), ops.mask_compartments(mask_a, ids, mask_b, ids_b, owner)))
+                    torch.cuda.synchronize()
+                    kernel_ms += (time.perf_counter() - t0) * 1e3
+                    for part in ("inner", "outer") if save_masks else ():
+                        files.append(f"{self.batch_id}_matching_{part}_{number}.npy")
+                        np.save(os.path.join(self.result_dir, files[-1]), parts[part].cpu().numpy().astype(np.int32))
+                    for part in ("inner", "outer") if intensities else ():
+                        image = pre.images_dev[i]
+                        t0 = time.perf_counter()
+                        area, sums_c, order = ops.cell_intensities(image, parts[part], pre.cell_ids_dev[i], pre.cell_bbox_dev[i], cell_stats.Q_NUM, cell_stats.Q_DEN)
+                        kernel_ms += (time.perf_counter() - t0) * 1e3
+                        t0 = time.perf_counter()
+                        feat = cell_stats.features(area, sums_c, order, cell_stats.Q_NUM, cell_stats.Q_DEN)
+                        kept[part].append(feat[:, :, 0].copy())
+                        files.append(f"{self.batch_id}_intensities_{part}_{number}.csv")
+                        self._write_text(files[-1], cell_stats.cells_csv(ids, types, names, area, self._marker_names(int(image.shape[0])), stats, feat))
+                        draw_ms += (time.perf_counter() - t0) * 1e3
+                image_files += files
+                cell_rows.append(np.stack([np.full(n, float(number)), ids.astype(np.float64), types.astype(np.float64), cells["status"].astype(np.float64),
+                                           cells["inner_fraction"]], axis=1).reshape(n, cell_width))
+                image_rows.append(np.concatenate([[float(number), 0.0, float(len(ids_b)), float(len(cell)), float((owner < 0).sum()), float(got["slots"])],
+                                                  counts.reshape(-1).astype(np.float64), sums]).reshape(1, image_width))
+            table, per_image = np.concatenate(cell_rows, axis=0), np.concatenate(image_rows, axis=0)
+            if integrate and self.tile_mode:
+                table, _ = self._gather_rows(table)
+                per_image, _ = self._gather_rows(per_image)
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            counts, sums = matching.add_agreement([(row[6:6 + 3 * k_thr].astype(np.int64).reshape(k_thr, 3), row[6 + 3 * k_thr:]) for row in per_image])
+            stem, tail = self._group_stem("matching", integrate, members)
+            files = [stem + "_agreement" + tail + ".csv", stem + "_summary" + tail + ".csv"]
+            self._write_text(files[0], matching.agreement_csv(matching.agreement_table(counts, sums)))
+            status = table[:, 3].astype(np.int64)
+            self._write_text(files[1], matching.summary_csv(names, matching.type_summary(table[:, 2].astype(np.int64), t, status, table[:, 4])))
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            rec = {"file": files[0], "files": files, "image_files": image_files, "n": len(table), "m": int(per_image[:, 2].sum()),
+                   "pairs": int(per_image[:, 3].sum()), "none": int((status == 0).sum()), "multi": int((status == 2).sum()),
+                   "orphans": int(per_image[:, 4].sum()), "slots": int(per_image[:, 5].max()) if len(per_image) else 0, "min_overlap": percent,
+                   "annotated": annotated, "kernel_ms": kernel_ms, "draw_ms": draw_ms}
+            self.matching_stats.append(rec)
+            self.logger.log("Mask matching {}: {} cells, {} objects of the second mask, {} overlapping pairs; {} cells without an object, {} with "
+                            "several, {} orphan objects (an owner needs {} % of its object); ops.overlap_pairs and the compartments with their copies "
+                            "{:.1f}, tables and drawing {:.1f} ms.".format(files[0], rec["n"], rec["m"], rec["pairs"], rec["none"], rec["multi"],
+                                                                           rec["orphans"], percent, kernel_ms, draw_ms))
+
     # ---- cell intensities: the marker columns of the single-cell table, over each cell's own pixels (steinbock's measure intensities) ------------
     def cell_intensities(self, integrate=True, maps=True, compartment="cell"):
         """The marker intensity table of every image: per cell and image channel the mean, population std, min, quartiles and max over the cell's

@@ -715,6 +715,125 @@ def mask_rings(mask: torch.Tensor, ids: np.ndarray, ws: Optional[torch.Tensor] =
     return {"rings": rings.cpu().numpy(), "first": first.cpu().numpy(), "vertices": vertices.cpu().numpy(), "calls": calls}
 
 
+OVERLAP_FIRST_SLOTS = 8           # a cell overlaps one or two objects of a second segmentation of the same image
+
+
+def mask_overlap_ws_bytes(h: int, w: int, n: int, slots: int) -> int:
+    return int(lib().ribca_mask_overlap_ws_bytes(int(h), int(w), int(n), int(slots)))
+
+
+def _two_masks(mask_a, mask_b, who: str):
+    if (not torch.is_tensor(mask_a) or not torch.is_tensor(mask_b) or mask_a.dtype != torch.int32 or mask_b.dtype != torch.int32 or mask_a.dim() != 2
+            or not mask_a.is_cuda or mask_b.device != mask_a.device or tuple(mask_b.shape) != tuple(mask_a.shape)):
+        raise ValueError(f"{who} takes two (H, W) int32 masks of one shape on one device")
+    a = mask_a.contiguous()
+    return a, (a if mask_b is mask_a else mask_b.contiguous())
+
+
+def _table_arg(table, device, who: str) -> torch.Tensor:
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 1:
+        raise ValueError(f"{who} takes (L) int32 label tables")
+    return table.contiguous().to(device)
+
+
+def mask_overlap(mask_a: torch.Tensor, tab_a: torch.Tensor, n: int, mask_b: torch.Tensor, tab_b: torch.Tensor, m: int, slots: int,
+                 ws: Optional[torch.Tensor] = None):
+    """(partner (n, slots) int32, inter (n, slots) int64, degree (n) int32, area_a (n) int32, area_b (m) int32, over (2) int32) device tensors of
+    ribca_mask_overlap, one attempt at ``slots`` slots per row: with over[0] == 0 row i lists the objects of ``mask_b`` that share pixels with
+    cell i of ``mask_a`` in ascending index order and the shared pixels beside them; ``tab_a`` maps the labels of ``mask_a`` to the cells
+    0 .. n - 1 and ``tab_b`` those of ``mask_b`` to the objects 0 .. m - 1; include/ribca_hip.h states the contract."""
+    mask_a, mask_b = _two_masks(mask_a, mask_b, "mask_overlap")
+    dev = mask_a.device
+    tab_a, tab_b = _table_arg(tab_a, dev, "mask_overlap"), _table_arg(tab_b, dev, "mask_overlap")
+    h, w = mask_a.shape
+    rows, objs, cols = max(int(n), 0), max(int(m), 0), max(int(slots), 0)
+    partner = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+    inter = torch.empty((rows, cols), dtype=torch.int64, device=dev)
+    degree = torch.empty((rows,), dtype=torch.int32, device=dev)
+    area_a = torch.empty((rows,), dtype=torch.int32, device=dev)
+    area_b = torch.empty((objs,), dtype=torch.int32, device=dev)
+    over = torch.empty((2,), dtype=torch.int32, device=dev)
+    ws = _ws(ws, mask_overlap_ws_bytes(h, w, n, slots), dev, "mask_overlap")
+    check(lib().ribca_mask_overlap(ptr(mask_a), ptr(mask_b), h, w, ptr(tab_a), tab_a.numel(), int(n), ptr(tab_b), tab_b.numel(), int(m), int(slots),
+                                   ptr(partner), ptr(inter), ptr(degree), ptr(area_a), ptr(area_b), ptr(over), ptr(ws), ws.numel(), stream_ptr()),
+          "ribca_mask_overlap")
+    return partner, inter, degree, area_a, area_b, over
+
+
+def _label_areas(mask: torch.Tensor, ids: np.ndarray) -> np.ndarray:
+    """the pixels of every label of ``ids`` in the mask, for the side of overlap_pairs that has a partner mask without a single object"""
+    tables = _label_tables(mask) if len(ids) else None
+    if tables is None:
+        return np.zeros(len(ids), np.int32)
+    count = tables[0][4].cpu().numpy()
+    inside = ids < len(count)
+    out = np.zeros(len(ids), np.int32)
+    out[inside] = count[ids[inside]]
+    return out
+
+
+def overlap_pairs(mask_a: torch.Tensor, ids_a, mask_b: torch.Tensor, ids_b, first_slots: int = OVERLAP_FIRST_SLOTS) -> Dict[str, np.ndarray]:
+    """The pixels every (cell, object) pair of two (H, W) int32 device masks shares: the cells are the labels ``ids_a`` of ``mask_a`` (ascending,
+    cell i = ids_a[i]), the objects the labels ``ids_b`` of ``mask_b``; both label -> index tables are built as ``contact_graph`` builds its one,
+    label 0 never a cell or an object.  Returns host arrays: ``cell``, ``obj`` int32 and ``inter`` int64, one entry per pair that shares a pixel,
+    sorted by (cell, obj); ``degree`` (n) int32, the objects a cell overlaps; ``area_a`` (n) and ``area_b`` (m) int32; and ``slots``, the row
+    length that fitted.  The table starts at ``first_slots`` slots per cell and doubles while a row overflows; ValueError when that would pass
+    1024 slots or 2 GiB -- a background region labelled as a cell is the usual cause, and the message names its mask label.  Without cells or
+    without objects there are no pairs and ribca_mask_overlap is not called: the areas of the other side come from the label table."""
+    mask_a, mask_b = _two_masks(mask_a, mask_b, "overlap_pairs")
+    ids_a, ids_b = np.asarray(ids_a, dtype=np.int64).reshape(-1), np.asarray(ids_b, dtype=np.int64).reshape(-1)
+    n, m = len(ids_a), len(ids_b)
+    if n == 0 or m == 0:
+        return {"cell": np.zeros(0, np.int32), "obj": np.zeros(0, np.int32), "inter": np.zeros(0, np.int64), "degree": np.zeros(n, np.int32),
+                "area_a": _label_areas(mask_a, ids_a), "area_b": _label_areas(mask_b, ids_b), "slots": int(first_slots)}
+    dev = mask_a.device
+    tab_a, tab_b = _cell_table(ids_a, dev), _cell_table(ids_b, dev)
+    slots = int(first_slots)
+    while True:
+        partner, inter, degree, area_a, area_b, over = mask_overlap(mask_a, tab_a, n, mask_b, tab_b, m, slots)
+        failed, lowest = over.tolist()
+        if failed == 0:
+            break
+        why = (f"overlap_pairs: {failed} cell(s) overlap more than {slots} objects of the second mask, the lowest of them mask label "
+               f"{int(ids_a[lowest])}; a background region labelled as a cell is the usual cause")
+        if slots * 2 > CONTACT_MAX_SLOTS:
+            raise ValueError(f"{why} (the table stops at {CONTACT_MAX_SLOTS} slots per cell)")
+        if 12 * n * slots * 2 > CONTACT_MAX_TABLE_BYTES:
+            raise ValueError(f"{why} (a table of {slots * 2} slots for {n} cells would pass 2 GiB)")
+        slots *= 2
+    part_h, inter_h, deg_h = partner.cpu().numpy(), inter.cpu().numpy(), degree.cpu().numpy()
+    keep = np.arange(slots)[None, :] < deg_h[:, None]      # row-major: sorted by (cell, obj)
+    return {"cell": np.repeat(np.arange(n, dtype=np.int32), deg_h), "obj": np.ascontiguousarray(part_h[keep], dtype=np.int32),
+            "inter": np.ascontiguousarray(inter_h[keep], dtype=np.int64), "degree": deg_h.astype(np.int32),
+            "area_a": area_a.cpu().numpy().astype(np.int32), "area_b": area_b.cpu().numpy().astype(np.int32), "slots": slots}
+
+
+def mask_compartments(mask_a: torch.Tensor, ids_a, mask_b: torch.Tensor, ids_b, owner) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``mask_a`` split by the objects of ``mask_b`` its cells own: ``owner`` (m) holds for every object of ``ids_b`` the index of its cell in
+    ``ids_a`` or -1.  Returns two new (H, W) int32 device tensors: ``inner`` keeps the label of ``mask_a`` on the pixels of a cell that lie in
+    an object the cell owns, ``outer`` on the other pixels of a cell; both are 0 elsewhere (include/ribca_hip.h states the contract).  Without
+    cells both are 0; without objects ``outer`` is the cells of ``mask_a``.  Does not synchronise."""
+    mask_a, mask_b = _two_masks(mask_a, mask_b, "mask_compartments")
+    ids_a, ids_b = np.asarray(ids_a, dtype=np.int64).reshape(-1), np.asarray(ids_b, dtype=np.int64).reshape(-1)
+    owner = np.ascontiguousarray(np.asarray(owner, dtype=np.int32).reshape(-1))
+    n, m = len(ids_a), len(ids_b)
+    if len(owner) != m:
+        raise ValueError(f"mask_compartments takes one owner per object, got {len(owner)} for {m} objects")
+    dev = mask_a.device
+    h, w = mask_a.shape
+    tab_a = _cell_table(ids_a, dev)
+    if n == 0 or m == 0:      # no object owns anything: the kernel's answer with one object that is nobody's
+        tab_b, owner, m = torch.full((1,), -1, dtype=torch.int32, device=dev), np.full(1, -1, np.int32), 1
+        n = max(n, 1)          # tab_a of no cells is one entry of -1: no pixel is a cell
+    else:
+        tab_b = _cell_table(ids_b, dev)
+    owner_d = torch.from_numpy(owner).to(dev)
+    inner, outer = torch.empty_like(mask_a), torch.empty_like(mask_a)
+    check(lib().ribca_mask_compartments(ptr(mask_a), ptr(mask_b), h, w, ptr(tab_a), tab_a.numel(), n, ptr(tab_b), tab_b.numel(), m, ptr(owner_d),
+                                        ptr(inner), ptr(outer), stream_ptr()), "ribca_mask_compartments")
+    return inner, outer
+
+
 INTENSITY_SMALL_BOX = 1024       # csrc/intensities.hip IN_SMALL_BOX: a clipped box of at most this many pixels is one wave's
 INTENSITY_RESIDENT = 4096         # csrc/intensities.hip IN_RESIDENT: in a larger box, a cell of more pixels takes the streaming form
 INTENSITY_MAX_CHANNELS = 64

@@ -369,6 +369,9 @@ class ImageProcessor(object):
         self.image_paths = table['image_path']
         self.mask_paths = table['mask_path']
         assert len(self.image_paths) == len(self.mask_paths)
+        # the second segmentation of every image for Annotator.mask_matching, one path per row of the batch CSV; None without the column.
+        # Nothing here reads the files
+        self.second_mask_paths = list(table['second_mask_path']) if 'second_mask_path' in table.columns else None
         self.logger = logger
         self._n_images = len(self.image_paths)
         self._log("Number of images: {}.".format(self._n_images))

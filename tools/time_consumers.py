@@ -27,7 +27,10 @@ whose composition at D = 8 is compared with the kernel's output (``--expand``: t
 (csrc/components.hip): the connected components of the same mask with 4000 injected faults, device events, the whole ops.repair_labels on the
 host clock, and scipy.ndimage.label of the same mask on the host (``--repair``: this section alone); and the cell outlines
 (csrc/outlines.hip): ribca_mask_rings and ribca_mask_ring_vertices on the same mask, device events, the whole ops.mask_rings and the GeoJSON text
-on the host clock, and the restatement of tests/outlines_numpy.py on a crop, scaled by boundary edges (``--outlines``: this section alone)."""
+on the host clock, and the restatement of tests/outlines_numpy.py on a crop, scaled by boundary edges (``--outlines``: this section alone); and the
+matching of a second mask (csrc/overlap.hip): ribca_mask_overlap and ribca_mask_compartments against a shifted copy of the same mask with labels
+dropped and merged, device events, beside ribca_contact_table at d = 1 in the same process, the whole ops.overlap_pairs and the rules of
+matching.py on the host clock, and np.unique over the 64-bit pair keys of the same two masks on the host (``--matching``: this section alone)."""
 import os
 import sys
 import time
@@ -492,6 +495,113 @@ def time_outlines():
           f"{host_ms * edges / max(crop_edges, 1) / 1e3:.1f} s scaled by boundary edges to {h}x{w}; equal to the GPU rings and vertices of the same crop: {same}")
 
 
+# ---- matching a second mask (csrc/overlap.hip, matching.py): the pair table of two masks, the compartments, the host rules --------------------------
+def time_matching():
+    """Mask B is the mask moved three columns to the right with one label in 50 dropped and one in 50 merged into the label before it.  Both masks,
+    both tables, outputs and workspace on the device before the clock starts; device events around 20 calls, the median of five such windows
+    after a warm-up, for ribca_mask_overlap, ribca_mask_compartments and, the yardstick, ribca_contact_table at d = 1 on the same mask.  Then the
+    whole ops.overlap_pairs -- label tables to the device, the kernels, the copies back -- and the rules of matching.py on the host clock, and the
+    numpy restatement, np.unique over the 64-bit pair keys of the same 16.7 M pixels, checked against the GPU's pairs."""
+    from multiplexed_image_annotator_amd import matching
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    h, w = mask.shape
+    host_a = mask.cpu().numpy()
+    host_b = np.zeros_like(host_a)
+    host_b[:, 3:] = host_a[:, :-3]
+    relabel = np.arange(int(host_a.max()) + 1, dtype=np.int32)
+    relabel[ids[49::50]] = 0                          # dropped
+    keep, gone = ids[24::50], ids[25::50]
+    relabel[gone] = keep[:len(gone)]                  # merged into the label before it in the id list
+    host_b = relabel[host_b]
+    mask_b = torch.from_numpy(host_b).to(dev)
+    ids_b = ops.label_table(mask_b)[0]
+    m, slots = len(ids_b), ops.OVERLAP_FIRST_SLOTS
+    tab_a, tab_b = ops._cell_table(ids, dev), ops._cell_table(ids_b, dev)
+    partner = torch.empty((n, slots), dtype=torch.int32, device=dev)
+    inter = torch.empty((n, slots), dtype=torch.int64, device=dev)
+    degree, area_a = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+    area_b = torch.empty((m,), dtype=torch.int32, device=dev)
+    over = torch.empty((2,), dtype=torch.int32, device=dev)
+    ws = torch.empty(ops.mask_overlap_ws_bytes(h, w, n, slots), dtype=torch.uint8, device=dev)
+    c_slots = 32
+    nbr, c_pairs = torch.empty((n, c_slots), dtype=torch.int32, device=dev), torch.empty((n, c_slots), dtype=torch.int64, device=dev)
+    c_ws = torch.empty(ops.contact_table_ws_bytes(h, w, n, c_slots), dtype=torch.uint8, device=dev)
+    inner, outer = torch.empty_like(mask), torch.empty_like(mask)
+    g = ops.overlap_pairs(mask, ids, mask_b, ids_b)
+    owner, inside = matching.owners(g["cell"], g["obj"], g["inter"], g["area_b"])
+    owner_d = torch.from_numpy(owner).to(dev)
+
+    def overlap():
+        _lib.check(lib().ribca_mask_overlap(ptr(mask), ptr(mask_b), h, w, ptr(tab_a), tab_a.numel(), n, ptr(tab_b), tab_b.numel(), m, slots, ptr(partner),
+                                            ptr(inter), ptr(degree), ptr(area_a), ptr(area_b), ptr(over), ptr(ws), ws.numel(), stream_ptr()), "overlap")
+
+    def compartments():
+        _lib.check(lib().ribca_mask_compartments(ptr(mask), ptr(mask_b), h, w, ptr(tab_a), tab_a.numel(), n, ptr(tab_b), tab_b.numel(), m, ptr(owner_d),
+                                                 ptr(inner), ptr(outer), stream_ptr()), "compartments")
+
+    def contact():
+        _lib.check(lib().ribca_contact_table(ptr(mask), h, w, ptr(tab_a), tab_a.numel(), n, 1, c_slots, ptr(nbr), ptr(c_pairs), ptr(degree), ptr(over),
+                                             ptr(c_ws), c_ws.numel(), stream_ptr()), "contact")
+
+    def events(fn, calls=20, windows=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(windows):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(calls):
+                fn()
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) / calls)
+        return f"median {sorted(times)[windows // 2]:.3f} ms per call, min {min(times):.3f}, max {max(times):.3f} of {windows} windows of {calls} calls"
+
+    hbm_ms = 2 * h * w * 4 / 6.29e12 * 1e3      # one read of both masks at the measured HBM copy rate DESIGN.md quotes
+    for kind in ("first", "second"):              # the three alternate, twice: the spread between the rounds is the noise
+        print(f"{kind} round: ribca_mask_overlap, {slots} slots ({ws.numel() / 2 ** 20:.1f} MiB workspace): {events(overlap)}")
+        print(f"{kind} round: ribca_contact_table, d = 1, {c_slots} slots ({c_ws.numel() / 2 ** 20:.1f} MiB workspace): {events(contact)}")
+        print(f"{kind} round: ribca_mask_compartments: {events(compartments)}")
+    overlap()
+    torch.cuda.synchronize()
+    print(f"{n} cells, {m} objects, {len(g['cell'])} pairs, largest degree {int(g['degree'].max())}, overflow {over.tolist()}, {h}x{w}; one read of both "
+          f"masks at 6.29 TB/s: {hbm_ms:.4f} ms; the compartments read two masks and write two: {2 * hbm_ms:.4f} ms")
+    times = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        g = ops.overlap_pairs(mask, ids, mask_b, ids_b)
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"whole ops.overlap_pairs (tables up, kernels, copies back, the pair list): median {sorted(times)[2]:.1f} ms, min {min(times):.1f}, max {max(times):.1f} of 5")
+    t0 = time.perf_counter()
+    owner, inside = matching.owners(g["cell"], g["obj"], g["inter"], g["area_b"])
+    cells = matching.cell_rows(g["cell"], g["obj"], g["inter"], g["area_a"], ids_b, owner)
+    objects = matching.object_rows(g["cell"], g["obj"], g["inter"], g["area_b"], ids, owner, inside)
+    union, iou = matching.pair_rows(g["cell"], g["obj"], g["inter"], g["area_a"], g["area_b"])
+    counts, sums = matching.agreement_counts(g["cell"], g["obj"], g["inter"], g["area_a"], g["area_b"])
+    rules_ms = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    texts = (matching.cells_csv(ids, cells), matching.objects_csv(ids_b, objects), matching.pairs_csv(ids, ids_b, g["cell"], g["obj"], g["inter"], union, iou))
+    text_ms = 1e3 * (time.perf_counter() - t0)
+    table = matching.agreement_table(counts, sums)
+    print(f"matching.py on the host: owners, cell, object and pair rows, agreement {rules_ms:.0f} ms; the three CSV texts ({sum(len(t) for t in texts) / 1e6:.1f} MB) "
+          f"{text_ms:.0f} ms; cells none / single / multi {np.bincount(cells['status'], minlength=3).tolist()}, orphans {int((owner < 0).sum())}, "
+          f"tp at IoU 0.5 / 0.75 / 0.95: {int(table[0, 2])} / {int(table[5, 2])} / {int(table[9, 2])}, PQ at 0.5 {table[0, 9]:.4f}")
+    t0 = time.perf_counter()
+    ta, tb = ops._cell_table(ids), ops._cell_table(ids_b)
+    ca, cb = ta[host_a].astype(np.int64), tb[host_b].astype(np.int64)
+    both = (ca >= 0) & (cb >= 0)
+    keys, count = np.unique((ca[both] << 32) | cb[both], return_counts=True)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    same = (np.array_equal(keys >> 32, g["cell"]) and np.array_equal(keys & 0xFFFFFFFF, g["obj"]) and np.array_equal(count, g["inter"])
+            and np.array_equal(np.bincount(ca[ca >= 0], minlength=n), g["area_a"]) and np.array_equal(np.bincount(cb[cb >= 0], minlength=m), g["area_b"]))
+    print(f"numpy restatement (host): both tables applied and np.unique over {int(both.sum())} 64-bit pair keys {host_ms:.0f} ms; equal to the GPU pairs and areas: {same}")
+
+
+if "--matching" in sys.argv:      # this section alone
+    time_matching()
+    sys.exit(0)
 if "--outlines" in sys.argv:      # this section alone
     time_outlines()
     sys.exit(0)
@@ -716,3 +826,6 @@ time_intensities()
 time_expand()
 time_repair()
 time_outlines()
+
+# ---- matching a second mask: defined above as well ----------------------------------------------------------------------------------------------
+time_matching()
