@@ -7,6 +7,17 @@ import enrichment_numpy as EN
 
 CHUNK = 256
 
+#: (n, C, m) of the kernel tests: the smallest cases; both sides of the chunk of 256 cells; a second chunk of one cell; a channel count across
+#: the tile of 16; the widest panel; 17 chunks
+SHAPES = [(2, 1, 1), (5, 3, 4), (255, 1, 24), (256, 2, 31), (257, 15, 24), (300, 17, 8), (1000, 64, 3), (4097, 15, 24)]
+
+
+def random_table(n, c, m, seed=0):
+    """a centred-looking table with channels of very different scale, and a random neighbour list (any cell may stand in any list)"""
+    rng = np.random.RandomState(n + c + m + seed)
+    z = rng.randn(n, c) * 10.0 ** rng.uniform(-3, 3, c)
+    return z - z.mean(axis=0), rng.randint(0, n, (n, m))
+
 
 def tree(v):
     """(n, C) -> (C): chunks of 256 cells padded with +0.0, eight rounds of adjacent pairs, then the chunks added from +0.0 in ascending order"""

@@ -2,7 +2,6 @@
 names against literal values, the rank gate, the ranges of a permutation null, the packing of the tile-per-rank count all-reduce, and the
 row exchange of cell_morphology / cell_intensities under a two-rank gloo group.  No GPU needed."""
 import os
-import socket
 from types import SimpleNamespace
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from batch_harness import free_port
 from multiplexed_image_annotator_amd import analyses
 
 
@@ -123,14 +123,6 @@ def test_all_reduce_counts_splits_a_summed_buffer(monkeypatch):
         assert got.dtype == np.int64 and got.shape == want.shape and np.array_equal(got, 2 * want)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _row_cases():
     """(name, cells per image) with image i on rank i % 2, as tile-per-rank mode deals them"""
     return [("unequal", [5, 3, 2]), ("one rank without rows", [4, 0, 6]), ("all empty", [0, 0, 0])]
@@ -167,7 +159,7 @@ def _gather_worker(rank, world, port, out):
 def test_gather_rows_gloo_world2():
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_gather_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    mp.spawn(_gather_worker, args=(2, free_port(), out), nprocs=2, join=True)
     assert dict(out) == {0: [True] * 6, 1: [True] * 6}
 
 

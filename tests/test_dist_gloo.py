@@ -1,19 +1,12 @@
 """N>1 path on CPU: world_size-2 gloo group, sharding + the all-gather of per-cell rows (the only data-path exchange)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from batch_harness import free_port
 
 
 def _worker(rank, world, port, golden_dir, out):
@@ -51,7 +44,7 @@ def test_shard_bounds_properties():
 
 
 def test_all_gather_rows_gloo_world2(golden_dir):
-    port = _free_port()
+    port = free_port()
     mgr = mp.Manager()
     out = mgr.dict()
     mp.spawn(_worker, args=(2, port, golden_dir, out), nprocs=2, join=True)
@@ -75,7 +68,7 @@ def test_all_gather_rows_group_of_one_forced_collective():
     """the path tests/test_gpu_rccl_single_rank.py drives through RCCL, here through gloo"""
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_worker_single, args=(1, _free_port(), out), nprocs=1, join=True)
+    mp.spawn(_worker_single, args=(1, free_port(), out), nprocs=1, join=True)
     assert dict(out) == {0: True}
 
 
@@ -104,7 +97,7 @@ def _worker_modes(rank, world, port, out):
 def test_planes_and_tile_mode_reductions_gloo_world2():
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_worker_modes, args=(2, _free_port(), out), nprocs=2, join=True)
+    mp.spawn(_worker_modes, args=(2, free_port(), out), nprocs=2, join=True)
     assert dict(out) == {0: True, 1: True}
 
 

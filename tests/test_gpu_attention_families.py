@@ -33,8 +33,7 @@ import pytest
 import torch
 
 import attention_families as af
-from test_gpu_guards import Arena
-from test_gpu_kernels import _fold, _ln_case, _row_stats, ps_decode, ps_encode, rnd
+from kernel_harness import Arena, fold_weight, ln_case, ps_decode, ps_encode, rnd, row_stats
 
 pytestmark = pytest.mark.gpu
 
@@ -82,9 +81,9 @@ def _case(d, heads, fold, family, mmax, dev):
     dp = (d + 31) // 32 * 32
     w, bias = af.apply_family(family, rnd((3 * d, d), seed + 3, dev, 1.0 / math.sqrt(d)), rnd((3 * d,), seed + 4, dev, 0.1), d)
     if fold:
-        rows, zq, g, b, _ = _ln_case(mmax, d, seed, dev, 0.5, 1.0)
-        w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-        rs = _row_stats(rows, dp, mmax, d, dev)
+        rows, zq, g, b, _ = ln_case(mmax, d, seed, dev, 0.5, 1.0)
+        w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+        rs = row_stats(rows, dp, mmax, d, dev)
         x = torch.nn.functional.layer_norm(zq, (d,), None, None, 1e-6)      # gain and shift live in the folded weight and bias2
     else:
         rows = ps_encode(rnd((mmax, d), seed, dev), dp)

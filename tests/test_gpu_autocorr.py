@@ -3,7 +3,6 @@ for bit (workspace and outputs pre-filled with junk), batch edges, split invaria
 Annotator.spatial_autocorrelation() end to end: files, the CSV against the oracle computed from the same tables, the PNG rectangle against the
 rasteriser, reruns, seeds, per-image files, two ranks."""
 import io
-import json
 import os
 
 import numpy as np
@@ -12,23 +11,12 @@ import torch
 
 import autocorr_numpy as AN
 import enrichment_numpy as EN
+from batch_harness import cli_runs, preprocessed, result_files, run_annotator, two_image_case, two_ranks
+from kernel_harness import junk
 from multiplexed_image_annotator_amd import _lib, autocorr, colors, ops
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
-
-
-def _junk(nbytes, dev):
-    return torch.full((max(int(nbytes), 1),), 255, dtype=torch.uint8, device=dev)      # as doubles: NaN
-
-
-def _table(n, c, m, seed=0):
-    """a centred-looking table with channels of very different scale, and a random neighbour list (any cell may stand in any list)"""
-    rng = np.random.RandomState(n + c + m + seed)
-    z = rng.randn(n, c) * 10.0 ** rng.uniform(-3, 3, c)
-    return z - z.mean(axis=0), rng.randint(0, n, (n, m))
 
 
 def _gpu_observed(z, idx):
@@ -37,8 +25,8 @@ def _gpu_observed(z, idx):
     zd = torch.from_numpy(np.ascontiguousarray(z)).to(dev)
     idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
     need = ops.autocorr_observed_ws_bytes(n, c)
-    ws = _junk(need, dev)
-    out = _junk(2 * c * 8, dev).view(torch.float64).reshape(2, c)
+    ws = junk(need, dev)
+    out = junk(2 * c * 8, dev).view(torch.float64).reshape(2, c)
     status = lib().ribca_autocorr_observed(ptr(zd), ptr(idx_d), n, c, idx.shape[1], ptr(out), ptr(ws), need, stream_ptr())
     torch.cuda.synchronize()
     return status, out.cpu().numpy()
@@ -50,8 +38,8 @@ def _gpu_perm(z, idx, seed, image, p0, p):
     zd = torch.from_numpy(np.ascontiguousarray(z)).to(dev)
     idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
     need = ops.autocorr_perm_ws_bytes(n, c, p)
-    ws = _junk(need, dev)
-    out = _junk(p * 2 * c * 8, dev).view(torch.float64).reshape(p, 2, c)
+    ws = junk(need, dev)
+    out = junk(p * 2 * c * 8, dev).view(torch.float64).reshape(p, 2, c)
     status = lib().ribca_autocorr_perm(ptr(zd), ptr(idx_d), n, c, idx.shape[1], seed, image, p0, p, ptr(out), ptr(ws), need, stream_ptr())
     torch.cuda.synchronize()
     return status, out.cpu().numpy()
@@ -61,14 +49,9 @@ def _same_bits(a, b):
     return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
-#: (n, C, m): the smallest cases; both sides of the chunk of 256 cells; a second chunk of one cell; a channel count across the tile of 16; the
-#: widest panel; 17 chunks
-SHAPES = [(2, 1, 1), (5, 3, 4), (255, 1, 24), (256, 2, 31), (257, 15, 24), (300, 17, 8), (1000, 64, 3), (4097, 15, 24)]
-
-
-@pytest.mark.parametrize("n,c,m", SHAPES)
+@pytest.mark.parametrize("n,c,m", AN.SHAPES)
 def test_bit_equal_to_numpy(n, c, m):
-    z, idx = _table(n, c, m)
+    z, idx = AN.random_table(n, c, m)
     status, got = _gpu_observed(z, idx)
     assert status == 0, lib().ribca_last_error()
     assert _same_bits(got, AN.observed(z, idx)), (n, c, m)
@@ -81,20 +64,20 @@ def test_bit_equal_to_numpy(n, c, m):
 
 def test_batch_edges():
     # more permutations than one batch of rows holds (32)
-    z, idx = _table(300, 5, 6)
+    z, idx = AN.random_table(300, 5, 6)
     status, got = _gpu_perm(z, idx, 2, 1, 0, 33)
     assert status == 0 and _same_bits(got, AN.perm(z, idx, 2, 1, 0, 33))
     # the byte rule: 64 MiB of rows hold 14 permutations of 9000 cells x 64 channels, P = 15 takes a batch of 14 and one of 1
     n, c, m, p = 9000, 64, 3, 15
     rows = ops.autocorr_perm_ws_bytes(n, c, p) - (36 * 14 * 2 * c * 8 + 255) // 256 * 256
     assert rows == 14 * n * c * 8 and rows <= 64 << 20 < 15 * n * c * 8
-    z, idx = _table(n, c, m)
+    z, idx = AN.random_table(n, c, m)
     status, got = _gpu_perm(z, idx, 0, 0, 0, p)
     assert status == 0 and _same_bits(got, AN.perm(z, idx, 0, 0, 0, p))
 
 
 def test_split_invariance_and_repeatability():
-    z, idx = _table(700, 15, 24)
+    z, idx = AN.random_table(700, 15, 24)
     status, all7 = _gpu_perm(z, idx, 4, 2, 0, 7)
     assert status == 0
     status, last2 = _gpu_perm(z, idx, 4, 2, 5, 2)
@@ -109,7 +92,7 @@ def test_split_invariance_and_repeatability():
     zd, idx_d = torch.from_numpy(z).to(dev), torch.from_numpy(idx.astype(np.int32)).to(dev)
     assert _same_bits(ops.autocorr_observed(zd, idx_d).cpu().numpy(), o1)
     assert _same_bits(ops.autocorr_perm(zd, idx_d, 4, 2, 0, 7).cpu().numpy(), all7)
-    ws = _junk(ops.autocorr_perm_ws_bytes(700, 15, 7), dev)
+    ws = junk(ops.autocorr_perm_ws_bytes(700, 15, 7), dev)
     assert _same_bits(ops.autocorr_perm(zd, idx_d, 4, 2, 0, 7, ws=ws).cpu().numpy(), all7)
     assert not _same_bits(ops.autocorr_perm(zd, idx_d, 4, 3, 0, 7).cpu().numpy(), all7)
     assert not _same_bits(ops.autocorr_perm(zd, idx_d, 5, 2, 0, 7).cpu().numpy(), all7)
@@ -121,7 +104,7 @@ def test_split_invariance_and_repeatability():
 
 def test_neighbours_out_of_range_are_skipped():
     n, c, m = 300, 3, 6
-    z, idx = _table(n, c, m)
+    z, idx = AN.random_table(n, c, m)
     idx[7, 2], idx[9, 0], idx[11, 5], idx[299, 3] = n, -1, 2 ** 31 - 1, -(2 ** 31)
     idx[20] = -1      # a cell without a neighbour: s = g = +0.0
     s, g = np.zeros((n, c)), np.zeros((n, c))
@@ -139,11 +122,11 @@ def test_neighbours_out_of_range_are_skipped():
 
 def test_refusals_are_a_status_and_nothing_runs():
     dev = _lib.require_gpu()
-    z, idx = _table(100, 3, 24)
+    z, idx = AN.random_table(100, 3, 24)
     zd, idx_d = torch.from_numpy(z).to(dev), torch.from_numpy(idx.astype(np.int32)).to(dev)
     out = torch.full((2, 2, 3), -1.0, dtype=torch.float64, device=dev)
     need = ops.autocorr_perm_ws_bytes(100, 3, 2)
-    ws = _junk(need, dev)
+    ws = junk(need, dev)
     assert lib().ribca_autocorr_perm(ptr(zd), ptr(idx_d), 100, 3, 24, 0, 0, 0, 2, ptr(out), ptr(ws), need - 1, stream_ptr()) == 1
     assert lib().ribca_last_error() == b"ribca_autocorr_perm: workspace too small"
     assert lib().ribca_autocorr_perm(ptr(zd), ptr(idx_d), 100, 3, 32, 0, 0, 0, 2, ptr(out), ptr(ws), need, stream_ptr()) == 1
@@ -158,20 +141,6 @@ def test_refusals_are_a_status_and_nothing_runs():
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------------------------
 P_TEST = 12
-
-
-def _preprocessed(root, out, batch="x"):
-    """preprocess() only: the step needs no classifier (the batch of the tests below went through the whole runner, predict() included)"""
-    from multiplexed_image_annotator_amd.annotator import Annotator
-    a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", out, batch, False, False, -1, True, 0.3, 99.8, 0.0, 30,
-                  None)
-    a.preprocess()
-    return a
-
-
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "spatial_autocorr" in f}
 
 
 def _analyse(a):
@@ -192,9 +161,9 @@ def batch(tmp_path_factory):
     os.makedirs(root)
     two_image_case(root)
     out = str(tmp / "one")
-    a = _run(root, out, -1, 0.0)
+    a = run_annotator(root, out, -1, 0.0)
     integrated = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "a": a, "out": out, "integrated": integrated, "files": _files(out)}
+    return {"root": root, "tmp": str(tmp), "a": a, "out": out, "integrated": integrated, "files": result_files(out, "spatial_autocorr")}
 
 
 def _oracle(a, images, seed, p, k=25):
@@ -251,12 +220,12 @@ def test_files_and_table_are_the_oracle_s(batch):
 
 def test_a_second_run_writes_the_same_bytes_and_a_seed_changes_the_null(batch, monkeypatch):
     out = os.path.join(batch["tmp"], "two")
-    b = _preprocessed(batch["root"], out)
+    b = preprocessed(batch["root"], out)
     _analyse(b)
-    assert len(b.annotations) == 0 and _files(out) == batch["files"]      # no predict(): the step needs none, and writes the same bytes without
+    assert len(b.annotations) == 0 and result_files(out, "spatial_autocorr") == batch["files"]      # no predict(): the step needs none, and writes the same bytes without
     monkeypatch.setenv("RIBCA_AUTOCORR_SEED", "5")
     b.spatial_autocorrelation(n_perms=P_TEST, integrate=True)
-    seeded = _files(out)
+    seeded = result_files(out, "spatial_autocorr")
     name = "x_integrated_spatial_autocorr.csv"
     assert seeded[name] != batch["files"][name] and b.autocorr_stats[0]["seed"] == 5
     cut = lambda text: [l.split(",")[:3] + l.split(",")[8:9] for l in text.decode().strip().split("\n")]      # marker, cells, I and C stay
@@ -274,7 +243,7 @@ def test_errors_leave_the_files_alone(batch):
         a.spatial_autocorrelation(n_neighbors=100000, n_perms=2)
     with pytest.raises(_lib.RibcaError, match="k must be in"):
         a.spatial_autocorrelation(n_neighbors=33, n_perms=2, integrate=False)
-    assert _files(batch["out"]) == batch["files"]
+    assert result_files(batch["out"], "spatial_autocorr") == batch["files"]
     from multiplexed_image_annotator_amd.annotator import Annotator
     fresh = Annotator(os.path.join(batch["root"], "markers.txt"), os.path.join(batch["root"], "images.csv"), "cuda", os.path.join(batch["tmp"], "fresh"), "x",
                       False, False, -1, True, 0.3, 99.8, 0.0, 30, None)
@@ -285,53 +254,21 @@ def test_errors_leave_the_files_alone(batch):
 def test_pipeline_switch(tmp_path):
     """--autocorr-perms 0 (the default) writes no such file; N > 0 writes the integrated pair beside the neighbourhood matrix"""
     import main as cli
-    root = str(tmp_path / "case")
-    planted_case(root, n_cells=150, h=256, w=300)
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
-        os.makedirs(mdir)
-        for m, sd in _weights().items():
-            torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
-        common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
-                  os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
-        cli.main(common + ["--main-dir", str(tmp_path / "off")])
-        cli.main(common + ["--main-dir", str(tmp_path / "on"), "--autocorr-perms", "8"])
-    finally:
-        os.chdir(cwd)
-    off, on = sorted(os.listdir(tmp_path / "off" / "results")), sorted(os.listdir(tmp_path / "on" / "results"))
-    assert not [f for f in off if "autocorr" in f]
+    listing, common = cli_runs(tmp_path, {"off": [], "on": ["--autocorr-perms", "8"]}, "autocorr")
+    on = listing["on"]
     assert [f for f in on if "autocorr" in f] == ["c_integrated_spatial_autocorr.csv", "c_integrated_spatial_autocorr.png"]
-    assert [f for f in on if "autocorr" not in f] == off
     assert cli.parse_args(common + ["--main-dir", "x"]).autocorr_perms == 0
 
 
-def _rank_worker(rank, world, port, root):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
+def _rank_body(rank, root):
     os.environ["RIBCA_SHARE_GPU"] = "1"
-    os.environ.pop("RIBCA_AUTOCORR_SEED", None)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    a = _run(root, os.path.join(root, "tiles"), -1, 0.0)
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, 0.0)
     assert a.tile_mode
     _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([s["file"] for s in a.autocorr_stats], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [s["file"] for s in a.autocorr_stats]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], unset=("RIBCA_AUTOCORR_SEED",))
+    assert result_files(os.path.join(batch["root"], "tiles"), "spatial_autocorr") == batch["files"]
     assert wrote == [["x_spatial_autocorr_0.png"], ["x_spatial_autocorr_1.png"]]      # the per-image call came last

@@ -3,7 +3,6 @@ with 0xFF), and Annotator.generate_heatmap() / cell_type_composition() end to en
 against the reference's formulas, PNG rectangles against the numpy rasters of the CSV values, reruns, two ranks in either sharding."""
 import collections
 import ctypes
-import json
 import os
 
 import numpy as np
@@ -11,9 +10,9 @@ import pytest
 import torch
 
 import celltype_numpy as CN
+from batch_harness import annotated_batch, load_config1, planted_case, result_files, run_annotator, two_ranks, weights, write_case
 from multiplexed_image_annotator_amd import _lib, colors, ops, plots
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_extra_cell_types import _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -209,18 +208,6 @@ def test_pie_raster_bit_equal_to_numpy(counts):
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------------------------
-def two_image_case(root):
-    """two planted images of different sizes in one batch CSV"""
-    planted_case(os.path.join(root, "a"))
-    planted_case(os.path.join(root, "b"), n_cells=250, h=320, w=360)
-    with open(os.path.join(root, "markers.txt"), "w") as f:
-        f.write(open(os.path.join(root, "a", "markers.txt")).read())
-    with open(os.path.join(root, "images.csv"), "w") as f:
-        f.write("image_path,mask_path\n")
-        for d in ("a", "b"):
-            f.write(f"{os.path.join(root, d, 'img.npy')},{os.path.join(root, d, 'mask.npy')}\n")
-
-
 def _plot_all(a):
     """the four calls; every one returns None"""
     assert a.generate_heatmap(integrate=True) is None
@@ -232,11 +219,7 @@ def _plot_all(a):
     return integrated, pies
 
 
-def _plot_files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "heatmap" in f or "composition" in f}
-
-
+NEEDLES = ("heatmap", "composition")
 EXPECTED = sorted([f"x_{stem}.{ext}" for stem in ("Integrated_heatmap", "heatmap_0", "heatmap_1", "integrated_cell-type_composition",
                                                   "cell-type_composition_0", "cell-type_composition_1") for ext in ("png", "csv")])
 
@@ -244,16 +227,9 @@ EXPECTED = sorted([f"x_{stem}.{ext}" for stem in ("Integrated_heatmap", "heatmap
 @pytest.fixture(scope="module")
 def batch(tmp_path_factory):
     """the two-image batch annotated once, with a confidence threshold at the median so that "Others" is one of the cell types, and plotted"""
-    tmp = tmp_path_factory.mktemp("plots")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated, pies = _plot_all(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "pies": pies, "files": _plot_files(out)}
+    b = annotated_batch(tmp_path_factory, "plots", _plot_all, NEEDLES)
+    b["integrated"], b["pies"] = b["integrated"]
+    return b
 
 
 def _read_heatmap_csv(text):
@@ -329,27 +305,27 @@ def test_compositions_end_to_end(batch):
         _check_pie(a, files, f"x_cell-type_composition_{i}", [i], a.composition_stats[i])
     # reduction=False changes the legend (the reference's raw count x 100), not the disc or the CSV
     a.cell_type_composition(reduction=False, integrate=True)
-    again = _plot_files(batch["out"])
+    again = result_files(batch["out"], NEEDLES)
     stem = "x_integrated_cell-type_composition"
     assert again[stem + ".csv"] == files[stem + ".csv"] and again[stem + ".png"] != files[stem + ".png"]
     _check_pie(a, again, stem, [0, 1], a.composition_stats[0])
     a.cell_type_composition(integrate=True)
-    assert _plot_files(batch["out"]) == files
+    assert result_files(batch["out"], NEEDLES) == files
 
 
 def test_a_second_run_writes_the_same_bytes(batch):
     out = os.path.join(batch["tmp"], "two")
-    b = _run(batch["root"], out, -1, batch["thr"])
+    b = run_annotator(batch["root"], out, -1, batch["thr"])
     _plot_all(b)
-    assert _plot_files(out) == batch["files"]
+    assert result_files(out, NEEDLES) == batch["files"]
 
 
 def test_additional_types_get_a_row(batch):
     out = os.path.join(batch["tmp"], "extra")
-    a = _run(batch["root"], out, 20, batch["thr"])
+    a = run_annotator(batch["root"], out, 20, batch["thr"])
     assert any(n.startswith("Additional type") for n in a.cell_types)
     integrated, pies = _plot_all(a)
-    files = _plot_files(out)
+    files = result_files(out, NEEDLES)
     head, names, means, cells = _read_heatmap_csv(files["x_Integrated_heatmap.csv"].decode())
     assert any(n.startswith("Additional type") for n in names) and names == sorted(names)
     _check_heatmap(a, files, "x_Integrated_heatmap", [0, 1], integrated[0])
@@ -359,8 +335,6 @@ def test_additional_types_get_a_row(batch):
 def test_config1_heatmap_matches_the_reference_golden(golden_dir, tmp_path):
     """the heat-map table of BASELINE config 1's stand-in against np.mean over the reference run's own intensity rows grouped by its own labels"""
     from multiplexed_image_annotator_amd.annotator import Annotator
-    from test_gpu_e2e import write_case
-    from test_oracle_e2e import load_config1
     meta, arrs, raw, mask, weights, mf = load_config1(golden_dir, tmp_path)
     _, csv = write_case(tmp_path, raw, mask, meta["markers"])
     a = Annotator(mf, csv, "cuda", str(tmp_path), "c1", True, False, -1, True, meta["blur"], meta["amax"], meta["conf"], 30, None)
@@ -403,7 +377,7 @@ def test_pipeline_leaves_both_integrated_figures(tmp_path):
     try:
         mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
         os.makedirs(mdir)
-        for m, sd in _weights().items():
+        for m, sd in weights().items():
             torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
         cli.main(["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
                   os.path.join(root, "mask.npy"), "--batch-id", "c", "--main-dir", str(tmp_path / "out"), "--no-infer", "--bs", "16", "--confidence", "0.0"])
@@ -415,34 +389,19 @@ def test_pipeline_leaves_both_integrated_figures(tmp_path):
         assert (res / f).exists(), f
 
 
-def _rank_worker(rank, world, port, root, thr, tile):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1" if tile else "0"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
+def _rank_body(rank, root, thr, tile):
     out = os.path.join(root, "tiles" if tile else "sharded")
-    a = _run(root, out, -1, thr)
+    a = run_annotator(root, out, -1, thr)
     assert a.tile_mode == bool(tile)
     _plot_all(a)
-    with open(os.path.join(root, f"{'tiles' if tile else 'sharded'}_rank{rank}.json"), "w") as f:
-        json.dump({"heatmaps": [s["file"] for s in a.heatmap_stats], "pies": [s["file"] for s in a.composition_stats]}, f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return {"heatmaps": [s["file"] for s in a.heatmap_stats], "pies": [s["file"] for s in a.composition_stats]}
 
 
 @pytest.mark.parametrize("tile", [0, 1], ids=["cell-sharded", "tile-per-rank"])
 def test_two_ranks_write_the_single_rank_bytes(batch, tile):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"], tile), nprocs=2, join=True)
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"], tile, tile=tile)
     name = "tiles" if tile else "sharded"
-    assert _plot_files(os.path.join(batch["root"], name)) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"{name}_rank{r}.json"))) for r in (0, 1)]
+    assert result_files(os.path.join(batch["root"], name), NEEDLES) == batch["files"]
     if tile:      # the per-image figures come from the rank that owns the image (after the calls of _plot_all: the per-image ones are the last)
         assert wrote[0] == {"heatmaps": ["x_heatmap_0.png"], "pies": ["x_cell-type_composition_0.png"]}
         assert wrote[1] == {"heatmaps": ["x_heatmap_1.png"], "pies": ["x_cell-type_composition_1.png"]}

@@ -29,8 +29,7 @@ import pytest
 import torch
 
 from multiplexed_image_annotator_amd import synth
-from test_gpu_guards import Arena
-from test_gpu_kernels import _fold, _ln_case, _row_stats, ps_decode, ps_encode, rnd
+from kernel_harness import Arena, fold_weight, ln_case, ps_decode, ps_encode, rnd, row_stats
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +75,7 @@ def _case(d, family, dev):
     cells = max(_cell_counts())
     m = cells * T
     hd = d // HEADS
-    z_ps, zq, g, b, dp = _ln_case(m, d, 300 + d, dev, 0.5, 1.0)
+    z_ps, zq, g, b, dp = ln_case(m, d, 300 + d, dev, 0.5, 1.0)
     w = rnd((3 * d, d), 303 + d, dev, 1.0 / math.sqrt(d))
     bias = rnd((3 * d,), 304 + d, dev, 0.1)
     if family == "heavy":
@@ -93,8 +92,8 @@ def _case(d, family, dev):
     elif family == "spike":
         w[d:2 * d] = 400.0 * w[:d]
         bias[:d] = 0.0
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     # ---- fp64 on the rounded inputs: y = LayerNorm without gain / shift, the folded weight as the kernels hold it
     y = torch.nn.functional.layer_norm(zq, (d,), None, None, 1e-6).reshape(cells, T, d)
     wq = ps_decode(w_ps, d)[:3 * d]

@@ -5,7 +5,6 @@ than a workgroup's table holds, the retry and the overflow report; the null over
 Annotator.contact_analysis() end to end: files, tables against the restatement run on the same masks and labels, reruns, the pipeline switch,
 two ranks."""
 import io
-import json
 import os
 
 import numpy as np
@@ -13,10 +12,9 @@ import pytest
 import torch
 
 import contact_numpy as CN
+from batch_harness import MARKERS, SEED, annotated_batch, cli_runs, result_files, run_annotator, two_ranks
 from multiplexed_image_annotator_amd import _lib, colors, contact, enrichment, ops, synth
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import MARKERS, SEED, _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -265,11 +263,6 @@ REACH = 3
 PERMS = 6
 
 
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "_contact" in f}
-
-
 def _analyse(a):
     assert a.contact_analysis(distance=REACH, n_perms=PERMS, integrate=True) is None
     integrated = list(a.contact_stats)
@@ -280,16 +273,7 @@ def _analyse(a):
 @pytest.fixture(scope="module")
 def batch(tmp_path_factory):
     """the two-image batch of the cell-type plots, annotated once with "Others" among the cell types, and analysed"""
-    tmp = tmp_path_factory.mktemp("contact")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "files": _files(out)}
+    return annotated_batch(tmp_path_factory, "contact", _analyse, "_contact")
 
 
 def _restated_graph(a, i):
@@ -380,19 +364,19 @@ def test_files_tables_and_maps_are_the_restatement_s(batch):
 
 def test_a_second_run_writes_the_same_bytes_and_no_null_means_no_z_files(batch, monkeypatch):
     out = os.path.join(batch["tmp"], "two")
-    b = _run(batch["root"], out, -1, batch["thr"])
+    b = run_annotator(batch["root"], out, -1, batch["thr"])
     b.contact_analysis(distance=REACH, integrate=False)
-    got = _files(out)
+    got = result_files(out, "_contact")
     assert sorted(got) == sorted(f for f in batch["files"] if "integrated" not in f and f not in [f"x_contact_{i}.{e}" for i in (0, 1) for e in ("csv", "png")])
     assert got["x_contact_table_0.csv"].decode().split("\n")[0] == "cell_type,neighbour,edges,pixel_pairs" and b.contact_stats[0]["P"] == 0
     assert all(got[f] == batch["files"][f] for f in got if "_table_" not in f)
     _analyse(b)
-    assert _files(out) == batch["files"]
+    assert result_files(out, "_contact") == batch["files"]
     # the seed moves the null and nothing else
     monkeypatch.setenv("RIBCA_CONTACT_SEED", "5")
     b.contact_analysis(distance=REACH, n_perms=PERMS, integrate=True)
     assert b.contact_stats[0]["seed"] == 5
-    seeded = _files(out)
+    seeded = result_files(out, "_contact")
     name = "x_integrated_contact_table.csv"
     rows, base = seeded[name].decode().split("\n"), batch["files"][name].decode().split("\n")
     assert [r.split(",")[:4] for r in rows] == [r.split(",")[:4] for r in base] and rows != base
@@ -405,7 +389,7 @@ def test_errors_leave_the_files_alone(batch):
         a.contact_analysis(distance=9)
     with pytest.raises(ValueError, match="must not be negative"):
         a.contact_analysis(n_perms=-1)
-    assert _files(batch["out"]) == batch["files"]
+    assert result_files(batch["out"], "_contact") == batch["files"]
     from multiplexed_image_annotator_amd.annotator import Annotator
     root = batch["root"]
     fresh = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", os.path.join(batch["tmp"], "fresh"), "x", False, False,
@@ -417,29 +401,13 @@ def test_errors_leave_the_files_alone(batch):
 def test_pipeline_switch(tmp_path):
     """--contact-distance 0 (the default) writes no contact file and changes no other; D > 0 writes the per-image and the integrated ones"""
     import main as cli
-    root = str(tmp_path / "case")
-    planted_case(root, n_cells=150, h=256, w=300)
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
-        os.makedirs(mdir)
-        for m, sd in _weights().items():
-            torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
-        common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
-                  os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
-        cli.main(common + ["--main-dir", str(tmp_path / "off")])
-        cli.main(common + ["--main-dir", str(tmp_path / "on"), "--contact-distance", "2", "--contact-perms", "5"])
-        cli.main(common + ["--main-dir", str(tmp_path / "bare"), "--contact-distance", "2"])
-    finally:
-        os.chdir(cwd)
-    off, on, bare = (sorted(os.listdir(tmp_path / k / "results")) for k in ("off", "on", "bare"))
-    assert not [f for f in off if "contact" in f]
+    listing, common = cli_runs(tmp_path, {"off": [], "on": ["--contact-distance", "2", "--contact-perms", "5"], "bare": ["--contact-distance", "2"]},
+                               "contact")
+    off, on, bare = listing["off"], listing["on"], listing["bare"]
     assert [f for f in on if "contact" in f] == sorted(["c_contact_edges_0.csv", "c_contact_cells_0.csv", "c_contact_degree_0.png", "c_integrated_contact_table.csv",
                                                        "c_integrated_contact_pairs.png", "c_integrated_contact.csv", "c_integrated_contact.png"])
     assert [f for f in bare if "contact" in f] == sorted(["c_contact_edges_0.csv", "c_contact_cells_0.csv", "c_contact_degree_0.png",
                                                          "c_integrated_contact_table.csv", "c_integrated_contact_pairs.png"])
-    assert [f for f in on if "contact" not in f] == off
     for f in off:
         if f.endswith(".csv") or f.endswith(".png"):
             assert open(tmp_path / "off" / "results" / f, "rb").read() == open(tmp_path / "on" / "results" / f, "rb").read(), f
@@ -448,31 +416,14 @@ def test_pipeline_switch(tmp_path):
     assert cli.parse_args(common + ["--main-dir", "x"]).contact_distance == 0
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    os.environ.pop("RIBCA_CONTACT_SEED", None)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    out = os.path.join(root, "tiles")
-    a = _run(root, out, -1, thr)
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, thr)
     assert a.tile_mode
     integrated = _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([[s["file"] for s in integrated], [s["file"] for s in a.contact_stats]], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [[s["file"] for s in integrated], [s["file"] for s in a.contact_stats]]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"], unset=("RIBCA_CONTACT_SEED",))
+    assert result_files(os.path.join(batch["root"], "tiles"), "_contact") == batch["files"]
     assert wrote == [[["x_integrated_contact_table.csv"], ["x_contact_table_0.csv"]], [[], ["x_contact_table_1.csv"]]]

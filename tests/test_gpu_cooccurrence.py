@@ -4,7 +4,6 @@ Annotator.cooccurrence_by_distance() end to end: files, the table against the or
 against the rasteriser, reruns, anchors, the command line, two ranks."""
 import ctypes
 import io
-import json
 import os
 
 import numpy as np
@@ -12,10 +11,9 @@ import pytest
 import torch
 
 import cooccurrence_numpy as CO
+from batch_harness import annotated_batch, cli_runs, result_files, run_annotator, two_ranks
 from multiplexed_image_annotator_amd import _lib, colors, cooccurrence, enrichment, ops
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -187,11 +185,6 @@ def test_adjacent_pairs_of_two_types_attract_near_and_not_far():
 RADII = [25.0, 60.0, 120.0, 250.0]
 
 
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "cooccurrence" in f}
-
-
 def _analyse(a):
     assert a.cooccurrence_by_distance(radii=RADII, integrate=True) is None
     integrated = list(a.cooccurrence_stats)
@@ -202,16 +195,7 @@ def _analyse(a):
 @pytest.fixture(scope="module")
 def batch(tmp_path_factory):
     """the two-image batch of the cell-type plots, annotated once with "Others" among the cell types, and analysed"""
-    tmp = tmp_path_factory.mktemp("cooc")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "files": _files(out)}
+    return annotated_batch(tmp_path_factory, "cooc", _analyse, "cooccurrence")
 
 
 def _oracle_counts(a, images):
@@ -274,16 +258,16 @@ def test_files_tables_and_figures_are_the_oracle_s(batch):
 
 def test_anchors_restrict_the_figures_and_a_second_run_writes_the_same_bytes(batch):
     out = os.path.join(batch["tmp"], "two")
-    b = _run(batch["root"], out, -1, batch["thr"])
+    b = run_annotator(batch["root"], out, -1, batch["thr"])
     names = [str(c) for c in b.cell_types]
     b.cooccurrence_by_distance(radii=RADII, integrate=True, anchors=[names[1], 0])
     wanted = [f"x_integrated_cooccurrence_{cooccurrence.slug(names[k])}.png" for k in (1, 0)]
     assert b.cooccurrence_stats[0]["files"] == ["x_integrated_cooccurrence.csv"] + wanted
-    first = _files(out)
+    first = result_files(out, "cooccurrence")
     assert sorted(first) == sorted(["x_integrated_cooccurrence.csv"] + wanted)
     assert all(first[f] == batch["files"][f] for f in first)
     _analyse(b)
-    assert _files(out) == batch["files"]
+    assert result_files(out, "cooccurrence") == batch["files"]
     # the default radii: 16 bands of one cell size
     b.cooccurrence_by_distance(integrate=True, anchors=[0])
     assert b.cooccurrence_stats[0]["radii"] == [30.0 * k for k in range(1, 17)] and b.cooccurrence_stats[0]["B"] == 16
@@ -300,7 +284,7 @@ def test_errors_leave_the_files_alone(batch):
         a.cooccurrence_by_distance(radii=RADII, anchors=["no such cell"])
     with pytest.raises(ValueError, match="is not one of the cell types"):
         a.cooccurrence_by_distance(radii=RADII, anchors=[len(a.cell_types)])
-    assert _files(batch["out"]) == batch["files"]
+    assert result_files(batch["out"], "cooccurrence") == batch["files"]
     from multiplexed_image_annotator_amd.annotator import Annotator
     root = batch["root"]
     fresh = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", os.path.join(batch["tmp"], "fresh"), "x", False, False,
@@ -312,57 +296,25 @@ def test_errors_leave_the_files_alone(batch):
 def test_pipeline_switch(tmp_path):
     """--cooccurrence-bands 0 (the default) writes no co-occurrence file; N > 0 writes the integrated table and its figures, N bands of one cell size"""
     import main as cli
-    root = str(tmp_path / "case")
-    planted_case(root, n_cells=150, h=256, w=300)
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
-        os.makedirs(mdir)
-        for m, sd in _weights().items():
-            torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
-        common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
-                  os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
-        cli.main(common + ["--main-dir", str(tmp_path / "off")])
-        cli.main(common + ["--main-dir", str(tmp_path / "on"), "--cooccurrence-bands", "4"])
-    finally:
-        os.chdir(cwd)
-    off, on = sorted(os.listdir(tmp_path / "off" / "results")), sorted(os.listdir(tmp_path / "on" / "results"))
-    assert not [f for f in off if "cooccurrence" in f]
+    listing, common = cli_runs(tmp_path, {"off": [], "on": ["--cooccurrence-bands", "4"]}, "cooccurrence")
+    on = listing["on"]
     added = [f for f in on if "cooccurrence" in f]
     assert "c_integrated_cooccurrence.csv" in added and len(added) >= 2
     assert all(f.startswith("c_integrated_cooccurrence_") and f.endswith(".png") for f in added if f != "c_integrated_cooccurrence.csv")
-    assert [f for f in on if "cooccurrence" not in f] == off
     rows = open(tmp_path / "on" / "results" / "c_integrated_cooccurrence.csv").read().strip().split("\n")
     assert rows[0] == "band,r_lo,r_hi,cell_type,neighbor_type,count,lift,cum_count,cum_lift"
     assert sorted({(r.split(",")[0], r.split(",")[2]) for r in rows[1:]}) == [("0", "30.0"), ("1", "60.0"), ("2", "90.0"), ("3", "120.0")]
     assert cli.parse_args(common + ["--main-dir", "x"]).cooccurrence_bands == 0
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    out = os.path.join(root, "tiles")
-    a = _run(root, out, -1, thr)
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, thr)
     assert a.tile_mode
     integrated = _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([[s["file"] for s in integrated], [s["file"] for s in a.cooccurrence_stats]], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [[s["file"] for s in integrated], [s["file"] for s in a.cooccurrence_stats]]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"])
+    assert result_files(os.path.join(batch["root"], "tiles"), "cooccurrence") == batch["files"]
     assert wrote == [[["x_integrated_cooccurrence.csv"], ["x_cooccurrence_0.csv"]], [[], ["x_cooccurrence_1.csv"]]]

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from batch_harness import load_config1, two_ranks, write_case
 from multiplexed_image_annotator_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -19,14 +20,6 @@ pytestmark = pytest.mark.gpu
 #: reference's own fp32 conv error, which another correct summation order (embed_f32_kernel) cannot reproduce bit for bit.
 #: North star: 1e-3.
 E2E_TOL = 2e-4
-
-
-def write_case(tmp_path, raw, mask, markers):
-    np.save(tmp_path / "img.npy", raw)
-    np.save(tmp_path / "mask.npy", mask)
-    (tmp_path / "markers.txt").write_text("\n".join(markers) + "\n")
-    (tmp_path / "images.csv").write_text(f"image_path,mask_path\n{tmp_path / 'img.npy'},{tmp_path / 'mask.npy'}\n")
-    return str(tmp_path / "markers.txt"), str(tmp_path / "images.csv")
 
 
 def csv_equal_up_to_conf(got: str, exp: str, tol: float):
@@ -324,13 +317,10 @@ def test_tissue_regions_end_to_end(tmp_path):
     assert (png[m == 0] == 0).all()
 
 
-def _rank_worker(rank, world, port, root, seed):
+def _rank_body(rank, root, seed):
     """One rank of the sharded Annotator (both ranks share cuda:0 here; gloo carries the all-gather)."""
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
     from multiplexed_image_annotator_amd.annotator import Annotator
+    world = 2
     sd = {m: synth.make_vit_state_dict(m, seed, depth=2) for m in ("immune_base", "struct")}
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", os.path.join(root, "sharded"), "r", False, False, -1,
                   True, 0.3, 99.8, 0.3, 30, None)
@@ -341,27 +331,18 @@ def _rank_worker(rank, world, port, root, seed):
     lo, hi = a.preprocessor.shards[0]
     n = len(a.preprocessor.cell_ids[0])
     assert (hi - lo) in (n // world, n // world + 1) and a.preprocessor.panel_patches(0).shape[0] == hi - lo   # only this rank's cells were cropped
-    tdist.barrier()
-    tdist.destroy_process_group()
 
 
 def test_two_ranks_match_single_rank(tmp_path):
     """BASELINE config 4 in small: cells sharded over 2 ranks (one process each, both on this GPU; gloo instead of RCCL), all-gather
     of the probability rows, rank 0 writes the CSV -- byte-identical to the single-rank run."""
-    import socket
-    import torch.multiprocessing as mp
     from multiplexed_image_annotator_amd.annotator import Annotator
     from multiplexed_image_annotator_amd.marker_parse import PANELS
     seed = synth.SEED_BASE + 71
     markers = ['CD45', 'CD20', 'CD4', 'CD8', 'DAPI', 'CD11c', 'CD3', 'aSMA', 'CD31', 'PanCK', 'Vimentin', 'Ki67']
     mask, img = synth.make_mask_and_image(208, 240, 91, len(markers), seed)
     write_case(tmp_path, img.numpy().astype(np.uint16), mask.numpy().astype(np.int32), markers)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.get_context("spawn")
-    mp.spawn(_rank_worker, args=(2, port, str(tmp_path), seed), nprocs=2, join=True)
+    two_ranks(_rank_body, str(tmp_path), seed, tile=None)
     sd = {m: synth.make_vit_state_dict(m, seed, depth=2) for m in ("immune_base", "struct")}
     one = Annotator(str(tmp_path / "markers.txt"), str(tmp_path / "images.csv"), "cuda", str(tmp_path / "single"), "r", False, False, -1, True, 0.3, 99.8,
                     0.3, 30, None)
@@ -441,13 +422,10 @@ def test_imputer_path_is_an_argument(monkeypatch):
     assert torch.equal(slow_arg[:, present], x[:, present])
 
 
-def _tile_rank_worker(rank, world, port, root, seed):
+def _tile_rank_body(rank, root, seed):
     """One rank of a tile-per-rank run: a batch CSV of three images over two ranks (both on cuda:0 here; gloo for the control plane)."""
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
     from multiplexed_image_annotator_amd.annotator import Annotator
+    world = 2
     sd = {m: synth.make_vit_state_dict(m, seed, depth=2) for m in ("immune_base", "struct")}
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", os.path.join(root, "tiles"), "r", False, False, -1,
                   True, 0.3, 99.8, 0.3, 30, None)
@@ -459,10 +437,7 @@ def _tile_rank_worker(rank, world, port, root, seed):
     a.export_annotations()
     a.neighborhood_analysis(n_neighbors=10, integrate=True)
     a.colorize(from_script=True)
-    with open(os.path.join(root, f"cell_types_rank{rank}.json"), "w") as f:
-        json.dump([str(t) for t in a.cell_types], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [str(t) for t in a.cell_types]
 
 
 def test_two_ranks_tile_per_rank_match_single_rank(tmp_path):
@@ -470,8 +445,6 @@ def test_two_ranks_tile_per_rank_match_single_rank(tmp_path):
     WHOLE images -- replicas only, nothing exchanged on the data path, every rank writes the CSVs / PNGs of its own images under their
     batch-wide numbers.  Files byte-identical to the single-rank run; the run-wide cell-type list and the integrated neighbourhood matrix
     (the two things the reference computes over the whole batch) agree as well."""
-    import socket
-    import torch.multiprocessing as mp
     from multiplexed_image_annotator_amd.annotator import Annotator
     seed = synth.SEED_BASE + 72
     markers = ['CD45', 'CD20', 'CD4', 'CD8', 'DAPI', 'CD11c', 'CD3', 'aSMA', 'CD31', 'PanCK', 'Vimentin', 'Ki67']
@@ -483,11 +456,7 @@ def test_two_ranks_tile_per_rank_match_single_rank(tmp_path):
         lines.append(f"{tmp_path / f'img{j}.npy'},{tmp_path / f'mask{j}.npy'}")
     (tmp_path / "markers.txt").write_text("\n".join(markers) + "\n")
     (tmp_path / "images.csv").write_text("\n".join(lines) + "\n")
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_tile_rank_worker, args=(2, port, str(tmp_path), seed), nprocs=2, join=True)
+    cell_types = two_ranks(_tile_rank_body, str(tmp_path), seed, tile=None)
     sd = {m: synth.make_vit_state_dict(m, seed, depth=2) for m in ("immune_base", "struct")}
     one = Annotator(str(tmp_path / "markers.txt"), str(tmp_path / "images.csv"), "cuda", str(tmp_path / "single"), "r", False, False, -1, True, 0.3, 99.8,
                     0.3, 30, None)
@@ -505,16 +474,13 @@ def test_two_ranks_tile_per_rank_match_single_rank(tmp_path):
             assert a == b, name
     assert open(tmp_path / "tiles" / "results" / "r_integrated_neighborhood.csv").read() == open(tmp_path / "single" / "results" / "r_integrated_neighborhood.csv").read()
     for r in range(2):
-        assert json.load(open(tmp_path / f"cell_types_rank{r}.json")) == [str(t) for t in one.cell_types]
+        assert cell_types[r] == [str(t) for t in one.cell_types]
 
 
-def _norm_shard_worker(rank, world, port, root, seed):
+def _norm_shard_body(rank, root, seed):
     os.environ["RIBCA_NORM_SHARD"] = "1"
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
     from multiplexed_image_annotator_amd.annotator import Annotator
+    world = 2
     sd = {m: synth.make_vit_state_dict(m, seed, depth=2) for m in ("immune_base", "struct")}
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", os.path.join(root, "normshard"), "r", False, False, -1,
                   True, 0.3, 99.8, 0.3, 30, None)
@@ -524,26 +490,18 @@ def _norm_shard_worker(rank, world, port, root, seed):
     np.save(os.path.join(root, f"normalised_rank{rank}.npy"), a.preprocessor.images_dev[0].cpu().numpy())
     a.predict(16)
     a.export_annotations()
-    tdist.barrier()
-    tdist.destroy_process_group()
 
 
 def test_two_ranks_channel_sharded_normalise(tmp_path):
     """RIBCA_NORM_SHARD=1 (cell-sharded runs): each rank normalises ceil(C / world) channels (reference preprocess.py:214-239 treats every
     channel on its own) and ONE all-gather of the fp32 planes gives every rank the image -- bit-identical to the replicated form, and the
     CSV behind it byte-identical to the single-rank run."""
-    import socket
-    import torch.multiprocessing as mp
     from multiplexed_image_annotator_amd.annotator import Annotator
     seed = synth.SEED_BASE + 73
     markers = ['CD45', 'CD20', 'CD4', 'CD8', 'DAPI', 'CD11c', 'CD3', 'aSMA', 'CD31', 'PanCK', 'Vimentin', 'Ki67', 'X1']      # 13 planes over 2 ranks: 6 + 7
     mask, img = synth.make_mask_and_image(208, 240, 91, len(markers), seed)
     write_case(tmp_path, img.numpy().astype(np.uint16), mask.numpy().astype(np.int32), markers)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_norm_shard_worker, args=(2, port, str(tmp_path), seed), nprocs=2, join=True)
+    two_ranks(_norm_shard_body, str(tmp_path), seed, tile=None)
     sd = {m: synth.make_vit_state_dict(m, seed, depth=2) for m in ("immune_base", "struct")}
     one = Annotator(str(tmp_path / "markers.txt"), str(tmp_path / "images.csv"), "cuda", str(tmp_path / "single"), "r", False, False, -1, True, 0.3, 99.8,
                     0.3, 30, None)
@@ -684,7 +642,6 @@ def test_config1_matches_reference_golden(golden_dir, tmp_path):
     """BASELINE.json configs[0] stand-in: the reference's examples/example_1_cell_mask.png (600 x 600, 1850 cells)
     + seeded 7-channel image, Basic panel, predict(8): labels identical to the reference Annotator's CPU run, confidences < 1e-3."""
     from multiplexed_image_annotator_amd.annotator import Annotator
-    from test_oracle_e2e import load_config1
     meta, arrs, raw, mask, weights, mf = load_config1(golden_dir, tmp_path)
     _, csv = write_case(tmp_path, raw, mask, meta["markers"])
     a = Annotator(mf, csv, "cuda", str(tmp_path), "c1", True, False, -1, True, meta["blur"], meta["amax"], meta["conf"], 30, None)

@@ -4,7 +4,6 @@ neighborhood_enrichment() end to end: files, the PNG rectangles against the rast
 tables, reruns, seeds, two ranks."""
 import ctypes
 import io
-import json
 import os
 
 import numpy as np
@@ -12,10 +11,9 @@ import pytest
 import torch
 
 import enrichment_numpy as EN
+from batch_harness import annotated_batch, cli_runs, result_files, run_annotator, two_ranks
 from multiplexed_image_annotator_amd import _lib, colors, enrichment, ops
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -214,11 +212,6 @@ def test_refusals_are_a_status_and_nothing_runs():
 P_TEST = 40
 
 
-def _enrichment_files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "neighborhood" in f}
-
-
 def _analyse(a):
     a.neighborhood_analysis(integrate=True)
     integrated = list(a.neighborhood_stats)
@@ -238,16 +231,9 @@ EXPECTED = sorted([f"x_{s}.{e}" for s in ("integrated_neighborhood", "neighborho
 def batch(tmp_path_factory):
     """the two-image batch of the cell-type plots, annotated once with "Others" among the cell types, and analysed"""
     os.environ.pop("RIBCA_ENRICH_SEED", None)
-    tmp = tmp_path_factory.mktemp("enrich")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated, enriched = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "enriched": enriched, "files": _enrichment_files(out)}
+    b = annotated_batch(tmp_path_factory, "enrich", _analyse, "neighborhood")
+    b["integrated"], b["enriched"] = b["integrated"]
+    return b
 
 
 def _rect_of(files, name, stats, t, cell):
@@ -332,12 +318,12 @@ def test_enrichment_table_is_the_oracle_s(batch):
 
 def test_a_second_run_writes_the_same_bytes_and_a_seed_changes_z(batch, monkeypatch):
     out = os.path.join(batch["tmp"], "two")
-    b = _run(batch["root"], out, -1, batch["thr"])
+    b = run_annotator(batch["root"], out, -1, batch["thr"])
     _analyse(b)
-    assert _enrichment_files(out) == batch["files"]
+    assert result_files(out, "neighborhood") == batch["files"]
     monkeypatch.setenv("RIBCA_ENRICH_SEED", "5")
     b.neighborhood_enrichment(n_perms=P_TEST, integrate=True)
-    seeded = _enrichment_files(out)
+    seeded = result_files(out, "neighborhood")
     name = "x_integrated_neighborhood_enrichment_table.csv"
     assert seeded[name] != batch["files"][name] and b.enrichment_stats[0]["seed"] == 5
     assert [r[:3] for r in _read_table(seeded[name].decode())] == [r[:3] for r in _read_table(batch["files"][name].decode())]      # observed stays
@@ -352,60 +338,28 @@ def test_errors_leave_the_files_alone(batch):
         a.neighborhood_enrichment(n_perms=0)
     with pytest.raises(_lib.RibcaError, match="n_neighbors must be in"):      # what neighborhood_analysis raises for a list this long
         a.neighborhood_enrichment(n_neighbors=33, n_perms=2, integrate=False)
-    assert _enrichment_files(batch["out"]) == batch["files"]
+    assert result_files(batch["out"], "neighborhood") == batch["files"]
 
 
 def test_pipeline_switch(tmp_path):
     """--enrichment-perms 0 (the default) writes no enrichment file; N > 0 writes the three integrated ones after the neighbourhood matrix"""
     import main as cli
-    root = str(tmp_path / "case")
-    planted_case(root, n_cells=150, h=256, w=300)
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
-        os.makedirs(mdir)
-        for m, sd in _weights().items():
-            torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
-        common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
-                  os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
-        cli.main(common + ["--main-dir", str(tmp_path / "off")])
-        cli.main(common + ["--main-dir", str(tmp_path / "on"), "--enrichment-perms", "20"])
-    finally:
-        os.chdir(cwd)
-    off, on = sorted(os.listdir(tmp_path / "off" / "results")), sorted(os.listdir(tmp_path / "on" / "results"))
-    assert not [f for f in off if "enrichment" in f] and "c_integrated_neighborhood.png" in off and "c_integrated_neighborhood.csv" in off
+    listing, common = cli_runs(tmp_path, {"off": [], "on": ["--enrichment-perms", "20"]}, "enrichment")
+    off, on = listing["off"], listing["on"]
+    assert "c_integrated_neighborhood.png" in off and "c_integrated_neighborhood.csv" in off
     assert [f for f in on if "enrichment" in f] == ["c_integrated_neighborhood_enrichment.csv", "c_integrated_neighborhood_enrichment.png",
                                                     "c_integrated_neighborhood_enrichment_table.csv"]
-    assert [f for f in on if "enrichment" not in f] == off
     assert cli.parse_args(common + ["--main-dir", "x"]).enrichment_perms == 0
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    os.environ.pop("RIBCA_ENRICH_SEED", None)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    out = os.path.join(root, "tiles")
-    a = _run(root, out, -1, thr)
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, thr)
     assert a.tile_mode
     _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([s["file"] for s in a.enrichment_stats], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [s["file"] for s in a.enrichment_stats]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"]), nprocs=2, join=True)
-    assert _enrichment_files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"], unset=("RIBCA_ENRICH_SEED",))
+    assert result_files(os.path.join(batch["root"], "tiles"), "neighborhood") == batch["files"]
     assert wrote == [["x_neighborhood_enrichment_0.png"], ["x_neighborhood_enrichment_1.png"]]      # the per-image call came last

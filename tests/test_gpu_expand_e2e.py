@@ -2,7 +2,6 @@
 argument; with 3 every stage reads the mask tests/expand_numpy.py grows from the file's -- the device and host masks, the label table, the
 lazy pixel lists, the .npy and the expansion CSV, the morphology areas, the contact graph -- the core and ring intensity tables add up to the
 cell's, and two tile-per-rank ranks write the single-rank bytes."""
-import json
 import os
 from fractions import Fraction
 
@@ -11,9 +10,8 @@ import pytest
 import torch
 
 import expand_numpy as EN
+from batch_harness import run_annotator, two_image_case, two_ranks, weights
 from multiplexed_image_annotator_amd import _lib, ops
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +23,7 @@ def _run_expanded(root, out, expand_mask):
     from multiplexed_image_annotator_amd.annotator import Annotator
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", out, "x", False, False, -1, True, 0.3, 99.8, 0.0, 30, None,
                   expand_mask=expand_mask)
-    a.set_weights(_weights())
+    a.set_weights(weights())
     a.preprocess()
     a.predict(16)
     a.export_annotations()
@@ -51,7 +49,7 @@ def runs(tmp_path_factory):
     root = str(tmp / "case")
     os.makedirs(root)
     two_image_case(root)
-    plain = _run(root, str(tmp / "plain"), -1, 0.0)
+    plain = run_annotator(root, str(tmp / "plain"), -1, 0.0)
     zero = _run_expanded(root, str(tmp / "zero"), 0)
     grown = _run_expanded(root, str(tmp / "grown"), D)
     for a in (plain, zero, grown):
@@ -183,30 +181,15 @@ def test_a_compartment_needs_an_expansion(runs):
         runs["grown"].cell_intensities(compartment="membrane")
 
 
-def _rank_worker(rank, world, port, root):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
+def _rank_body(rank, root):
     a = _run_expanded(root, os.path.join(root, "tiles"), D)
     assert a.tile_mode and len(a.expansion_stats) == 1
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump(a.expansion_stats[0]["files"], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return a.expansion_stats[0]["files"]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(runs):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, runs["root"]), nprocs=2, join=True)
+    wrote = two_ranks(_rank_body, runs["root"])
     single = {f: b for f, b in _files(os.path.join(runs["tmp"], "grown")).items() if "_expan" in f}
     tiles = {f: b for f, b in _files(os.path.join(runs["root"], "tiles")).items() if "_expan" in f}
     assert sorted(single) == ["x_expanded_mask_0.npy", "x_expanded_mask_1.npy", "x_expansion_0.csv", "x_expansion_1.csv"] and tiles == single
-    wrote = [json.load(open(os.path.join(runs["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
     assert wrote == [["x_expanded_mask_0.npy", "x_expansion_0.csv"], ["x_expanded_mask_1.npy", "x_expansion_1.csv"]]

@@ -6,62 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-from multiplexed_image_annotator_amd import synth
+from batch_harness import planted_case, run_annotator, threshold, two_ranks, weights
 
 pytestmark = pytest.mark.gpu
-
-# the immune_base panel and five markers no panel uses: one classifier, whose vote sends a cell below the confidence threshold to "Others"
-MARKERS = ['CD45', 'CD20', 'CD4', 'CD8', 'DAPI', 'CD11c', 'CD3', 'Ki67', 'HLA-DR', 'CD14', 'CD57', 'Bcl2']
-SEED = synth.SEED_BASE + 83
-
-
-def planted_case(root, n_cells=400, h=416, w=480):
-    """the synth mask; every cell gets one of 4 marker profiles (a few bright channels each) with 5 % multiplicative pixel noise"""
-    mask, _ = synth.make_mask_and_image(h, w, n_cells, len(MARKERS), SEED, want_image=False)
-    mk = mask.numpy().astype(np.int32)
-    rng = np.random.RandomState(SEED % (1 << 32))
-    prof = np.full((4, len(MARKERS)), 150.0)
-    for p in range(4):
-        prof[p, rng.choice(len(MARKERS), 3, replace=False)] = rng.uniform(3000, 8000, 3)
-    ids = np.unique(mk[mk > 0])
-    planted = {int(c): int(rng.randint(4)) for c in ids}
-    lut = np.zeros((mk.max() + 1, len(MARKERS)))
-    for c, p in planted.items():
-        lut[c] = prof[p]
-    img = lut[mk].transpose(2, 0, 1) * (1 + 0.05 * rng.randn(len(MARKERS), h, w))
-    raw = np.clip(img, 0, 65535).astype(np.uint16)
-    os.makedirs(root, exist_ok=True)
-    np.save(os.path.join(root, "img.npy"), raw)
-    np.save(os.path.join(root, "mask.npy"), mk)
-    with open(os.path.join(root, "markers.txt"), "w") as f:
-        f.write("\n".join(MARKERS) + "\n")
-    with open(os.path.join(root, "images.csv"), "w") as f:
-        f.write(f"image_path,mask_path\n{os.path.join(root, 'img.npy')},{os.path.join(root, 'mask.npy')}\n")
-    return planted
-
-
-def _weights():
-    sd = synth.make_vit_state_dict("immune_base", SEED, depth=2)
-    sd["head.bias"] = sd["head.bias"].clone()
-    sd["head.bias"][3] -= 10.0      # class 3 of immune_base is "Others": the random model then votes a cell type, and the threshold decides
-    return {"immune_base": sd}
-
-
-def _run(root, out, min_cells, confidence, batch="x"):
-    from multiplexed_image_annotator_amd.annotator import Annotator
-    a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", out, batch, False, False, min_cells, True, 0.3,
-                  99.8, confidence, 30, None)
-    a.set_weights(_weights())
-    a.preprocess()
-    a.predict(16)
-    a.export_annotations()
-    return a
-
-
-def _threshold(root, tmp):
-    """a confidence threshold that sends most, not all, cells to "Others": the 85th percentile of the unthresholded confidences"""
-    a = _run(root, os.path.join(tmp, "probe"), -1, 0.0)
-    return float(np.quantile(a._conf_arrays[0], 0.85))
 
 
 def test_extra_cell_types_end_to_end(tmp_path):
@@ -69,9 +16,9 @@ def test_extra_cell_types_end_to_end(tmp_path):
     from multiplexed_image_annotator_amd import ops
     root = str(tmp_path / "case")
     planted = planted_case(root)
-    thr = _threshold(root, str(tmp_path))
-    base = _run(root, str(tmp_path / "base"), -1, thr)
-    a = _run(root, str(tmp_path / "extra"), 20, thr)
+    thr = threshold(root, str(tmp_path))
+    base = run_annotator(root, str(tmp_path / "base"), -1, thr)
+    a = run_annotator(root, str(tmp_path / "extra"), 20, thr)
     ids = a.preprocessor.cell_ids[0].tolist()
     others = [j for j, n in enumerate(base.annotations[0]) if n == "Others"]
     assert 0.5 * len(ids) < len(others) < len(ids)
@@ -93,7 +40,7 @@ def test_extra_cell_types_end_to_end(tmp_path):
     # CSV carries the new names, and two runs write the same bytes
     csv = open(tmp_path / "extra" / "results" / "x_annotation_0.csv").read()
     assert "Additional type 0" in csv
-    b = _run(root, str(tmp_path / "extra2"), 20, thr)
+    b = run_annotator(root, str(tmp_path / "extra2"), 20, thr)
     assert open(tmp_path / "extra2" / "results" / "x_annotation_0.csv").read() == csv
     # cell types: np.sort of the names, "Others" last; colorize / neighbourhood use the same indices
     assert list(a.cell_types[:-1]) == sorted(a.cell_types[:-1]) and a.cell_types[-1] == "Others"
@@ -124,7 +71,7 @@ def test_cli_min_cells_runs_to_the_end(tmp_path):
     try:
         mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
         os.makedirs(mdir)
-        for m, sd in _weights().items():
+        for m, sd in weights().items():
             torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
         cli.main(["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
                   os.path.join(root, "mask.npy"), "--batch-id", "c", "--main-dir", str(tmp_path / "out"), "--no-infer", "--bs", "16",
@@ -136,29 +83,17 @@ def test_cli_min_cells_runs_to_the_end(tmp_path):
     assert (res / "c_integrated_neighborhood.csv").exists()
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    a = _run(root, os.path.join(root, "sharded"), 20, thr, batch="r")
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "sharded"), 20, thr, batch="r")
     assert not a.tile_mode
-    tdist.barrier()
-    tdist.destroy_process_group()
 
 
 def test_two_ranks_match_single_rank_with_extra_types(tmp_path):
-    import socket
-    import torch.multiprocessing as mp
     root = str(tmp_path / "case")
     planted_case(root, n_cells=200, h=300, w=340)
-    thr = _threshold(root, str(tmp_path))
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, root, thr), nprocs=2, join=True)
-    one = _run(root, os.path.join(root, "single"), 20, thr, batch="r")
+    thr = threshold(root, str(tmp_path))
+    two_ranks(_rank_body, root, thr, tile=None)
+    one = run_annotator(root, os.path.join(root, "single"), 20, thr, batch="r")
     assert any(n.startswith("Additional type") for n in one.annotations[0])
     a = open(os.path.join(root, "sharded", "results", "r_annotation_0.csv")).read()
     b = open(os.path.join(root, "single", "results", "r_annotation_0.csv")).read()

@@ -12,51 +12,14 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_kernels import _fold, _ln_case, _row_stats, ps_encode, rnd
+from kernel_harness import Arena, fold_weight, ln_case, ps_encode, rnd, row_stats
 
 pytestmark = pytest.mark.gpu
-
-BAND = 8192      # bytes on either side of every operand: more than a 128-row tile of 48-byte rows, a 4 KB page and a 1 KB DMA piece
-
 
 @pytest.fixture(scope="module")
 def dev():
     from multiplexed_image_annotator_amd import _lib
     return _lib.require_gpu()
-
-
-class Arena:
-    """operands carved out of ONE device buffer with a band of `fill` bytes before and after each"""
-
-    def __init__(self, dev, fill, capacity=96 << 20):
-        self.buf = torch.full((capacity,), fill, dtype=torch.uint8, device=dev)
-        self.fill, self.off, self.spans = fill, BAND, []
-
-    def put(self, t: torch.Tensor) -> torch.Tensor:
-        """a copy of t inside the arena"""
-        v = self.empty(t.shape, t.dtype)
-        v.copy_(t)
-        return v
-
-    def zeros(self, shape, dtype):
-        v = self.empty(shape, dtype)
-        v.zero_()
-        return v
-
-    def empty(self, shape, dtype):
-        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        start = (self.off + 255) // 256 * 256
-        assert start + nbytes + BAND <= self.buf.numel(), "arena too small"
-        self.spans.append((start, nbytes))
-        self.off = start + nbytes + BAND
-        return self.buf[start:start + nbytes].view(dtype).view(shape)
-
-    def bands_intact(self):
-        """every byte outside the carved spans still holds the fill pattern"""
-        mask = torch.ones(self.off, dtype=torch.bool, device=self.buf.device)
-        for s, n in self.spans:
-            mask[s:s + n] = False
-        return bool(torch.all(self.buf[:self.off][mask] == self.fill))
 
 
 def _twice(dev, body):
@@ -84,11 +47,11 @@ def test_qkv_attention_mx_one_cell_between_guard_bands(dev, d):
     heads, ntok, cells = 12, 101, 1
     hdp = (d // heads + 7) // 8 * 8
     m = cells * ntok
-    z_ps, _, g, b, dp = _ln_case(m, d, 60, dev, 0.5, 1.0)
+    z_ps, _, g, b, dp = ln_case(m, d, 60, dev, 0.5, 1.0)
     w = rnd((3 * d, d), 63, dev, 1.0 / np.sqrt(d))
     bias = rnd((3 * d,), 64, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     kz = (dp + 127) // 128 * 128
 
     def body(ar):
@@ -111,11 +74,11 @@ def test_gemm_mx_fc1_ragged_rows_between_guard_bands(dev, m):
     from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
     d = 384
     n = 4 * d
-    z_ps, _, g, b, dp = _ln_case(m, d, 50, dev, 0.5, 3.0)
+    z_ps, _, g, b, dp = ln_case(m, d, 50, dev, 0.5, 3.0)
     w = rnd((n, d), 53, dev, 2.0 / np.sqrt(d))
     bias = rnd((n,), 54, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     kz = (dp + 127) // 128 * 128
 
     def body(ar):
@@ -144,7 +107,7 @@ def test_gemm_resid_zmx_ragged_rows_between_guard_bands(dev, kind, n, k, m):
     zk = (n + 127) // 128 * 128
     z0 = (rnd((m, n), 8, dev) + 3.0) * torch.exp(rnd((m, 1), 58, dev) * 2.0)
     a_ps, w_ps, z_ps = ps_encode(a, k), ps_encode(w, k, lib().ribca_gemm_padded_n(n)), ps_encode(z0, npd)
-    prev = _row_stats(z_ps, npd, m, n, dev)
+    prev = row_stats(z_ps, npd, m, n, dev)
 
     def body(ar):
         ap, wp, zp, bs, pv = ar.put(a_ps), ar.put(w_ps), ar.put(z_ps), ar.put(bias), ar.put(prev)
@@ -170,11 +133,11 @@ def test_gemm_resid_zmx_ragged_rows_between_guard_bands(dev, kind, n, k, m):
 def test_cell_attention_one_cell_between_guard_bands(dev, d):
     from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
     m = 101
-    z_ps, _, g, b, dp = _ln_case(m, d, 70, dev, 0.5, 1.0)
+    z_ps, _, g, b, dp = ln_case(m, d, 70, dev, 0.5, 1.0)
     w = rnd((3 * d, d), 73, dev, 1.0 / np.sqrt(d))
     bias = rnd((3 * d,), 74, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
 
     def body(ar):
         z, wp, cs, b2, r = ar.put(z_ps), ar.put(w_ps), ar.put(csum), ar.put(bias2), ar.put(rs)
@@ -208,11 +171,11 @@ def test_mx_launchers_refuse_shapes_without_a_tile_form(dev):
     from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
     m, d = 64, 132      # 4 d = 528 = 11 x 48: a multiple of the MX kernel's wave block, not of its 192-column tile
     n = 4 * d
-    z_ps, _, g, b, dp = _ln_case(m, d, 50, dev)
+    z_ps, _, g, b, dp = ln_case(m, d, 50, dev)
     w = rnd((n, d), 53, dev, 0.1)
     bias = rnd((n,), 54, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     kz = (dp + 127) // 128 * 128
     z3 = lambda *s, dt=torch.uint8: torch.zeros(s, dtype=dt, device=dev)
     a_hi, a_l8, a_sc = z3(m, kz, dt=torch.int16), z3(m, kz), z3(m, kz // 32)

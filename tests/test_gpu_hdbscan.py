@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import hdbscan_numpy as H
-from test_hdbscan_host import CAP, PLANTED
+from batch_harness import planted_case, run_annotator, threshold
 
 pytestmark = pytest.mark.gpu
 
@@ -101,7 +101,7 @@ def test_two_calls_and_a_second_stream_give_identical_bytes():
         assert a == b and a == c
 
 
-@pytest.mark.parametrize("seed,n,m", PLANTED)
+@pytest.mark.parametrize("seed,n,m", H.PLANTED)
 def test_hdbscan_equals_the_oracle_path_label_for_label(seed, n, m):
     from multiplexed_image_annotator_amd import manifold
     x, _ = H.planted(seed, n)
@@ -127,7 +127,7 @@ def test_hdbscan_20k_points_against_sklearn():
     diff = H.best_renaming_mismatches(ref, got)
     print(f"[hdbscan 20k vs sklearn] {got.max() + 1} / {ref.max() + 1} clusters, {diff} of {n} points differ; ms {t}")
     assert got.max() == ref.max()
-    assert diff <= CAP * n
+    assert diff <= H.CAP * n
 
 
 def test_bad_requests_return_a_status_not_an_abort():
@@ -165,15 +165,14 @@ def test_bad_requests_return_a_status_not_an_abort():
 
 
 def test_annotator_backend_switch(tmp_path, monkeypatch):
-    from test_gpu_extra_cell_types import _run, _threshold, planted_case
     root = str(tmp_path / "case")
     planted_case(root)
-    thr = _threshold(root, str(tmp_path))
+    thr = threshold(root, str(tmp_path))
     monkeypatch.delenv("RIBCA_HDBSCAN", raising=False)
-    a = _run(root, str(tmp_path / "gpu"), 20, thr)
-    b = _run(root, str(tmp_path / "gpu2"), 20, thr)
+    a = run_annotator(root, str(tmp_path / "gpu"), 20, thr)
+    b = run_annotator(root, str(tmp_path / "gpu2"), 20, thr)
     monkeypatch.setenv("RIBCA_HDBSCAN", "sklearn")
-    s = _run(root, str(tmp_path / "sk"), 20, thr)
+    s = run_annotator(root, str(tmp_path / "sk"), 20, thr)
     assert a.extra_stats["backend"] == "gpu" and s.extra_stats["backend"] == "sklearn"
     assert {"core_ms", "mst_ms", "tree_ms", "cluster_ms"} <= set(a.extra_stats)
     assert a.extra_stats["clusters"] == s.extra_stats["clusters"] >= 2
@@ -187,7 +186,7 @@ def test_annotator_backend_switch(tmp_path, monkeypatch):
     assert others_a == others_s
     diff = H.best_renaming_mismatches(ls, la)
     print(f"[annotator backends] {len(la)} pooled, {a.extra_stats['clusters']} clusters, {diff} points differ; gpu {a.extra_stats}; sklearn {s.extra_stats}")
-    assert diff <= CAP * len(la)
+    assert diff <= H.CAP * len(la)
     csv_a = open(os.path.join(str(tmp_path / "gpu"), "results", "x_annotation_0.csv")).read()
     csv_b = open(os.path.join(str(tmp_path / "gpu2"), "results", "x_annotation_0.csv")).read()
     assert "Additional type 0" in csv_a and csv_a == csv_b

@@ -4,7 +4,6 @@ pixel, of exactly ops.INTENSITY_RESIDENT pixels and of one more (the streaming f
 that hold other cells or reach past the image, ids that are no cell; and Annotator.cell_intensities() end to end: files against the restatement
 run on the same images, the maps, the pipeline switch, two ranks, the comparison with the window table on a constant marker."""
 import io
-import json
 import os
 
 import numpy as np
@@ -12,9 +11,8 @@ import pytest
 import torch
 
 import intensities_numpy as IN
+from batch_harness import annotated_batch, cli_runs, planted_case, result_files, run_annotator, two_ranks, weights
 from multiplexed_image_annotator_amd import _lib, colors, intensities, ops
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -144,11 +142,6 @@ def test_infinite_pixels_order_statistics_only():
 
 
 # ------------------------------------------------------------------------------------------------------------------- Annotator.cell_intensities
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "_intensit" in f}
-
-
 def _analyse(a):
     assert a.cell_intensities(integrate=True) is None
     integrated = list(a.intensity_stats)
@@ -159,16 +152,7 @@ def _analyse(a):
 @pytest.fixture(scope="module")
 def batch(tmp_path_factory):
     """the two-image batch of the cell-type plots, annotated once with "Others" among the cell types, and analysed"""
-    tmp = tmp_path_factory.mktemp("intensities")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "files": _files(out)}
+    return annotated_batch(tmp_path_factory, "intensities", _analyse, "_intensit")
 
 
 def _markers(a):
@@ -255,7 +239,7 @@ def test_files_and_maps_are_the_restatement_s(batch):
     assert log.count("Cell intensities x_integrated_intensities_summary.csv: ") == 1 and log.count("Cell intensities x_intensities_summary_1.csv: ") == 1
     before = sorted(os.listdir(os.path.join(batch["out"], "results")))
     a.cell_intensities(integrate=False, maps=False)      # no maps: the tables only, the same bytes
-    assert sorted(os.listdir(os.path.join(batch["out"], "results"))) == before and _files(batch["out"]) == files
+    assert sorted(os.listdir(os.path.join(batch["out"], "results"))) == before and result_files(batch["out"], "_intensit") == files
     assert not [f for f in a.intensity_stats[0]["image_files"] if f.endswith(".png")]
     from multiplexed_image_annotator_amd.annotator import Annotator
     root = batch["root"]
@@ -267,29 +251,12 @@ def test_files_and_maps_are_the_restatement_s(batch):
 
 def test_pipeline_switch(tmp_path):
     """without --intensities no intensity file is written and no other file changes; with it the per-image and the integrated ones appear"""
-    import main as cli
-    root = str(tmp_path / "case")
-    planted_case(root, n_cells=150, h=256, w=300)
-    markers = [m for m in open(os.path.join(root, "markers.txt")).read().split("\n") if m]
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
-        os.makedirs(mdir)
-        for m, sd in _weights().items():
-            torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
-        common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
-                  os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
-        cli.main(common + ["--main-dir", str(tmp_path / "off")])
-        cli.main(common + ["--main-dir", str(tmp_path / "on"), "--intensities"])
-    finally:
-        os.chdir(cwd)
-    off, on = (sorted(os.listdir(tmp_path / k / "results")) for k in ("off", "on"))
-    assert not [f for f in off if "_intensit" in f]
+    listing, _ = cli_runs(tmp_path, {"off": [], "on": ["--intensities"]}, "_intensit")
+    off, on = listing["off"], listing["on"]
+    markers = [m for m in open(tmp_path / "case" / "markers.txt").read().split("\n") if m]
     assert [f for f in on if "_intensit" in f] == sorted(
         ["c_intensities_0.csv", "c_integrated_intensities_summary.csv", "c_integrated_intensities.csv", "c_integrated_intensities.png",
          "c_integrated_intensities_vs_window.csv"] + [f"c_intensity_{intensities.file_slug(m)}_0.png" for m in markers])
-    assert [f for f in on if "_intensit" not in f] == off
     for f in off:
         if f.endswith(".csv") or f.endswith(".png"):
             assert open(tmp_path / "off" / "results" / f, "rb").read() == open(tmp_path / "on" / "results" / f, "rb").read(), f
@@ -308,7 +275,7 @@ def test_a_constant_marker_is_the_same_in_both_tables(tmp_path):
     from multiplexed_image_annotator_amd.annotator import Annotator
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", str(tmp_path / "out"), "k", False, False, -1, False, 0.3,
                   99.8, 0.0, 30, None)      # no normalisation: the image on the device is the file's
-    a.set_weights(_weights())
+    a.set_weights(weights())
     a.preprocess()
     a.predict(16)
     a.export_annotations()
@@ -322,30 +289,14 @@ def test_a_constant_marker_is_the_same_in_both_tables(tmp_path):
     assert other[1] > 0.0 and other[2] >= other[1]
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    out = os.path.join(root, "tiles")
-    a = _run(root, out, -1, thr)
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, thr)
     assert a.tile_mode
     integrated = _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([[s["file"] for s in integrated], [s["file"] for s in a.intensity_stats]], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [[s["file"] for s in integrated], [s["file"] for s in a.intensity_stats]]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"])
+    assert result_files(os.path.join(batch["root"], "tiles"), "_intensit") == batch["files"]
     assert wrote == [[["x_integrated_intensities_summary.csv"], ["x_intensities_summary_0.csv"]], [[], ["x_intensities_summary_1.csv"]]]

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from batch_harness import neighborhood_inputs
+from kernel_harness import fold_weight, ln_case, note_err, ps_decode, ps_encode, rnd, row_stats, stats_err
 from multiplexed_image_annotator_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -22,36 +24,6 @@ def dev():
 def _ops():
     from multiplexed_image_annotator_amd import ops
     return ops
-
-
-def ps_encode(x: torch.Tensor, kp: int, rows_pad: int = None) -> torch.Tensor:
-    """fp32 [R, K] -> packed-split fp16 bits [Rp, 2*Kp] (int16 storage) via the library's own packer."""
-    from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
-    r, k = x.shape
-    rp = rows_pad or r
-    out = torch.zeros((rp, 2 * kp), dtype=torch.int16, device=x.device)
-    check(lib().ribca_test_pack_weight(ptr(x.contiguous()), r, k, ptr(out), rp, kp, stream_ptr()), "pack")
-    return out
-
-
-def ps_decode(buf: torch.Tensor, k: int) -> torch.Tensor:
-    """packed-split [R, 2*Kp] int16 -> fp64 [R, K] (hi + lo)."""
-    r = buf.shape[0]
-    f = buf.view(torch.float16).view(r, -1, 2, 8)
-    hi, lo = f[:, :, 0, :].reshape(r, -1), f[:, :, 1, :].reshape(r, -1)
-    return (hi.double() + lo.double())[:, :k]
-
-
-def note_err(tag, err):
-    """RIBCA_TEST_REPORT=1: print the measured error next to each bound (how the bounds below were checked on hardware)."""
-    if os.environ.get("RIBCA_TEST_REPORT"):
-        import sys
-        print(f"[measured] {tag}: {err:.3e}", file=sys.__stdout__, flush=True)      # past pytest's capture: the log of a run carries the values
-
-
-def rnd(shape, seed, dev, scale=1.0):
-    n = int(np.prod(shape))
-    return (synth.approx_normal(synth.stream_key(seed, "t"), n).reshape(shape) * scale).to(torch.float32).to(dev)
 
 
 def test_pack_roundtrip(dev):
@@ -164,48 +136,6 @@ def test_split_operand_range(dev):
     assert (z.double() - ref).abs().max().item() < 65504 * 2.0 ** -23
 
 
-def _ln_case(m, d, seed, dev, mean=0.5, std=3.0, row_scale=False):
-    """rows of a packed-split residual stream with a chosen mean / spread, their exact (fp64) decode, LayerNorm parameters"""
-    z = rnd((m, d), seed, dev, std) + mean
-    if row_scale:      # spread the row scales over three decades (background tokens of a real patch sit at |z| ~ 0.02)
-        z = z * torch.logspace(-2, 1, m, device=dev, dtype=torch.float32)[:, None]
-    dp = (d + 31) // 32 * 32
-    z_ps = ps_encode(z, dp)
-    zq = ps_decode(z_ps, d)
-    g = rnd((d,), seed + 1, dev, 0.1) + 1.0
-    b = rnd((d,), seed + 2, dev, 0.1)
-    return z_ps, zq, g, b, dp
-
-
-def _row_stats(z_ps, dp, m, d, dev, recentre=False):
-    """(rstd, mean) per row of a packed-split buffer; recentre rewrites the rows as z - mean first"""
-    from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
-    rs = torch.zeros((m, 2), dtype=torch.float32, device=dev)
-    check(lib().ribca_test_row_stats(ptr(z_ps), 2 * dp, m, d, ptr(rs), 1 if recentre else 0, stream_ptr()), "row_stats")
-    return rs
-
-
-def _stats_err(rs, rows):
-    """relative error of (rstd, mean) against the fp64 statistics of `rows`; the mean is measured on the scale of the row's spread"""
-    mu = rows.mean(1)
-    rstd = 1.0 / torch.sqrt(rows.var(1, unbiased=False) + 1e-6)
-    amp = 1.0 + mu.abs() * rstd
-    e1 = ((rs[:, 0].double() - rstd).abs() / (rstd * amp)).max().item()
-    e2 = ((rs[:, 1].double() - mu).abs() * rstd / amp).max().item()
-    return e1, e2
-
-
-def _fold(w, g, b, bias, kp, dev):
-    from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
-    n, k = w.shape
-    npad = lib().ribca_gemm_padded_n(n)
-    w_ps = torch.zeros((npad, 2 * kp), dtype=torch.int16, device=dev)
-    csum = torch.zeros(n, dtype=torch.float32, device=dev)
-    bias2 = torch.zeros(n, dtype=torch.float32, device=dev)
-    check(lib().ribca_test_fold_weight(ptr(w), n, k, ptr(g), ptr(b), ptr(bias), ptr(w_ps), npad, kp, ptr(csum), ptr(bias2), stream_ptr()), "fold")
-    return w_ps, csum, bias2
-
-
 @pytest.mark.parametrize("n,k", [(432, 144), (1152, 288), (1536, 384), (2304, 576)])
 def test_fold_weight(dev, n, k):
     """gamma o W packed, csum = row sums of the PACKED values (what the MFMAs multiply the row mean with), bias2 = b + W beta"""
@@ -214,7 +144,7 @@ def test_fold_weight(dev, n, k):
     g = rnd((k,), 41, dev, 0.1) + 1.0
     b = rnd((k,), 42, dev, 0.1)
     bias = rnd((n,), 43, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, kp, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, kp, dev)
     wq = ps_decode(w_ps, kp)
     ref = (g * w).double()                                           # the kernel rounds gamma * w to fp32 once, then splits
     assert torch.all((wq[:n, :k] - ref).abs() <= ref.abs() * 2.0 ** -23 + 2.0 ** -25)
@@ -229,18 +159,18 @@ def test_fold_weight(dev, n, k):
 @pytest.mark.parametrize("mean,std", [(0.5, 3.0), (30.0, 1.0), (-300.0, 2.0)])
 def test_row_stats(dev, d, mean, std):
     m = 203
-    z_ps, zq, _, _, dp = _ln_case(m, d, 44, dev, mean, std, row_scale=(mean == 0.5))
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    z_ps, zq, _, _, dp = ln_case(m, d, 44, dev, mean, std, row_scale=(mean == 0.5))
+    rs = row_stats(z_ps, dp, m, d, dev)
     # two-pass fp32 statistics of exactly representable inputs: the mean carries 2^-24 |mu| (relative to the spread: x |mu| / sigma),
     # the centred squares then see that error twice
-    e1, e2 = _stats_err(rs, zq)
+    e1, e2 = stats_err(rs, zq)
     note_err(f"row_stats d={d} mean {mean}", max(e1, e2))
     assert e1 < 4e-7 and e2 < 4e-7, (e1, e2)
     assert torch.equal(ps_decode(z_ps, d), zq)                      # untouched
     # re-centred: the rows are rewritten as z - mean (|stored mean| << spread) and the statistics are those of what is stored
-    rs2 = _row_stats(z_ps, dp, m, d, dev, recentre=True)
+    rs2 = row_stats(z_ps, dp, m, d, dev, recentre=True)
     z2 = ps_decode(z_ps, d)
-    e1, e2 = _stats_err(rs2, z2)
+    e1, e2 = stats_err(rs2, z2)
     assert e1 < 4e-7 and e2 < 4e-7, (e1, e2)
     sig = zq.std(1, unbiased=False)
     assert torch.all(z2.mean(1).abs() <= 1e-6 * sig + 2.0 ** -21 * zq.mean(1).abs())      # the fp32 mean itself: a few ulps of |mean|
@@ -280,7 +210,7 @@ def test_gemm_resid_ps(dev, m, n, k, duo, mean, recentre):
     part = torch.zeros((tiles, m, 2), dtype=torch.float32, device=dev)
     rs = torch.zeros((m, 2), dtype=torch.float32, device=dev)
     # the forward hands the epilogue the (rstd, mean) the stored rows had: it subtracts that mean (re-centring)
-    prev = _row_stats(z_ps, npd, m, n, dev) if recentre else None
+    prev = row_stats(z_ps, npd, m, n, dev) if recentre else None
     if duo:
         wf = torch.zeros_like(w_ps)
         check(lib().ribca_test_gemm_resid_ps_duo(ptr(a_ps), 2 * kp, ptr(w_ps), 2 * kp, m, n, kp, ptr(bias), ptr(wf), ptr(z_ps), 2 * npd, ptr(part),
@@ -301,7 +231,7 @@ def test_gemm_resid_ps(dev, m, n, k, duo, mean, recentre):
     if recentre:
         assert got.mean(1).abs().max().item() < 1.0        # the offset is gone: what is left is the mean of the update itself
     # the statistics describe the rows that were STORED
-    e1, e2 = _stats_err(rs, got)
+    e1, e2 = stats_err(rs, got)
     note_err(f"resid_ps stats {m}x{n}x{k} mean {mean}", max(e1, e2))
     assert e1 < 1e-6 and e2 < 1e-6, (e1, e2)
 
@@ -313,11 +243,11 @@ def test_gemm_fold_gelu(dev, m, d, mean, std):
     two-workgroups-per-CU kernel the forward uses for M >= 4096 must give the same bits as the one-workgroup kernel"""
     from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
     n = 4 * d
-    z_ps, zq, g, b, dp = _ln_case(m, d, 50, dev, mean, std, row_scale=(mean == 0.5))
+    z_ps, zq, g, b, dp = ln_case(m, d, 50, dev, mean, std, row_scale=(mean == 0.5))
     w = rnd((n, d), 53, dev, 2.0 / np.sqrt(d))
     bias = rnd((n,), 54, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     out = torch.zeros((m, 2 * n), dtype=torch.int16, device=dev)
     check(lib().ribca_test_gemm_fold(1, ptr(z_ps), 2 * dp, ptr(w_ps), 2 * dp, m, n, dp, ptr(bias2), ptr(csum), ptr(rs), ptr(out), 2 * n,
                                      stream_ptr()), "gemm_fold")
@@ -366,11 +296,11 @@ def test_qkv_attention_fold(dev, d, cells, mean, std):
     hd = d // heads
     hdp, hdv = (hd + 7) // 8 * 8, (hd + 15) // 16 * 16
     m = cells * ntok
-    z_ps, zq, g, b, dp = _ln_case(m, d, 60, dev, mean, std)
+    z_ps, zq, g, b, dp = ln_case(m, d, 60, dev, mean, std)
     w = rnd((3 * d, d), 63, dev, 1.0 / np.sqrt(d))
     bias = rnd((3 * d,), 64, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     q = torch.zeros((cells, heads, 112, 2 * hdp), dtype=torch.int16, device=dev)
     k = torch.zeros_like(q)
     vt = torch.zeros_like(q)
@@ -402,11 +332,11 @@ def test_cell_attention_fused(dev, d, cells, mean, std):
     hd = d // heads
     hdp = (hd + 7) // 8 * 8
     m = cells * ntok
-    z_ps, zq, g, b, dp = _ln_case(m, d, 80, dev, mean, std)
+    z_ps, zq, g, b, dp = ln_case(m, d, 80, dev, mean, std)
     w = rnd((3 * d, d), 83, dev, 1.0 / np.sqrt(d))
     bias = rnd((3 * d,), 84, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     out = torch.zeros((m, 2 * dp), dtype=torch.int16, device=dev)
     check(lib().ribca_test_cell_attention(ptr(z_ps), 2 * dp, ptr(w_ps), 2 * dp, cells, d, ptr(bias2), ptr(csum), ptr(rs), ptr(out), 2 * dp, stream_ptr()),
           "cell attention")
@@ -941,9 +871,8 @@ def test_colorize_golden(dev, golden_dir, name):
 def test_knn_cooccurrence_golden(dev, golden_dir, cname):
     """ribca_knn_cooccurrence vs the CSVs the reference's neighborhood_analysis wrote (scikit-learn ball tree, spatial_methods.py:13-130)."""
     from oracle import ref_spatial
-    from test_oracle_host_logic import _neighborhood_inputs
     ops = _ops()
-    g, x, y, types, names = _neighborhood_inputs(golden_dir, cname)
+    g, x, y, types, names = neighborhood_inputs(golden_dir, cname)
     for k in (10, 25):
         m = ops.knn_cooccurrence(x, y, types, len(names), k).cpu().numpy().astype(np.float64)
         assert ref_spatial.csv_text(ref_spatial.normalize_rows(m), names) == g[f"{cname}__k{k}"]
@@ -960,10 +889,9 @@ def test_knn_cooccurrence_golden(dev, golden_dir, cname):
 
 def test_tissue_compositions_golden(dev, golden_dir):
     """ribca_knn_compositions (k = 201 via an LDS candidate buffer) vs the compositions matrix of the reference's tissue_region_partition."""
-    from test_oracle_host_logic import _neighborhood_inputs
     ops = _ops()
     g = np.load(os.path.join(golden_dir, "tissue.npz"))
-    _, x, y, types, _ = _neighborhood_inputs(golden_dir, "big")
+    _, x, y, types, _ = neighborhood_inputs(golden_dir, "big")
     got = ops.knn_compositions(x, y, types, int(types.max()) + 1)
     np.testing.assert_array_equal(got, g["compositions"])
     # small neighbourhoods agree with the register-list kernel

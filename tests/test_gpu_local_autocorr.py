@@ -3,7 +3,6 @@ tests/local_autocorr_numpy.py byte for byte (workspace and outputs pre-filled wi
 repeatability, seeds, and Annotator.local_autocorrelation() end to end: files, the CSVs against the oracle computed from the same tables, every
 painted pixel, reruns, seeds, a marker selection, errors, two ranks."""
 import io
-import json
 import os
 
 import numpy as np
@@ -13,10 +12,10 @@ import torch
 import autocorr_numpy as AN
 import enrichment_numpy as EN
 import local_autocorr_numpy as LN
+from batch_harness import planted_case, preprocessed, result_files, two_image_case, two_ranks, weights
+from kernel_harness import junk
 from multiplexed_image_annotator_amd import _lib, colors, local_autocorr, ops
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_autocorr import SHAPES, _junk, _preprocessed, _table
-from test_gpu_celltype_plots import two_image_case
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +25,7 @@ def _gpu_lag(z, idx):
     n, c = z.shape
     zd = torch.from_numpy(np.ascontiguousarray(z)).to(dev)
     idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
-    out = _junk(n * c * 8, dev).view(torch.float64).reshape(n, c)
+    out = junk(n * c * 8, dev).view(torch.float64).reshape(n, c)
     status = lib().ribca_local_lag(ptr(zd), ptr(idx_d), n, c, idx.shape[1], ptr(out), stream_ptr())
     torch.cuda.synchronize()
     return status, out.cpu().numpy()
@@ -39,9 +38,9 @@ def _gpu_counts(z, idx, lag, seed, image, p0, p):
     idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
     lag_d = torch.from_numpy(np.ascontiguousarray(lag)).to(dev)
     need = ops.local_perm_counts_ws_bytes(n, c, p)
-    ws = _junk(need, dev)
-    ge = _junk(n * c * 4, dev).view(torch.int32).reshape(n, c)
-    le = _junk(n * c * 4, dev).view(torch.int32).reshape(n, c)
+    ws = junk(need, dev)
+    ge = junk(n * c * 4, dev).view(torch.int32).reshape(n, c)
+    le = junk(n * c * 4, dev).view(torch.int32).reshape(n, c)
     status = lib().ribca_local_perm_counts(ptr(zd), ptr(idx_d), ptr(lag_d), n, c, idx.shape[1], seed, image, p0, p, ptr(ge), ptr(le), ptr(ws), need,
                                            stream_ptr())
     torch.cuda.synchronize()
@@ -57,10 +56,10 @@ def _check_counts(z, idx, seed, image, p0, p):
     return ge, le
 
 
-@pytest.mark.parametrize("n,c,m", SHAPES)
+@pytest.mark.parametrize("n,c,m", AN.SHAPES)
 def test_byte_equal_to_numpy(n, c, m):
     """the lists are random over [0, n): self entries, duplicates and sigma(j) == i all occur (at n = 2 and 5 in most permutations)"""
-    z, idx = _table(n, c, m)
+    z, idx = AN.random_table(n, c, m)
     status, got = _gpu_lag(z, idx)
     assert status == 0, lib().ribca_last_error()
     assert got.tobytes() == LN.lag(z, idx).tobytes(), (n, c, m)
@@ -71,7 +70,7 @@ def test_byte_equal_to_numpy(n, c, m):
 
 def test_neighbours_out_of_range_are_skipped():
     n, c, m = 300, 3, 6
-    z, idx = _table(n, c, m)
+    z, idx = AN.random_table(n, c, m)
     idx[7, 2], idx[9, 0], idx[11, 5], idx[299, 3] = n, -1, 2 ** 31 - 1, -(2 ** 31)
     idx[20] = -1      # a cell without a neighbour: lag = +0.0, every permuted sum ties with it
     idx[30, 1] = 30
@@ -84,18 +83,18 @@ def test_neighbours_out_of_range_are_skipped():
 
 def test_batch_edges():
     # more permutations than one batch of rows holds (32)
-    z, idx = _table(300, 5, 6)
+    z, idx = AN.random_table(300, 5, 6)
     _check_counts(z, idx, 2, 1, 0, 33)
     # the byte rule: 64 MiB of rows hold 14 permutations of 9000 cells x 64 channels, P = 15 takes a batch of 14 and one of 1
     n, c, m, p = 9000, 64, 3, 15
     need = ops.local_perm_counts_ws_bytes(n, c, p)
     assert need == 14 * n * c * 8 + (14 * n * 4 + 255) // 256 * 256 and 14 * n * c * 8 <= 64 << 20 < 15 * n * c * 8
-    z, idx = _table(n, c, m)
+    z, idx = AN.random_table(n, c, m)
     _check_counts(z, idx, 0, 0, 0, p)
 
 
 def test_split_additivity_repeatability_seeds_and_the_wrappers():
-    z, idx = _table(700, 15, 24)
+    z, idx = AN.random_table(700, 15, 24)
     lag = LN.lag(z, idx)
     status, ge7, le7 = _gpu_counts(z, idx, lag, 4, 2, 0, 7)
     assert status == 0
@@ -113,7 +112,7 @@ def test_split_additivity_repeatability_seeds_and_the_wrappers():
     counts = lambda *key, **kw: [t.cpu().numpy() for t in ops.local_perm_counts(zd, idx_d, lag_d, *key, **kw)]
     got = counts(4, 2, 0, 7)
     assert got[0].dtype == np.int64 and np.array_equal(got[0], ge7) and np.array_equal(got[1], le7)
-    got = counts(4, 2, 0, 7, ws=_junk(ops.local_perm_counts_ws_bytes(700, 15, 7), dev))
+    got = counts(4, 2, 0, 7, ws=junk(ops.local_perm_counts_ws_bytes(700, 15, 7), dev))
     assert np.array_equal(got[0], ge7) and np.array_equal(got[1], le7)
     assert not np.array_equal(counts(4, 3, 0, 7)[0], ge7)
     assert not np.array_equal(counts(5, 2, 0, 7)[0], ge7)
@@ -131,11 +130,6 @@ def test_split_additivity_repeatability_seeds_and_the_wrappers():
 P_TEST = 39      # with alpha = 1/20: significant iff no permutation reaches the observed lag on one side
 
 
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "local_autocorr" in f}
-
-
 def _slugs(a):
     return [''.join(ch if ch.isascii() and ch.isalnum() else '_' for ch in str(m)) for m in a.channel_parser.markers]
 
@@ -148,9 +142,9 @@ def batch(tmp_path_factory):
     os.makedirs(root)
     two_image_case(root)
     out = str(tmp / "one")
-    a = _preprocessed(root, out)
+    a = preprocessed(root, out)
     assert a.local_autocorrelation(n_perms=P_TEST) is None
-    return {"root": root, "tmp": str(tmp), "a": a, "out": out, "files": _files(out), "stats": list(a.local_autocorr_stats)}
+    return {"root": root, "tmp": str(tmp), "a": a, "out": out, "files": result_files(out, "local_autocorr"), "stats": list(a.local_autocorr_stats)}
 
 
 def _oracle(a, i, seed, p, k=25, alpha=0.05):
@@ -205,12 +199,12 @@ def test_files_tables_and_maps_are_the_oracle_s(batch):
 
 def test_rerun_seed_and_marker_selection(batch, monkeypatch):
     out = os.path.join(batch["tmp"], "two")
-    b = _preprocessed(batch["root"], out)
+    b = preprocessed(batch["root"], out)
     b.local_autocorrelation(n_perms=P_TEST)
-    assert _files(out) == batch["files"]
+    assert result_files(out, "local_autocorr") == batch["files"]
     monkeypatch.setenv("RIBCA_LOCAL_SEED", "5")
     b.local_autocorrelation(n_perms=P_TEST)
-    seeded = _files(out)
+    seeded = result_files(out, "local_autocorr")
     name = "x_local_autocorr_1.csv"
     assert seeded[name] != batch["files"][name] and b.local_autocorr_stats[1]["seed"] == 5
     markers = [str(m) for m in b.channel_parser.markers]
@@ -221,9 +215,9 @@ def test_rerun_seed_and_marker_selection(batch, monkeypatch):
     monkeypatch.delenv("RIBCA_LOCAL_SEED")
     # one marker: its columns and its PNG alone, the same numbers
     one = os.path.join(batch["tmp"], "three")
-    c = _preprocessed(batch["root"], one)
+    c = preprocessed(batch["root"], one)
     c.local_autocorrelation(n_perms=P_TEST, markers=[markers[1]])
-    got = _files(one)
+    got = result_files(one, "local_autocorr")
     assert sorted(got) == sorted(f"x_local_autocorr_{i}{tail}" for i in (0, 1) for tail in (".csv", "_summary.csv", f"_{_slugs(c)[1]}.png"))
     for i in (0, 1):
         full = [l.split(",") for l in batch["files"][f"x_local_autocorr_{i}.csv"].decode().strip().split("\n")]
@@ -250,7 +244,7 @@ def test_errors_leave_the_files_alone(batch):
             a.local_autocorrelation(n_perms=2)
     finally:
         a.preprocessor.intensity_full = wide
-    assert _files(batch["out"]) == batch["files"]
+    assert result_files(batch["out"], "local_autocorr") == batch["files"]
     from multiplexed_image_annotator_amd.annotator import Annotator
     fresh = Annotator(os.path.join(batch["root"], "markers.txt"), os.path.join(batch["root"], "images.csv"), "cuda", os.path.join(batch["tmp"], "fresh"), "x",
                       False, False, -1, True, 0.3, 99.8, 0.0, 30, None)
@@ -261,7 +255,6 @@ def test_errors_leave_the_files_alone(batch):
 def test_pipeline_switch(tmp_path):
     """--local-autocorr-perms 0 (the default) is off; N > 0 writes the per-image files beside the neighbourhood matrix"""
     import main as cli
-    from test_gpu_extra_cell_types import _weights, planted_case
     root = str(tmp_path / "case")
     planted_case(root, n_cells=150, h=256, w=300)
     cwd = os.getcwd()
@@ -269,7 +262,7 @@ def test_pipeline_switch(tmp_path):
     try:
         mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
         os.makedirs(mdir)
-        for m, sd in _weights().items():
+        for m, sd in weights().items():
             torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
         common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
                   os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
@@ -282,31 +275,15 @@ def test_pipeline_switch(tmp_path):
     assert "c_local_autocorr_0.csv" in on and "c_local_autocorr_0_summary.csv" in on and len(on) == 2 + len(markers)
 
 
-def _rank_worker(rank, world, port, root):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
+def _rank_body(rank, root):
     os.environ["RIBCA_SHARE_GPU"] = "1"
-    os.environ.pop("RIBCA_LOCAL_SEED", None)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    a = _preprocessed(root, os.path.join(root, "tiles"))
+    a = preprocessed(root, os.path.join(root, "tiles"))
     assert a.tile_mode
     a.local_autocorrelation(n_perms=P_TEST)
-    with open(os.path.join(root, f"local_tiles_rank{rank}.json"), "w") as f:
-        json.dump([s["file"] for s in a.local_autocorr_stats], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [s["file"] for s in a.local_autocorr_stats]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"local_tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], unset=("RIBCA_LOCAL_SEED",))
+    assert result_files(os.path.join(batch["root"], "tiles"), "local_autocorr") == batch["files"]
     assert wrote == [["x_local_autocorr_0.csv"], ["x_local_autocorr_1.csv"]]

@@ -4,7 +4,6 @@ core mask and the core / ring intensity tables byte for byte; (b) a second mask 
 and merging two gives the texts of tests/overlap_numpy.py, the painted map and the counted statistics; reruns, errors, the command line and
 two tile-per-rank ranks."""
 import io
-import json
 import os
 
 import numpy as np
@@ -12,9 +11,8 @@ import pytest
 import torch
 
 import overlap_numpy as ON
+from batch_harness import planted_case, result_files, two_image_case, two_ranks, weights
 from multiplexed_image_annotator_amd import colors
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +36,7 @@ def _annotator(root, csv, out, expand_mask=0, predict=True):
     from multiplexed_image_annotator_amd.annotator import Annotator
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, csv), "cuda", out, "x", False, False, -1, True, 0.3, 99.8, 0.0, 30, None,
                   expand_mask=expand_mask)
-    a.set_weights(_weights())
+    a.set_weights(weights())
     a.preprocess()
     if predict:
         a.predict(16)
@@ -46,9 +44,8 @@ def _annotator(root, csv, out, expand_mask=0, predict=True):
     return a
 
 
-def _files(out, keys=("_matching", "intensities_inner", "intensities_outer")):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if any(k in f for k in keys)}
+def _files(out):
+    return result_files(out, ("_matching", "intensities_inner", "intensities_outer"))
 
 
 def _match_both_ways(a):
@@ -207,7 +204,7 @@ def test_pipeline_switch(tmp_path):
     try:
         mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
         os.makedirs(mdir)
-        for m, sd in _weights().items():
+        for m, sd in weights().items():
             torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
         common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
                   os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
@@ -230,29 +227,14 @@ def test_pipeline_switch(tmp_path):
     assert rows == want["objects_csv"]
 
 
-def _rank_worker(rank, world, port, root):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
+def _rank_body(rank, root):
     a = _annotator(root, "match.csv", os.path.join(root, "tiles"))
     assert a.tile_mode
     integrated = _match_both_ways(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([[s["file"] for s in integrated], [s["file"] for s in a.matching_stats]], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [[s["file"] for s in integrated], [s["file"] for s in a.matching_stats]]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"]), nprocs=2, join=True)
+    wrote = two_ranks(_rank_body, batch["root"])
     assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
     assert wrote == [[["x_integrated_matching_agreement.csv"], ["x_matching_agreement_0.csv"]], [[], ["x_matching_agreement_1.csv"]]]

@@ -4,7 +4,6 @@ that are no multiple of the pixel tile and thinner than the halo, more cells in 
 cells far from the origin, the contact graph's border lengths; and Annotator.cell_morphology() end to end: files against the restatement run on
 the same masks, the maps' scales, the pipeline switch, two ranks."""
 import io
-import json
 import os
 
 import numpy as np
@@ -13,10 +12,9 @@ import torch
 
 import contact_numpy as CN
 import morphology_numpy as MN
+from batch_harness import annotated_batch, cli_runs, result_files, run_annotator, two_ranks
 from multiplexed_image_annotator_amd import _lib, colors, morphology, ops
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -181,11 +179,6 @@ def test_the_rectangle_is_the_window_the_patch_kernels_crop(patch):
 
 
 # ---- end to end: (h) -----------------------------------------------------------------------------------------------------------------------------
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "_morphology" in f}
-
-
 def _analyse(a):
     assert a.cell_morphology(integrate=True) is None
     integrated = list(a.morphology_stats)
@@ -196,16 +189,7 @@ def _analyse(a):
 @pytest.fixture(scope="module")
 def batch(tmp_path_factory):
     """the two-image batch of the cell-type plots, annotated once with "Others" among the cell types, and analysed"""
-    tmp = tmp_path_factory.mktemp("morphology")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "files": _files(out)}
+    return annotated_batch(tmp_path_factory, "morphology", _analyse, "_morphology")
 
 
 def _restated(a, i):
@@ -289,27 +273,10 @@ def test_files_and_maps_are_the_restatement_s(batch):
 
 def test_pipeline_switch(tmp_path):
     """without --morphology no morphology file is written and no other file changes; with it the per-image and the integrated ones appear"""
-    import main as cli
-    root = str(tmp_path / "case")
-    planted_case(root, n_cells=150, h=256, w=300)
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        mdir = "src/multiplexed_image_annotator/cell_type_annotation/models"
-        os.makedirs(mdir)
-        for m, sd in _weights().items():
-            torch.save({"model": sd}, os.path.join(mdir, m + ".pth"))
-        common = ["--marker-list-path", os.path.join(root, "markers.txt"), "--image-path", os.path.join(root, "img.npy"), "--mask-path",
-                  os.path.join(root, "mask.npy"), "--batch-id", "c", "--no-infer", "--bs", "16", "--confidence", "0.0", "--n-regions", "0"]
-        cli.main(common + ["--main-dir", str(tmp_path / "off")])
-        cli.main(common + ["--main-dir", str(tmp_path / "on"), "--morphology"])
-    finally:
-        os.chdir(cwd)
-    off, on = (sorted(os.listdir(tmp_path / k / "results")) for k in ("off", "on"))
-    assert not [f for f in off if "morphology" in f]
+    listing, _ = cli_runs(tmp_path, {"off": [], "on": ["--morphology"]}, "morphology")
+    off, on = listing["off"], listing["on"]
     assert [f for f in on if "morphology" in f] == sorted(["c_morphology_0.csv", "c_morphology_diameter_0.png", "c_morphology_coverage_0.png",
                                                           "c_integrated_morphology_summary.csv", "c_integrated_morphology.csv", "c_integrated_morphology.png"])
-    assert [f for f in on if "morphology" not in f] == off
     for f in off:
         if f.endswith(".csv") or f.endswith(".png"):
             assert open(tmp_path / "off" / "results" / f, "rb").read() == open(tmp_path / "on" / "results" / f, "rb").read(), f
@@ -317,30 +284,14 @@ def test_pipeline_switch(tmp_path):
     assert rows[0] == "cell_id,cell_type," + ",".join(morphology.FEATURES) and len(rows) > 100
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    out = os.path.join(root, "tiles")
-    a = _run(root, out, -1, thr)
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, thr)
     assert a.tile_mode
     integrated = _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([[s["file"] for s in integrated], [s["file"] for s in a.morphology_stats]], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [[s["file"] for s in integrated], [s["file"] for s in a.morphology_stats]]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"])
+    assert result_files(os.path.join(batch["root"], "tiles"), "_morphology") == batch["files"]
     assert wrote == [[["x_integrated_morphology_summary.csv"], ["x_morphology_summary_0.csv"]], [[], ["x_morphology_summary_1.csv"]]]

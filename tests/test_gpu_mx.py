@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import mx_emulation as mx
-from test_gpu_kernels import _fold, _ln_case, _row_stats, _stats_err, note_err, ps_decode, ps_encode, rnd
+from kernel_harness import fold_weight, ln_case, note_err, ps_decode, ps_encode, rnd, row_stats, stats_err
 
 pytestmark = pytest.mark.gpu
 
@@ -196,7 +196,7 @@ def test_gemm_mx_resid(dev, m, n, k, recentre):
     tiles = n // 48
     part = torch.zeros((tiles, m, 2), dtype=torch.float32, device=dev)
     rs = torch.zeros((m, 2), dtype=torch.float32, device=dev)
-    prev = _row_stats(z_ps, npd, m, n, dev) if recentre else None
+    prev = row_stats(z_ps, npd, m, n, dev) if recentre else None
     check(lib().ribca_test_gemm_mx_resid(ptr(a_ps), 2 * k, ptr(w_ps), 2 * k, m, n, k, ptr(bias), ptr(hi_p), ptr(l8_p), ptr(sc_p), ptr(wh), ptr(wx),
                                          ptr(z_ps), 2 * npd, ptr(part), ptr(rs), ptr(prev) if recentre else None, stream_ptr()), "gemm_mx_resid")
     got = ps_decode(z_ps, n)
@@ -220,7 +220,7 @@ def test_gemm_mx_resid(dev, m, n, k, recentre):
     note_err(f"gemm_mx vs exact product {m}x{n}x{k}", e_ref)
     assert e_ref < 3e-5, e_ref
     assert torch.all(ps_decode(z_ps, npd)[:, n:] == 0)
-    e1, e2 = _stats_err(rs, got)
+    e1, e2 = stats_err(rs, got)
     note_err(f"gemm_mx stats {m}x{n}x{k}", max(e1, e2))
     assert e1 < 1e-6 and e2 < 1e-6, (e1, e2)
 
@@ -234,11 +234,11 @@ def test_gemm_gelu_mx(dev, m, d, mean, std):
     boundary sits every 2^-4 relative: about one value in 64 (measured 1.54-1.60 %), one code step each"""
     from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
     n = 4 * d
-    z_ps, zq, g, b, dp = _ln_case(m, d, 50, dev, mean, std, row_scale=(mean == 0.5))
+    z_ps, zq, g, b, dp = ln_case(m, d, 50, dev, mean, std, row_scale=(mean == 0.5))
     w = rnd((n, d), 53, dev, 2.0 / np.sqrt(d))
     bias = rnd((n,), 54, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     wf = torch.zeros_like(w_ps)
     hi_p, l8_p, sc_p = _planes(m, n, dev)
     check(lib().ribca_test_gemm_gelu_mx(ptr(z_ps), 2 * dp, ptr(w_ps), 2 * dp, m, n, dp, ptr(bias2), ptr(csum), ptr(rs), ptr(wf), ptr(hi_p), ptr(l8_p),
@@ -270,11 +270,11 @@ def test_gemm_mx_fc1(dev, m, d, mean, std):
     emitted hi plane, and against the fp16x3 kernel's output"""
     from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
     n = 4 * d
-    z_ps, zq, g, b, dp = _ln_case(m, d, 50, dev, mean, std, row_scale=(mean == 0.5))
+    z_ps, zq, g, b, dp = ln_case(m, d, 50, dev, mean, std, row_scale=(mean == 0.5))
     w = rnd((n, d), 53, dev, 2.0 / np.sqrt(d))
     bias = rnd((n,), 54, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     kz = (dp + 127) // 128 * 128
     a_hi, a_l8, a_sc = _planes(m, kz, dev)
     wh = torch.zeros(lib().ribca_test_mx_weight_bytes(n, kz, 0), dtype=torch.uint8, device=dev)
@@ -315,11 +315,11 @@ def test_qkv_attention_mx(dev, d, cells, mean, std):
     hd = d // heads
     hdp = (hd + 7) // 8 * 8
     m = cells * ntok
-    z_ps, zq, g, b, dp = _ln_case(m, d, 60, dev, mean, std)
+    z_ps, zq, g, b, dp = ln_case(m, d, 60, dev, mean, std)
     w = rnd((3 * d, d), 63, dev, 1.0 / np.sqrt(d))
     bias = rnd((3 * d,), 64, dev, 0.1)
-    w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     kz = (dp + 127) // 128 * 128
     a_hi, a_l8, a_sc = _planes(m, kz, dev)
     wh = torch.zeros(lib().ribca_test_mx_weight_bytes(3 * d, kz, 0), dtype=torch.uint8, device=dev)
@@ -366,7 +366,7 @@ def test_gemm_resid_zmx(dev, kind, m, n, k, recentre):
     w_ps = ps_encode(w, k, lib().ribca_gemm_padded_n(n))
     z_ps = ps_encode(z0, npd)
     z_ref = z_ps.clone()
-    prev = _row_stats(z_ps, npd, m, n, dev) if recentre else None
+    prev = row_stats(z_ps, npd, m, n, dev) if recentre else None
     tiles = n // 48
     part = torch.zeros((tiles, m, 2), dtype=torch.float32, device=dev)
     rs = torch.zeros((m, 2), dtype=torch.float32, device=dev)

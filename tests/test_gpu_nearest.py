@@ -5,7 +5,6 @@ per-cell table against the ops results, the tables against the oracle computed f
 refusals, two ranks."""
 import ctypes
 import io
-import json
 import os
 
 import numpy as np
@@ -14,10 +13,9 @@ import torch
 
 import enrichment_numpy as EN
 import nearest_numpy as NN
+from batch_harness import annotated_batch, result_files, run_annotator, two_ranks
 from multiplexed_image_annotator_amd import _lib, colors, cooccurrence, nearest, ops
 from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run
 
 pytestmark = pytest.mark.gpu
 
@@ -235,11 +233,6 @@ RADII = [25.0, 60.0, 120.0, 250.0]
 PERMS = 6
 
 
-def _files(out):
-    res = os.path.join(out, "results")
-    return {f: open(os.path.join(res, f), "rb").read() for f in sorted(os.listdir(res)) if "_nearest_" in f}
-
-
 def _analyse(a, **kw):
     assert a.nearest_type_distances(radii=RADII, n_perms=PERMS, integrate=True, **kw) is None
     integrated = list(a.nearest_stats)
@@ -250,16 +243,7 @@ def _analyse(a, **kw):
 @pytest.fixture(scope="module")
 def batch(tmp_path_factory):
     """the two-image batch of the cell-type plots, annotated once with "Others" among the cell types, and analysed"""
-    tmp = tmp_path_factory.mktemp("nearest")
-    root = str(tmp / "case")
-    os.makedirs(root)
-    two_image_case(root)
-    probe = _run(root, str(tmp / "probe"), -1, 0.0)
-    thr = float(np.median(np.concatenate(probe._conf_arrays)))
-    out = str(tmp / "one")
-    a = _run(root, out, -1, thr)
-    integrated = _analyse(a)
-    return {"root": root, "tmp": str(tmp), "thr": thr, "a": a, "out": out, "integrated": integrated, "files": _files(out)}
+    return annotated_batch(tmp_path_factory, "nearest", _analyse, "_nearest_")
 
 
 def _xy(a, i):
@@ -360,20 +344,20 @@ def test_files_tables_and_maps_are_the_oracle_s(batch):
 
 def test_targets_restrict_the_maps_and_a_second_run_writes_the_same_bytes(batch):
     out = os.path.join(batch["tmp"], "two")
-    b = _run(batch["root"], out, -1, batch["thr"])
+    b = run_annotator(batch["root"], out, -1, batch["thr"])
     names = [str(c) for c in b.cell_types]
     b.nearest_type_distances(radii=RADII, n_perms=0, integrate=False, targets=[names[1], 0])
-    maps = sorted(f for f in _files(out) if f.endswith(".png") and "_table" not in f)
+    maps = sorted(f for f in result_files(out, "_nearest_") if f.endswith(".png") and "_table" not in f)
     assert maps == sorted(f"x_nearest_{cooccurrence.slug(names[k])}_{i}.png" for k in (1, 0) for i in (0, 1))
     # without a null: no z figure, and the table has the seven columns
-    assert not [f for f in _files(out) if f.endswith("_z_0.png")]
-    assert _files(out)["x_nearest_table_0.csv"].decode().split("\n")[0] == "anchor,target,anchor_cells,r,count,cum_count,G"
-    assert all(_files(out)[f] == batch["files"][f] for f in maps if f in batch["files"])
+    assert not [f for f in result_files(out, "_nearest_") if f.endswith("_z_0.png")]
+    assert result_files(out, "_nearest_")["x_nearest_table_0.csv"].decode().split("\n")[0] == "anchor,target,anchor_cells,r,count,cum_count,G"
+    assert all(result_files(out, "_nearest_")[f] == batch["files"][f] for f in maps if f in batch["files"])
     for f in os.listdir(os.path.join(out, "results")):
         if "_nearest_" in f:
             os.remove(os.path.join(out, "results", f))
     _analyse(b)
-    assert _files(out) == batch["files"]
+    assert result_files(out, "_nearest_") == batch["files"]
     # the default radii: 16 of one cell size
     b.nearest_type_distances(integrate=True, targets=[0])
     assert b.nearest_stats[0]["radii"] == [30.0 * k for k in range(1, 17)] and b.nearest_stats[0]["B"] == 16 and b.nearest_stats[0]["P"] == 0
@@ -406,7 +390,7 @@ def test_errors_leave_the_files_alone(batch, monkeypatch):
     with pytest.raises(ValueError, match="at most 10 cells per image"):
         a.nearest_type_distances(radii=RADII)
     monkeypatch.undo()
-    assert _files(batch["out"]) == batch["files"]
+    assert result_files(batch["out"], "_nearest_") == batch["files"]
     from multiplexed_image_annotator_amd.annotator import Annotator
     root = batch["root"]
     fresh = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", os.path.join(batch["tmp"], "fresh"), "x", False, False,
@@ -417,40 +401,24 @@ def test_errors_leave_the_files_alone(batch, monkeypatch):
 
 def test_the_seed_switch_moves_the_null_and_nothing_else(batch, monkeypatch):
     out = os.path.join(batch["tmp"], "seeded")
-    b = _run(batch["root"], out, -1, batch["thr"])
+    b = run_annotator(batch["root"], out, -1, batch["thr"])
     monkeypatch.setenv("RIBCA_NEAREST_SEED", "5")
     b.nearest_type_distances(radii=RADII, n_perms=PERMS, integrate=True)
     assert b.nearest_stats[0]["seed"] == 5
-    got = _files(out)
+    got = result_files(out, "_nearest_")
     assert got["x_nearest_0.csv"] == batch["files"]["x_nearest_0.csv"]
     rows, base = got["x_integrated_nearest_table.csv"].decode().split("\n"), batch["files"]["x_integrated_nearest_table.csv"].decode().split("\n")
     assert [r.split(",")[:7] for r in rows] == [r.split(",")[:7] for r in base] and rows != base
 
 
-def _rank_worker(rank, world, port, root, thr):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    out = os.path.join(root, "tiles")
-    a = _run(root, out, -1, thr)
+def _rank_body(rank, root, thr):
+    a = run_annotator(root, os.path.join(root, "tiles"), -1, thr)
     assert a.tile_mode
     integrated = _analyse(a)
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump([[s["file"] for s in integrated], [s["file"] for s in a.nearest_stats]], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return [[s["file"] for s in integrated], [s["file"] for s in a.nearest_stats]]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(batch):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, batch["root"], batch["thr"]), nprocs=2, join=True)
-    assert _files(os.path.join(batch["root"], "tiles")) == batch["files"]
-    wrote = [json.load(open(os.path.join(batch["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
+    wrote = two_ranks(_rank_body, batch["root"], batch["thr"])
+    assert result_files(os.path.join(batch["root"], "tiles"), "_nearest_") == batch["files"]
     assert wrote == [[["x_integrated_nearest_table.csv"], ["x_nearest_table_0.csv"]], [[], ["x_nearest_table_1.csv"]]]

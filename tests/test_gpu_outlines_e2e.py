@@ -10,10 +10,8 @@ import numpy as np
 import pytest
 
 import outlines_numpy as ON
+from batch_harness import paint_faults, two_image_case, weights
 from multiplexed_image_annotator_amd import outlines
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _weights
-from test_gpu_repair_e2e import paint_faults
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +20,7 @@ def _annotator(root, out, **kw):
     from multiplexed_image_annotator_amd.annotator import Annotator
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", out, "x", False, False, -1, True, 0.3, 99.8, 0.0, 30, None,
                   **kw)
-    a.set_weights(_weights())
+    a.set_weights(weights())
     return a
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import regions_numpy as R
+from batch_harness import two_ranks
 from multiplexed_image_annotator_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -283,36 +284,19 @@ def test_backend_switch_decides_whether_scikit_learn_is_imported(tmp_path, backe
     assert f"SKLEARN_IMPORTED {1 if backend == 'sklearn' else 0}" in r.stdout, r.stdout
 
 
-def _rank_worker(rank, world, port, root, seed):
+def _rank_body(rank, root, seed):
     """One rank of the cell-sharded Annotator (both ranks share the device; gloo carries the all-gather): every rank computes the regions on
-    its own, no collective, and saves them."""
-    import json
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
+    its own, no collective, and returns them."""
     a = _run(root, "sharded", seed, write=False)
-    with open(os.path.join(root, f"regions_rank{rank}.json"), "w") as f:
-        json.dump(sorted(a.tissue_regions[0].items()), f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return sorted(a.tissue_regions[0].items())
 
 
 def test_two_ranks_agree_with_each_other_and_with_one_rank(tmp_path, monkeypatch):
-    import json
-    import socket
-    import torch.multiprocessing as mp
     monkeypatch.delenv("RIBCA_REGIONS", raising=False)
     monkeypatch.delenv("RIBCA_REGION_SEED", raising=False)
     seed = synth.SEED_BASE + 81
     root = str(tmp_path)
     _write_case(root, seed)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, root, seed), nprocs=2, join=True)
+    r0, r1 = two_ranks(_rank_body, root, seed, tile=None)
     one = _run(root, "single", seed, write=False)
-    r0 = json.load(open(os.path.join(root, "regions_rank0.json")))
-    r1 = json.load(open(os.path.join(root, "regions_rank1.json")))
     assert r0 == r1 == [[k, v] for k, v in sorted(one.tissue_regions[0].items())]

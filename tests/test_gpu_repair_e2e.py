@@ -4,7 +4,6 @@ that does not pass the argument; with 3 every stage reads the mask tests/compone
 masks, the label table, the lazy pixel lists, the .npy and the repair CSV, the morphology areas --, cell_morphology reports an Euler number
 of 1 for every cell but the one around the foreign speck, repair_mask=3 with expand_mask=2 is the restated expansion of the repaired mask,
 and two tile-per-rank ranks write the single-rank bytes."""
-import json
 import os
 
 import numpy as np
@@ -13,9 +12,8 @@ import torch
 
 import components_numpy as CN
 import expand_numpy as EN
+from batch_harness import paint_faults, run_annotator, two_image_case, two_ranks, weights
 from multiplexed_image_annotator_amd import _lib, ops
-from test_gpu_celltype_plots import two_image_case
-from test_gpu_extra_cell_types import _run, _weights
 
 pytestmark = pytest.mark.gpu
 
@@ -23,36 +21,11 @@ A = 3
 D = 2
 
 
-def paint_faults(mask):
-    """the four faults, placed by what the mask holds; returns the label of the cell whose hole keeps a foreign speck"""
-    from scipy import ndimage
-    mask = mask.copy()
-    h, w = mask.shape
-    solid = (ndimage.minimum_filter(mask, size=9) == ndimage.maximum_filter(mask, size=9)) & (mask > 0)      # 9 x 9 of one label around
-    rr, cc = np.nonzero(solid)
-    centres = {}
-    for r, c in zip(rr.tolist(), cc.tolist()):
-        centres.setdefault(int(mask[r, c]), (r, c))
-    ids = sorted(centres)
-    assert len(ids) >= 6
-    a, b, holed, outer, foreign = ids[0], ids[-1], ids[1], ids[2], ids[3]
-    mask[mask == b] = a                                   # a label torn in two: cell b becomes a second piece of a
-    r, c = centres[holed]
-    mask[r, c] = 0                                        # a hole of one pixel
-    r, c = centres[outer]
-    mask[r - 2:r + 3, c - 2:c + 3] = 0                    # a hole of 5 x 5 ...
-    mask[r:r + 2, c:c + 2] = foreign                      # ... with four pixels of another cell's label inside
-    empty = ndimage.maximum_filter(mask, size=7) == 0
-    r, c = np.argwhere(empty)[0]
-    mask[r, c:c + 2] = ids[4]                             # a speck of two pixels in open background
-    return mask, outer
-
-
 def _run_repaired(root, out, **kw):
     from multiplexed_image_annotator_amd.annotator import Annotator
     a = Annotator(os.path.join(root, "markers.txt"), os.path.join(root, "images.csv"), "cuda", out, "x", False, False, -1, True, 0.3, 99.8, 0.0, 30, None,
                   **kw)
-    a.set_weights(_weights())
+    a.set_weights(weights())
     a.preprocess()
     a.predict(16)
     a.export_annotations()
@@ -83,7 +56,7 @@ def runs(tmp_path_factory):
         np.save(path, mask)
         read.append(mask)
         outer.append(enclosing)
-    plain = _run(root, str(tmp / "plain"), -1, 0.0)
+    plain = run_annotator(root, str(tmp / "plain"), -1, 0.0)
     zero = _run_repaired(root, str(tmp / "zero"), repair_mask=0)
     fixed = _run_repaired(root, str(tmp / "fixed"), repair_mask=A)
     both = _run_repaired(root, str(tmp / "both"), repair_mask=A, expand_mask=D)
@@ -176,30 +149,15 @@ def test_repair_then_expand_is_the_restated_expansion_of_the_repaired_mask(runs)
     assert len(both.repair_stats) == 2 and len(both.expansion_stats) == 2
 
 
-def _rank_worker(rank, world, port, root):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["RIBCA_TILE_MODE"] = "1"
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
+def _rank_body(rank, root):
     a = _run_repaired(root, os.path.join(root, "tiles"), repair_mask=A)
     assert a.tile_mode and len(a.repair_stats) == 1
-    with open(os.path.join(root, f"tiles_rank{rank}.json"), "w") as f:
-        json.dump(a.repair_stats[0]["files"], f)
-    tdist.barrier()
-    tdist.destroy_process_group()
+    return a.repair_stats[0]["files"]
 
 
 def test_two_ranks_tile_per_rank_write_the_single_rank_bytes(runs):
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, runs["root"]), nprocs=2, join=True)
+    wrote = two_ranks(_rank_body, runs["root"])
     single = {f: b for f, b in _files(os.path.join(runs["tmp"], "fixed")).items() if "_repair" in f}
     tiles = {f: b for f, b in _files(os.path.join(runs["root"], "tiles")).items() if "_repair" in f}
     assert sorted(single) == ["x_repair_0.csv", "x_repair_1.csv", "x_repaired_mask_0.npy", "x_repaired_mask_1.npy"] and tiles == single
-    wrote = [json.load(open(os.path.join(runs["root"], f"tiles_rank{r}.json"))) for r in (0, 1)]
     assert wrote == [["x_repaired_mask_0.npy", "x_repair_0.csv"], ["x_repaired_mask_1.npy", "x_repair_1.csv"]]

@@ -14,9 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import BAND, Arena, fold_weight, ln_case, ps_decode, ps_encode, rnd, row_stats, umap_graph
 from multiplexed_image_annotator_amd import synth
-from test_gpu_guards import BAND, Arena
-from test_gpu_kernels import _fold, _ln_case, _row_stats, ps_decode, ps_encode, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -50,10 +49,10 @@ def _attn_launcher(dev, kind, d, cells):
             check(lib().ribca_test_qkv_attention(ptr(y_ps), 2 * dp, ptr(w_ps), 2 * dp, cells, d, dp, ptr(bias), ptr(q), ptr(k), ptr(vt), ptr(out), 2 * dp,
                                                  stream_ptr()), "qkv + attention")
         return launch
-    z_ps, _, g, b, dp = _ln_case(m, d, 60, dev, 0.5, 1.0)
+    z_ps, _, g, b, dp = ln_case(m, d, 60, dev, 0.5, 1.0)
     w = rnd((3 * d, d), 63, dev, 1.0 / np.sqrt(d))
-    w_ps, csum, bias2 = _fold(w, g, b, rnd((3 * d,), 64, dev, 0.1), dp, dev)
-    rs = _row_stats(z_ps, dp, m, d, dev)
+    w_ps, csum, bias2 = fold_weight(w, g, b, rnd((3 * d,), 64, dev, 0.1), dp, dev)
+    rs = row_stats(z_ps, dp, m, d, dev)
     if kind == "fold":
         def launch(q, k, vt, out):
             check(lib().ribca_test_qkv_attention_fold(ptr(z_ps), 2 * dp, ptr(w_ps), 2 * dp, cells, d, dp, ptr(bias2), ptr(csum), ptr(rs), ptr(q), ptr(k),
@@ -367,8 +366,7 @@ def _case_scatter_raster(dev, h, w, n):
 
 def _case_umap_optimize(dev, n, dim, epochs):
     from multiplexed_image_annotator_amd import manifold, ops
-    from test_gpu_umap import _graph
-    g, eps, rev = _graph(n, dim)
+    g, eps, rev = umap_graph(n, dim)
     a, b = manifold.find_ab_params()
     emb0 = torch.from_numpy(np.ascontiguousarray(manifold.initial_embedding(g, dim, 0), dtype=np.float32)).to(dev)
     indptr, indices = torch.from_numpy(g.indptr.astype(np.int64)).to(dev), torch.from_numpy(g.indices.astype(np.int32)).to(dev)

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import umap_restatement as R
+from kernel_harness import umap_graph
 from multiplexed_image_annotator_amd import _lib, manifold, ops
 
 pytestmark = pytest.mark.gpu
@@ -85,14 +86,6 @@ def test_fuzzy_weights_match_restatement():
     assert np.allclose(w, R.membership(idx, dist, rs, rr), rtol=1e-5, atol=1e-7)
 
 
-def _graph(n, seed, n_epochs=500):
-    x = np.random.RandomState(seed).randn(n, 6).astype(np.float32)
-    idx, dist = R.knn(x, 15)
-    sigma, rho = R.smooth_knn_dist(dist)
-    g = manifold.prune_graph(manifold.fuzzy_union(idx, R.membership(idx, dist, sigma, rho), n), n_epochs)
-    return g, manifold.epochs_per_sample(g.data, n_epochs), manifold.reverse_edges(g)
-
-
 def _gpu_optimize(emb, g, eps, rev, epochs, n_epochs, a, b, seed):
     dev = _lib.require_gpu()
     e = torch.from_numpy(emb.copy()).to(dev)
@@ -103,7 +96,7 @@ def _gpu_optimize(emb, g, eps, rev, epochs, n_epochs, a, b, seed):
 
 @pytest.mark.parametrize("dim", [2, 5])
 def test_sgd_matches_restated_jacobi_epochs(dim):
-    g, eps, rev = _graph(400, dim)
+    g, eps, rev = umap_graph(400, dim)
     a, b = manifold.find_ab_params()
     emb0 = manifold.initial_embedding(g, dim, 0)
     for epochs in (1, 3, 10):
@@ -114,7 +107,7 @@ def test_sgd_matches_restated_jacobi_epochs(dim):
 
 
 def test_sgd_is_deterministic_and_seeded():
-    g, eps, rev = _graph(1500, 1)
+    g, eps, rev = umap_graph(1500, 1)
     a, b = manifold.find_ab_params()
     emb0 = manifold.initial_embedding(g, 5, 0)
     r1 = _gpu_optimize(emb0, g, eps, rev, 50, 500, a, b, 3)

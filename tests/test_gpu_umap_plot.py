@@ -8,8 +8,8 @@ import torch
 
 import scatter_numpy as SC
 import umap_restatement as R
+from batch_harness import planted_case, run_annotator, two_ranks
 from multiplexed_image_annotator_amd import _lib, manifold, ops
-from test_gpu_extra_cell_types import _run, planted_case
 
 pytestmark = pytest.mark.gpu
 
@@ -130,18 +130,18 @@ def test_umap_visualization_end_to_end(tmp_path, monkeypatch):
     root = str(tmp_path / "case")
     planted_case(root)
     out1, out2, out3 = (str(tmp_path / d) for d in ("one", "two", "three"))
-    a = _run(root, out1, -1, 0.0)
+    a = run_annotator(root, out1, -1, 0.0)
     emb = a.umap_visualization()
     assert emb is not None      # the parent commit logs "skipped", returns None and writes nothing
     png, csv = _check_plot(a, emb, out1, "x")
     s = a.umap_stats
     assert s["n"] == len(emb) and s["spectral_backend"] == "gpu" and s["spectral_gpu_components"] >= 1 and s["spectral_iterations"] >= 0 and s["seed"] == 0 and s["skipped_points"] == 0
     assert len(set(a.annotations[0])) >= 2      # more than one colour on the canvas
-    b = _run(root, out2, -1, 0.0)
+    b = run_annotator(root, out2, -1, 0.0)
     assert np.array_equal(b.umap_visualization(), emb)
     assert _files(out2, "x") == (png, csv)
     monkeypatch.setenv("RIBCA_SPECTRAL", "scipy")
-    c = _run(root, out3, -1, 0.0)
+    c = run_annotator(root, out3, -1, 0.0)
     emb_c = c.umap_visualization()
     _check_plot(c, emb_c, out3, "x")
     assert c.umap_stats["spectral_backend"] == "scipy" and c.umap_stats["spectral_iterations"] is None
@@ -163,33 +163,21 @@ def test_umap_visualization_before_predict_and_on_tiny_batches(tmp_path):
     assert not os.path.exists(os.path.join(str(tmp_path / "o"), "results", "t_umap.png"))
 
 
-def _rank_worker(rank, world, port, root):
-    import torch.distributed as tdist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    tdist.init_process_group("gloo", rank=rank, world_size=world)
-    a = _run(root, os.path.join(root, "sharded"), -1, 0.0, batch="r")
+def _rank_body(rank, root):
+    a = run_annotator(root, os.path.join(root, "sharded"), -1, 0.0, batch="r")
     assert not a.tile_mode
     emb = a.umap_visualization()
     assert emb is not None and emb.shape == (sum(len(x) for x in a.annotations), 2)
     np.save(os.path.join(root, f"emb_rank{rank}.npy"), emb)
-    tdist.barrier()
-    tdist.destroy_process_group()
 
 
 def test_two_ranks_only_rank0_writes(tmp_path):
-    import socket
-    import torch.multiprocessing as mp
     root = str(tmp_path / "case")
     planted_case(root, n_cells=200, h=300, w=340)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mp.spawn(_rank_worker, args=(2, port, root), nprocs=2, join=True)
+    two_ranks(_rank_body, root, tile=None)
     e0, e1 = np.load(os.path.join(root, "emb_rank0.npy")), np.load(os.path.join(root, "emb_rank1.npy"))
     assert np.array_equal(e0, e1)
-    one = _run(root, os.path.join(root, "single"), -1, 0.0, batch="r")
+    one = run_annotator(root, os.path.join(root, "single"), -1, 0.0, batch="r")
     assert np.array_equal(one.umap_visualization(), e0)
     assert _files(os.path.join(root, "sharded"), "r") == _files(os.path.join(root, "single"), "r")
     found = [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(root, "sharded")) for f in fs if "umap" in f]

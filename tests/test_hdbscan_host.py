@@ -8,12 +8,6 @@ import pytest
 
 import hdbscan_numpy as H
 
-# (seed, n, min_cluster_size): the planted inputs the feature was specified on
-PLANTED = [(0, 1500, 10), (1, 1500, 25), (2, 3000, 50), (3, 3000, 10), (4, 2000, 5), (5, 3000, 20), (6, 2500, 15)]
-# after the best one-to-one renaming at most 0.5 % of the points may differ from sklearn.cluster.HDBSCAN (ties between equal
-# mutual-reachability weights are broken by index here, by Prim's visiting order there)
-CAP = 0.005
-
 
 def _sklearn_tree_routines():
     """sklearn's private tree routines; another sklearn without them skips"""
@@ -70,7 +64,7 @@ def test_tree_code_matches_sklearn_routines_on_the_same_tree(case):
         assert labels.max() + 1 >= 6
 
 
-@pytest.mark.parametrize("seed,n,m", PLANTED)
+@pytest.mark.parametrize("seed,n,m", H.PLANTED)
 def test_oracle_and_tree_code_match_sklearn_hdbscan(seed, n, m):
     from sklearn.cluster import HDBSCAN
     from multiplexed_image_annotator_amd import manifold
@@ -81,7 +75,7 @@ def test_oracle_and_tree_code_match_sklearn_hdbscan(seed, n, m):
     diff = H.best_renaming_mismatches(ref, labels)
     print(f"[hdbscan oracle vs sklearn] seed {seed} n {n} m {m}: {labels.max() + 1} / {ref.max() + 1} clusters, {diff} points differ")
     assert labels.max() == ref.max()
-    assert diff <= CAP * n
+    assert diff <= H.CAP * n
 
 
 def test_parameter_validation_raises_what_sklearn_raises():

@@ -6,16 +6,16 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import mx_emulation as mx
 import test_gpu_mx as T
-from test_gpu_kernels import _fold, _ln_case, _row_stats, rnd, ps_decode
+from kernel_harness import fold_weight, ln_case, ps_decode, rnd, row_stats
 from multiplexed_image_annotator_amd import _lib
 from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
 dev = _lib.require_gpu()
 m, d, mean, std = 7001, 288, 0.5, 3.0
 n = 4 * d
-z_ps, zq, g, b, dp = _ln_case(m, d, 50, dev, mean, std, row_scale=True)
+z_ps, zq, g, b, dp = ln_case(m, d, 50, dev, mean, std, row_scale=True)
 w = rnd((n, d), 53, dev, 2.0 / np.sqrt(d)); bias = rnd((n,), 54, dev, 0.1)
-w_ps, csum, bias2 = _fold(w, g, b, bias, dp, dev)
-rs = _row_stats(z_ps, dp, m, d, dev)
+w_ps, csum, bias2 = fold_weight(w, g, b, bias, dp, dev)
+rs = row_stats(z_ps, dp, m, d, dev)
 wf = torch.zeros_like(w_ps)
 hi_p, l8_p, sc_p = T._planes(m, n, dev)
 check(lib().ribca_test_gemm_gelu_mx(ptr(z_ps), 2 * dp, ptr(w_ps), 2 * dp, m, n, dp, ptr(bias2), ptr(csum), ptr(rs), ptr(wf), ptr(hi_p), ptr(l8_p), ptr(sc_p), stream_ptr()), "gelu_mx")

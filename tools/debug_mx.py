@@ -3,7 +3,7 @@ import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
 import numpy as np, torch
 import mx_emulation as mx
-from test_gpu_kernels import ps_decode, ps_encode, rnd
+from kernel_harness import ps_decode, ps_encode, rnd
 from test_gpu_mx import _ps_halves, _planes
 from multiplexed_image_annotator_amd import _lib
 from multiplexed_image_annotator_amd._lib import check, lib, ptr, stream_ptr
