@@ -467,6 +467,38 @@ int ribca_mask_overlap(const int32_t* mask_a, const int32_t* mask_b, int32_t H, 
 int ribca_mask_compartments(const int32_t* mask_a, const int32_t* mask_b, int32_t H, int32_t W, const int32_t* a_to_cell, int32_t La, int32_t n,
                             const int32_t* b_to_obj, int32_t Lb, int32_t m, const int32_t* owner, int32_t* inner, int32_t* outer, void* stream);
 
+/* ---- where a marker sits in the cell: depth below the cell's edge, sums per depth shell (csrc/localization.hip) ---------
+ * ribca_mask_depth: mask (H, W) int32 row-major on the device, read only; depth2 (H, W) int32 is OVERWRITTEN, every byte.  With
+ * l(q) = max(mask[q], 0): a pixel p with l(p) == 0 gets depth2[p] = 0.  For a pixel p with l(p) > 0 let m be the smallest squared Euclidean
+ * distance from p to a pixel q INSIDE the image with l(q) != l(p) -- background or another cell, whichever is nearer: depth2[p] = m when such
+ * a q exists and m <= D D, else -1, "deeper than D".  Nothing outside the image is read and nothing outside it counts as a different pixel: a
+ * cell cut by the image border is measured from its VISIBLE edge only, so its pixels on the border are as deep as the rest of its outline
+ * lets them be, and a label that fills the image is -1 everywhere.  Negative pixels are background, as for ribca_expand_labels.  Integer
+ * arithmetic, no atomics: a pure function of (mask, D), the same for every launch geometry and every run.  1 <= H, W, H W < 2^31,
+ * 1 <= D <= 32; labels are any positive int32.  mask and depth2 must not overlap.  ws: ribca_mask_depth_ws_bytes(H, W, D) bytes; 0 for
+ * arguments the entry point refuses.  The piece is RESERVED: 256 bytes today, and the kernel neither reads nor writes it; a NULL or short
+ * workspace is refused all the same, as for every entry point that takes one.
+ * ribca_cell_shell_sums: image (C, H, W) fp32, mask and depth2 (H, W) int32, ids (n) int32 and bbox (n, 4) int32 on the device, as for
+ * ribca_cell_intensities: the same clipping, the same pixel set S_i in row-major order, the same empty cases.  depth2 holds values >= -1, as
+ * ribca_mask_depth writes them.  edges2 (S - 1) int32 is a HOST array, read before the launch: strictly increasing and positive,
+ * 2 <= S <= 8.  THE SHELL of a pixel: S - 1 when its depth2 is -1, else #{ j : depth2 > edges2[j] }.  All three outputs are OVERWRITTEN:
+ *     count   (n, S) int32      the pixels of S_i per shell
+ *     deepest (n) int32         -1 when a pixel of S_i has depth2 == -1, else the largest depth2 over S_i -- the squared radius of the largest
+ *                               disc centred on a pixel of the cell that holds no other pixel; 0 for a cell without a pixel
+ *     sums    (n, C, S) fp64    element e of S_i is its e-th pixel in row-major order WHATEVER its shell, and belongs to partial e mod 256.
+ *                               Partial p[k][j], k the shell, j = 0 .. 255, starts at 0.0 and adds, in increasing e, the values widened to
+ *                               fp64 of its elements whose shell is k -- elements of other shells are skipped, not added as zeros; then for
+ *                               s = 128, 64, ..., 1: p[k][j] += p[k][j+s] for j < s; the sum is p[k][0].  Every operation is rounded on
+ *                               its own
+ * For finite inputs the outputs are a pure function of the arguments, the same for every launch geometry and every run (no floating-point
+ * atomics).  1 <= C <= 64, 1 <= H, W <= 65535, H W < 2^31, 1 <= n <= 2^21; n == 0 returns 0 and touches nothing.  No workspace.
+ * Both: arguments outside the limits return a status with text (ribca_last_error) before any HIP call.  No loop of any kernel waits for
+ * another thread.  Neither entry point synchronises. */
+int64_t ribca_mask_depth_ws_bytes(int32_t H, int32_t W, int32_t D);
+int ribca_mask_depth(const int32_t* mask, int32_t H, int32_t W, int32_t D, int32_t* depth2, void* ws, int64_t ws_bytes, void* stream);
+int ribca_cell_shell_sums(const float* image, int32_t C, int32_t H, int32_t W, const int32_t* mask, const int32_t* depth2, const int32_t* ids,
+                          const int32_t* bbox, int32_t n, const int32_t* edges2, int32_t S, int32_t* count, int32_t* deepest, double* sums, void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

@@ -16,7 +16,10 @@ segmentation mask -- which cells lie within D pixels of each other -- with its e
 per-cell morphology table read off the mask -- area, axes, eccentricity, perimeter, Euler number, the share of the outline that faces other cells,
 the share of the cell inside its classifier window -- with its per-type summary and two maps per image (Annotator.cell_morphology);
 ``--intensities`` the per-cell marker intensities over each cell's own pixels -- mean, std, min, quartiles, max of every channel -- with the per-type
-summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities); ``--expand-mask D`` (1 <= D <= 32) grows every label of the mask by D pixels on the GPU
+summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities); ``--localization B`` (B one of 1, 2, 3, 4, 6, 8)
+where every marker sits in every cell -- its mean over the pixels at most B pixels below the cell's edge and over the rest, their contrast, the
+inscribed radius -- with the per-type profile over seven depth shells, the summary and one contrast map per marker and image
+(Annotator.marker_localization); ``--expand-mask D`` (1 <= D <= 32) grows every label of the mask by D pixels on the GPU
 before anything reads it -- for masks that outline nuclei -- and writes the grown mask and a per-cell expansion table, and with ``--intensities``
 the intensity tables of the nucleus (core) and of the grown ring as well (Annotator(expand_mask=D)); ``--repair-mask A`` (A >= 1) repairs the mask on
 the GPU before the expansion and before anything reads it -- the pieces of a torn label become labels of their own, pieces of fewer than A pixels are
@@ -75,6 +78,9 @@ def parse_args(argv=None):
                     help='per-cell morphology table from the mask (shape, border, Euler number, patch coverage), per-type summary and two maps per image')
     ap.add_argument('--intensities', action='store_true',
                     help="per-cell marker intensities over the cell's own mask pixels (mean, std, min, quartiles, max), per-type summary and one map per marker and image")
+    ap.add_argument('--localization', type=int, default=0,
+                    help="width in pixels (1, 2, 3, 4, 6 or 8) of the edge compartment of the marker localisation table: per cell and marker the mean "
+                         "below the cell's edge and inside, their contrast and the inscribed radius, per-type depth profile and one map per marker and image (0 = off)")
     ap.add_argument('--outlines', action='store_true',
                     help='every cell as a polygon with properties, traced on the GPU from the mask after repair and expansion: one GeoJSON file '
                          '(QuPath detections: id, area, cell type, colour, confidence) and one per-cell ring table per image')
@@ -108,6 +114,8 @@ def parse_args(argv=None):
         ap.error("--contact-distance takes 0 (off) or a reach of 1 .. 8 pixels")
     if not 0 <= args.expand_mask <= 32:
         ap.error("--expand-mask takes 0 (off) or a distance of 1 .. 32 pixels")
+    if args.localization not in (0, 1, 2, 3, 4, 6, 8):
+        ap.error("--localization takes 0 (off) or an edge band of 1, 2, 3, 4, 6 or 8 pixels")
     if not 0 <= args.repair_mask <= 2 ** 31 - 1:
         ap.error("--repair-mask takes 0 (off) or a smallest area of 1 pixel or more")
     return args
@@ -137,8 +145,8 @@ def _check_repair_mask(repair_mask):
 
 
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
-              nearest_perms=0, match=None, outlines=False, expand_mask=0, morphology=False, intensities=False, contact_distance=0,
-              contact_perms=0):
+              nearest_perms=0, match=None, outlines=False, localization=0, expand_mask=0, morphology=False, intensities=False,
+              contact_distance=0, contact_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
     carries the regions).  Two guards the reference lacks keep small images from raising inside its k-NN queries.  Its plotting
@@ -180,6 +188,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
         if expand_mask > 0:                         # the mask was grown from nuclei: the same table over the nucleus and over the grown ring
             annotator.cell_intensities(integrate=True, maps=False, compartment="core")
             annotator.cell_intensities(integrate=True, maps=False, compartment="ring")
+    if localization > 0:                            # and where in the cell they express it: rim or interior, per cell and marker (any number of cells)
+        annotator.marker_localization(band=localization, integrate=True)
     if match is not None:                           # and how a second mask of the same images -- nuclei, another tool's cells -- sits in the cells
         annotator.mask_matching(integrate=True, **match)
     if outlines:                                    # and the cells as objects a viewer can load: polygons with properties, per image
@@ -192,8 +202,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, match=None, second_mask_path=None, outlines=False, repair_mask=0, expand_mask=0, morphology=False,
-        intensities=False, contact_distance=0, contact_perms=0):
+        nearest_bands=0, nearest_perms=0, match=None, second_mask_path=None, outlines=False, localization=0, repair_mask=0, expand_mask=0,
+        morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
     _check_expand_mask(expand_mask)
@@ -215,7 +225,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
                           cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
-              outlines=outlines, match=match)
+              outlines=outlines, match=match, localization=localization)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -227,8 +237,8 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, match=None, outlines=False, repair_mask=0, expand_mask=0, morphology=False,
-              intensities=False, contact_distance=0, contact_perms=0):
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, match=None, outlines=False, localization=0, repair_mask=0, expand_mask=0,
+              morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path (and second_mask_path for ``match``)."""
     _check_expand_mask(expand_mask)
     _check_repair_mask(repair_mask)
@@ -238,7 +248,7 @@ def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, stri
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
-              outlines=outlines, match=match)
+              outlines=outlines, match=match, localization=localization)
 
 
 def main(argv=None):
@@ -250,7 +260,7 @@ def main(argv=None):
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
                   contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities,
-                  expand_mask=args.expand_mask, repair_mask=args.repair_mask, outlines=args.outlines)
+                  expand_mask=args.expand_mask, repair_mask=args.repair_mask, outlines=args.outlines, localization=args.localization)
     if args.match_masks:      # the arguments of Annotator.mask_matching; None: nothing of it is read or written
         common["match"] = dict(min_overlap=args.match_min_overlap, intensities=args.match_intensities, save_masks=args.match_save_masks)
     if args.batch_csv:

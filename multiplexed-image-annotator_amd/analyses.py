@@ -988,6 +988,104 @@ class Analyses(object):
                             "ops.cell_intensities with its copies {:.1f}, tables and drawing {:.1f} ms.".format(
                                 files[0], cells, c_img, t, empty, streamed, ops.INTENSITY_RESIDENT, kernel_ms, draw_ms))
 
+    # ---- marker localisation: rim or blob, this cell's rim or the neighbour's spill (CellProfiler's MeasureObjectIntensityDistribution) ----------
+    def marker_localization(self, band=2, integrate=True, maps=True):
+        """Where every marker sits in every cell, from the segmentation mask the run works on -- after ``repair_mask`` and ``expand_mask``.
+        ops.mask_depth (csrc/localization.hip) gives every labelled pixel its depth below the edge of its own cell, the distance to the nearest
+        pixel of the background OR of another cell, up to localization.DEPTH pixels; ops.cell_shell_sums adds every marker over the cell's
+        pixels per depth shell (localization.EDGES: seven shells) in a fixed fp64 order; localization.features, which states every formula,
+        finishes on the host: the mean over the EDGE compartment (depth <= ``band`` pixels, ``band`` one of localization.EDGES) and over the
+        INNER compartment (the rest), ``contrast = (edge - inner) / (edge + inner)`` -- near +1 for a membrane marker, near -1 for a nuclear
+        one, NaN for a cell too small to have both compartments -- and ``inradius``, the radius of the largest disc inside the cell.  A cell cut
+        by the image border is measured from its visible edge only.  Per image it writes ``{batch_id}_localization_{image number}.csv``
+        (localization.cells_csv, one line per cell in id order) and, with ``maps``, one ``{batch_id}_localization_{marker}_{image number}.png``
+        per marker (intensities.file_slug), the contrast painted through ops.colorize with the diverging table on +- 1
+        (localization.colour_index; NaN cells at index 0, background 0).  Per group (the batch with ``integrate``, else every image), with stem
+        = ``{batch_id}_integrated_localization`` or ``{batch_id}_localization`` and the image number at the end of each name:
+        ``{stem}_profile.csv`` (localization.profile_csv: pixels and pooled mean per cell type, marker and shell), ``{stem}_summary.csv``
+        (localization.summary_csv: n, cells with a NaN contrast, mean and median contrast per cell type and marker) and ``{stem}.csv`` /
+        ``.png``, the median contrast per type and marker on +- 1 (for a single image ``{batch_id}_localization_medians_{image number}``, since
+        ``{batch_id}_localization_{image number}.csv`` is its cell table).  Keeps the per-cell contrasts as ``self.localization_contrast``, one
+        (n, C) array per local image, and records ``localization_stats``, one record per group written by this rank; its ``kernel_ms`` is the
+        host's clock around ops.mask_depth and ops.cell_shell_sums with the copy of the outputs back (tools/time_consumers.py --localization
+        times the kernels alone).  Multi-rank runs as cell_intensities.  A wrong ``band`` raises ValueError before anything is written or
+        set."""
+        import time
+        from . import intensities, localization
+        self._check_annotated("No annotations")
+        band = localization.check_band(band)
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        self.localization_stats = []
+        kept = self.localization_contrast = []
+        if not self._computes_here():
+            return None
+        n_local = len(self.annotations)
+        lut = colors.diverging_table()
+        e2 = localization.edges2()
+        shells = len(e2) + 1
+        c_img = int(self.preprocessor.images_dev[0].shape[0]) if n_local else len(self.channel_parser.markers)
+        markers = self._marker_names(c_img)
+        width = 4 + shells + c_img * shells      # image number, cell id, cell type, deepest, then the counts and the sums: a row of the exchange
+        for members in _groups(integrate, n_local):
+            rows, image_files, kernel_ms, draw_ms = [np.zeros((0, width))], [], 0.0, 0.0
+            for i in members:
+                ids = np.asarray(self.preprocessor.cell_ids[i], dtype=np.int64)
+                mask, image = self.preprocessor.masks_dev[i], self.preprocessor.images_dev[i]
+                n = len(ids)
+                if int(image.shape[0]) != c_img:
+                    raise ValueError(f"image {self._image_number(i)} has {int(image.shape[0])} channels, the batch {c_img}")
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                depth2 = ops.mask_depth(mask, localization.DEPTH)
+                count, deepest, sums = ops.cell_shell_sums(image, mask, depth2, self.preprocessor.cell_ids_dev[i], self.preprocessor.cell_bbox_dev[i], e2)
+                kernel_ms += (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                feat = localization.features(count, deepest, sums, band)
+                kept.append(feat["contrast"].copy())
+                number = self._image_number(i)
+                image_files.append(f"{self.batch_id}_localization_{number}.csv")
+                self._write_text(image_files[-1], localization.cells_csv(ids, types, names, markers, feat))
+                if maps:
+                    for c, marker in enumerate(markers):
+                        image_files.append(f"{self.batch_id}_localization_{intensities.file_slug(marker)}_{number}.png")
+                        idx = localization.colour_index(feat["contrast"][:, c])
+                        self._paint_map(i, lut[idx], idx, image_files[-1])
+                rows.append(np.concatenate([np.full((n, 1), float(number)), ids.reshape(n, 1).astype(np.float64), types.reshape(n, 1).astype(np.float64),
+                                            deepest.reshape(n, 1).astype(np.float64), count.reshape(n, shells).astype(np.float64),
+                                            sums.reshape(n, c_img * shells)], axis=1))
+                draw_ms += (time.perf_counter() - t0) * 1e3
+            table = np.concatenate(rows, axis=0)
+            if integrate and self.tile_mode:
+                table, _ = self._gather_rows(table)
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            cells = len(table)
+            types = table[:, 2].astype(np.int64)
+            deepest, count = table[:, 3].astype(np.int64), table[:, 4:4 + shells].astype(np.int64)
+            sums = table[:, 4 + shells:].reshape(cells, c_img, shells)
+            feat = localization.features(count, deepest, sums, band)
+            stem, tail = self._group_stem("localization", integrate, members)
+            mid = "" if integrate else "_medians"      # {batch_id}_localization_{image number}.csv is the image's cell table
+            files = [stem + "_profile" + tail + ".csv", stem + "_summary" + tail + ".csv", stem + mid + tail + ".csv"]
+            self._write_text(files[0], localization.profile_csv(names, markers, *localization.profile(types, t, count, sums)))
+            summary = localization.summary(types, t, feat["contrast"])
+            self._write_text(files[1], localization.summary_csv(names, markers, summary))
+            self._write_text(files[2], localization.matrix_csv(names, markers, summary[:, :, 3]))
+            fig = self._write_table_figure(stem + mid + tail, summary[:, :, 3], -localization.LIMIT, localization.LIMIT, row_names=names, col_names=markers)
+            files.append(fig["file"])
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            deeper = int((deepest == -1).sum())
+            undefined = int(np.isnan(feat["contrast"]).all(axis=1).sum()) if c_img else 0
+            rec = {"file": files[0], "files": files, "image_files": image_files, "figure": {"file": fig["file"], "limit": localization.LIMIT, "rect": fig["rect"]},
+                   "n": cells, "C": c_img, "T": t, "band": band, "deeper": deeper, "undefined": undefined, "kernel_ms": kernel_ms, "draw_ms": draw_ms}
+            self.localization_stats.append(rec)
+            self.logger.log("Marker localization {}: {} cells, {} markers, {} cell types, edge band {} px; {} cells deeper than {} px, {} without a "
+                            "contrast; ops.mask_depth and ops.cell_shell_sums with their copies {:.1f}, tables and drawing {:.1f} ms.".format(
+                                files[0], cells, c_img, t, band, deeper, localization.DEPTH, undefined, kernel_ms, draw_ms))
+
     # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
     def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
         """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as

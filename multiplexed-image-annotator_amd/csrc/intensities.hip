@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/ribca_hip.h"
+#include "ribca_cellbox.h"
 #include "ribca_common.h"
 #include "ribca_status.h"
 
@@ -72,17 +73,8 @@ struct Shared {
 };
 static_assert(sizeof(Shared) <= 64 * 1024, "LDS of cell_intensities");
 
-// rank of this thread's flagged pixel among the chunk's flagged pixels, and their number m; one barrier, wave_tot alternates by parity
-__device__ __forceinline__ int chunk_rank(Shared& sh, bool flag, int parity, int& m) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(flag);
-  if (lane == 0) sh.wave_tot[parity][wave] = __popcll(b);
-  __syncthreads();
-  const int t0 = sh.wave_tot[parity][0], t1 = sh.wave_tot[parity][1], t2 = sh.wave_tot[parity][2], t3 = sh.wave_tot[parity][3];
-  m = t0 + t1 + t2 + t3;
-  const int before = wave == 0 ? 0 : wave == 1 ? t0 : wave == 2 ? t0 + t1 : t0 + t1 + t2;
-  return before + __popcll(b & ((1ull << lane) - 1ull));
-}
+// the chunk's ballot scan of ribca_cellbox.h on this kernel's LDS
+__device__ __forceinline__ int chunk_rank(Shared& sh, bool flag, int parity, int& m) { return ribca::chunk_rank(sh.wave_tot, flag, parity, m); }
 
 // the stated tree over the 256 partials: s = 128, 64 through LDS, s = 32 .. 1 in wave 0; every thread returns p_0
 __device__ __forceinline__ double tree(Shared& sh, double p) {
@@ -96,20 +88,6 @@ __device__ __forceinline__ double tree(Shared& sh, double p) {
   }
   __syncthreads();
   return sh.result;
-}
-
-// the box of a cell, clipped; pixel e of it in row-major order is (r0 + e / bw, c0 + e % bw); total = 0: no pixel (ids[i] <= 0 or an empty box)
-struct Box {
-  int r0, c0, bw;
-  unsigned total;
-};
-
-__device__ __forceinline__ Box clipped_box(const int32_t* __restrict__ b, int32_t id, int H, int W) {
-  const int rmin = max(b[0], 0), rmax = min(b[1], H - 1), cmin = max(b[2], 0), cmax = min(b[3], W - 1);
-  Box box;
-  box.r0 = rmin, box.c0 = cmin, box.bw = cmax - cmin + 1;
-  box.total = id > 0 && rmin <= rmax && cmin <= cmax ? (unsigned)(rmax - rmin + 1) * (unsigned)box.bw : 0u;      // <= H W < 2^31
-  return box;
 }
 
 // rank r of the two that bracket quantile k of a cell of a pixels (slot = 2 k for lo, 2 k + 1 for hi)

@@ -878,6 +878,74 @@ def cell_intensities(image: torch.Tensor, mask: torch.Tensor, ids, bbox, q_num: 
     return area.cpu().numpy(), sums.cpu().numpy(), order.cpu().numpy()
 
 
+DEPTH_MAX_DISTANCE = 32           # csrc/localization.hip LO_D_MAX: the largest halo of a pixel tile
+DEPTH_TILE = 32                   # csrc/localization.hip LO_TILE
+SHELLS_MAX = 8                    # csrc/localization.hip LO_S_MAX: the accumulators a partial's owner keeps in registers
+
+
+def mask_depth_ws_bytes(h: int, w: int, distance: int) -> int:
+    return int(lib().ribca_mask_depth_ws_bytes(int(h), int(w), int(distance)))
+
+
+def mask_depth(mask: torch.Tensor, distance: int, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The depth of every labelled pixel of an (H, W) int32 device mask below the edge of its own cell: the squared Euclidean distance to the
+    nearest pixel inside the image that carries another value -- background or another cell --, -1 where that is more than ``distance`` pixels
+    away, 0 on the background (<= 0).  A cell cut by the image border is measured from its visible edge only (include/ribca_hip.h states the
+    contract).  Returns a new (H, W) int32 device tensor.  Does not synchronise."""
+    if not torch.is_tensor(mask) or mask.dtype != torch.int32 or mask.dim() != 2 or not mask.is_cuda:
+        raise ValueError("mask_depth takes an (H, W) int32 device mask")
+    if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)) or not 1 <= int(distance) <= DEPTH_MAX_DISTANCE:
+        raise ValueError(f"distance must be an integer from 1 to {DEPTH_MAX_DISTANCE} pixels, got {distance!r}")
+    d = int(distance)
+    mask = mask.contiguous()
+    h, w = mask.shape
+    depth2 = torch.empty_like(mask)
+    ws = _ws(ws, mask_depth_ws_bytes(h, w, d), mask.device, "mask_depth")
+    check(lib().ribca_mask_depth(ptr(mask), h, w, d, ptr(depth2), ptr(ws), ws.numel(), stream_ptr()), "ribca_mask_depth")
+    return depth2
+
+
+def cell_shell_sums(image: torch.Tensor, mask: torch.Tensor, depth2: torch.Tensor, ids, bbox, edges2: Sequence[int],
+                    out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """Per cell the pixels, and per cell and channel the exact fp64 sum, of every depth shell: ``image`` (C, H, W) fp32, ``mask`` and ``depth2``
+    (H, W) int32 on the device (``depth2`` from ``mask_depth``), ``ids`` (n) and ``bbox`` (n, 4) as for ``cell_intensities``, ``edges2`` the
+    S - 1 strictly increasing positive squared shell edges (2 <= S <= SHELLS_MAX).  A pixel is in shell #{j : depth2 > edges2[j]}, in the last
+    one when its depth2 is -1.  Returns host arrays ``count`` (n, S) int32, ``deepest`` (n) int32 -- the largest depth2 of the cell, -1 when
+    one of its pixels is -1, 0 for a cell without a pixel -- and ``sums`` (n, C, S) fp64 (include/ribca_hip.h states the summation order;
+    localization.features turns them into the table).  ``out``: device tensors to fill instead (returned as they are, no copy back, no
+    synchronise)."""
+    assert image.is_cuda and image.dtype == torch.float32 and image.dim() == 3
+    assert mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2 and tuple(mask.shape) == tuple(image.shape[1:])
+    assert depth2.is_cuda and depth2.dtype == torch.int32 and tuple(depth2.shape) == tuple(mask.shape)
+    dev = image.device
+    e2 = np.ascontiguousarray(np.asarray(edges2, dtype=np.int32).reshape(-1))
+    s = len(e2) + 1
+    c, h, w = (int(v) for v in image.shape)
+    ids_d = ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1)))
+    bbox_d = bbox if torch.is_tensor(bbox) else torch.from_numpy(np.ascontiguousarray(np.asarray(bbox, dtype=np.int32).reshape(-1, 4)))
+    ids_d = ids_d.to(device=dev, dtype=torch.int32).contiguous()
+    bbox_d = bbox_d.to(device=dev, dtype=torch.int32).contiguous()
+    n = ids_d.numel()
+    if tuple(bbox_d.shape) != (n, 4):
+        raise ValueError(f"cell_shell_sums takes one box rmin, rmax, cmin, cmax per cell, got {tuple(bbox_d.shape)} for {n} cells")
+    if out is None:
+        count = torch.empty((n, s), dtype=torch.int32, device=dev)
+        deepest = torch.empty((n,), dtype=torch.int32, device=dev)
+        sums = torch.empty((n, c, s), dtype=torch.float64, device=dev)
+    else:
+        count, deepest, sums = out
+        assert count.is_contiguous() and deepest.is_contiguous() and sums.is_contiguous()
+        assert count.dtype == torch.int32 and deepest.dtype == torch.int32 and sums.dtype == torch.float64
+        assert count.numel() == n * s and deepest.numel() == n and sums.numel() == n * c * s
+    if n:
+        check(lib().ribca_cell_shell_sums(ptr(image.contiguous()), c, h, w, ptr(mask.contiguous()), ptr(depth2.contiguous()), ptr(ids_d), ptr(bbox_d), n,
+                                          e2.ctypes.data_as(ctypes.c_void_p), s, ptr(count), ptr(deepest), ptr(sums), stream_ptr()),
+              "ribca_cell_shell_sums")
+    if out is not None:
+        return out
+    return count.cpu().numpy(), deepest.cpu().numpy(), sums.cpu().numpy()
+
+
 AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
 AUTOCORR_MAX_NEIGHBOURS = 31
 

@@ -30,7 +30,10 @@ host clock, and scipy.ndimage.label of the same mask on the host (``--repair``: 
 on the host clock, and the restatement of tests/outlines_numpy.py on a crop, scaled by boundary edges (``--outlines``: this section alone); and the
 matching of a second mask (csrc/overlap.hip): ribca_mask_overlap and ribca_mask_compartments against a shifted copy of the same mask with labels
 dropped and merged, device events, beside ribca_contact_table at d = 1 in the same process, the whole ops.overlap_pairs and the rules of
-matching.py on the host clock, and np.unique over the 64-bit pair keys of the same two masks on the host (``--matching``: this section alone)."""
+matching.py on the host clock, and np.unique over the 64-bit pair keys of the same two masks on the host (``--matching``: this section alone); and the
+marker localisation (csrc/localization.hip): ribca_mask_depth at D = 8 and 32 and ribca_cell_shell_sums on the 15-channel image of the same tile,
+device events, the whole ops calls and the host features on the host clock, scipy's distance_transform_edt of the foreground on the host, and the
+restatement of tests/localization_numpy.py on a crop, scaled by the area (``--localization``: this section alone)."""
 import os
 import sys
 import time
@@ -599,6 +602,110 @@ def time_matching():
     print(f"numpy restatement (host): both tables applied and np.unique over {int(both.sum())} 64-bit pair keys {host_ms:.0f} ms; equal to the GPU pairs and areas: {same}")
 
 
+# ---- marker localisation (csrc/localization.hip): the depth of every labelled pixel below its cell's edge, then the marker sums per depth shell -------
+def time_localization():
+    """mask, image, ids, boxes, outputs and workspace on the device before the clock starts: each entry point between two device events, median of
+    five calls after a warm-up -- ribca_mask_depth at D = 8 and D = 32, ribca_cell_shell_sums on the 15-channel image at the product's seven
+    shells; then the whole ops calls with their copies and the host features on the host clock, scipy's exact distance transform of the
+    foreground of the same mask (the yardstick of the expansion: it measures to the background only, not to the neighbour), and the numpy
+    restatement on a crop, checked against the GPU on the same crop"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import intensities_numpy as IN
+    import localization_numpy as LN
+    from multiplexed_image_annotator_amd import localization
+    from multiplexed_image_annotator_amd._lib import lib, ptr, stream_ptr
+    h, w = mask.shape
+    c = 15
+
+    def events(call):
+        call()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            call()
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop))
+        return f"median {sorted(times)[2]:.3f} ms, min {min(times):.3f}, max {max(times):.3f} of 5 (device events)"
+
+    depth2 = torch.empty_like(mask)
+    labelled = int((mask > 0).sum())
+    for d in (8, 32):
+        ws = torch.empty(max(ops.mask_depth_ws_bytes(h, w, d), 1), dtype=torch.uint8, device=dev)
+        took = events(lambda: _lib.check(lib().ribca_mask_depth(ptr(mask), h, w, d, ptr(depth2), ptr(ws), ws.numel(), stream_ptr()), "depth"))
+        print(f"mask depth, D = {d}: {took} for {n} cells, {h}x{w}; {int((depth2 == -1).sum())} of {labelled} labelled pixels deeper than D; read + write of "
+              f"{2 * h * w * 4 / 1e9:.2f} GB at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: {1e3 * 2 * h * w * 4 / HBM_BYTES_PER_S:.3f} ms")
+    depth2 = ops.mask_depth(mask, localization.DEPTH)
+    _, raw = synth.make_mask_and_image(h, w, 100000, c, synth.SEED_BASE + 3, device=dev)
+    image = (raw.to(torch.float32) / 32767.5 - 1.0).contiguous()      # the normalised range, with the background's ties
+    del raw
+    ids_d = torch.from_numpy(np.asarray(ids, dtype=np.int32)).to(dev)
+    bbox_d = torch.from_numpy(np.ascontiguousarray(tab[:, :4], dtype=np.int32)).to(dev)
+    e2 = localization.edges2()
+    shells = len(e2) + 1
+    out = (torch.empty((n, shells), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
+           torch.empty((n, c, shells), dtype=torch.float64, device=dev))
+    took = events(lambda: ops.cell_shell_sums(image, mask, depth2, ids_d, bbox_d, e2, out=out))
+    count = out[0].cpu().numpy()
+    print(f"cell shell sums, S = {shells}: {took} for {n} cells, {c} channels, {h}x{w}; one read of the {image.numel() * 4 / 1e9:.2f} GB image at "
+          f"{HBM_BYTES_PER_S / 1e12:.2f} TB/s: {1e3 * image.numel() * 4 / HBM_BYTES_PER_S:.2f} ms; counts add up to the label table's areas: "
+          f"{np.array_equal(count.sum(axis=1), tab[:, 6])}; pixels per shell {count.sum(axis=0).tolist()}; cells deeper than {localization.DEPTH} px: "
+          f"{int((out[1] == -1).sum())}")
+    for name, fn in ((f"ops.mask_depth, D = {localization.DEPTH} (scratch allocated, depth2 left on the device)", lambda: ops.mask_depth(mask, localization.DEPTH)),
+                     ("ops.cell_shell_sums with the copy of its outputs to the host", lambda: ops.cell_shell_sums(image, mask, depth2, ids_d, bbox_d, e2))):
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            got = fn()
+            torch.cuda.synchronize()
+            times.append(1e3 * (time.perf_counter() - t0))
+        print(f"{name}: median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} of 5 (host clock)")
+    t0 = time.perf_counter()
+    feat = localization.features(*got, 2)
+    print(f"localization.features on the host, band 2, {n} cells x {c} channels: {1e3 * (time.perf_counter() - t0):.0f} ms; cells without a contrast: "
+          f"{int(np.isnan(feat['contrast']).all(axis=1).sum())}")
+    host = mask.cpu().numpy()
+    try:
+        from scipy import ndimage
+        t0 = time.perf_counter()
+        dist = ndimage.distance_transform_edt(host > 0)
+        host_ms = 1e3 * (time.perf_counter() - t0)
+        near = (host > 0) & (dist <= localization.DEPTH)
+        got2 = depth2.cpu().numpy()
+        # scipy measures to the background alone: where cells touch, the kernel's depth is the smaller
+        print(f"scipy distance_transform_edt of the foreground, {h}x{w} (host): {host_ms:.0f} ms; within {localization.DEPTH} px of the background the "
+              f"kernel's depth is never larger: {bool((got2[near] <= np.rint(dist[near] ** 2)).all())}, and smaller, next to another cell, on "
+              f"{int((got2[near] < np.rint(dist[near] ** 2)).sum())} of {int(near.sum())} pixels")
+    except ImportError:
+        print("scipy is not installed: no distance_transform_edt yardstick")
+    side = 1024
+    crop_mask = np.ascontiguousarray(host[:side, :side])
+    crop_image = np.ascontiguousarray(image[:, :side, :side].cpu().numpy())
+    crop_ids = np.unique(crop_mask[crop_mask > 0]).astype(np.int32)
+    crop_box = IN.boxes_of_all(crop_mask, crop_ids)
+    t0 = time.perf_counter()
+    want_depth = LN.depth(crop_mask, localization.DEPTH)
+    depth_ms = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    want = LN.shell_sums(crop_image, crop_mask, want_depth, crop_ids, crop_box, e2)
+    sums_ms = 1e3 * (time.perf_counter() - t0)
+    crop_dev = torch.from_numpy(crop_mask).to(dev)
+    g_depth = ops.mask_depth(crop_dev, localization.DEPTH)
+    g = ops.cell_shell_sums(torch.from_numpy(crop_image).to(dev), crop_dev, g_depth, crop_ids, crop_box, e2)
+    same = (np.array_equal(g_depth.cpu().numpy(), want_depth) and np.array_equal(g[0], want[0]) and np.array_equal(g[1], want[1])
+            and np.array_equal(g[2].view(np.int64), want[2].view(np.int64)))
+    scale = (h * w) / (side * side)
+    print(f"numpy restatement, top-left {side}x{side} crop, {len(crop_ids)} cells (host): depth {depth_ms:.0f} ms, shell sums {sums_ms:.0f} ms -> "
+          f"{depth_ms * scale / 1e3:.1f} s and {sums_ms * scale / 1e3:.1f} s scaled by area to {h}x{w}; equal to the GPU outputs of the same crop, byte for byte: {same}")
+
+
+if "--localization" in sys.argv:      # this section alone
+    time_localization()
+    sys.exit(0)
 if "--matching" in sys.argv:      # this section alone
     time_matching()
     sys.exit(0)
