@@ -499,6 +499,34 @@ int ribca_mask_depth(const int32_t* mask, int32_t H, int32_t W, int32_t D, int32
 int ribca_cell_shell_sums(const float* image, int32_t C, int32_t H, int32_t W, const int32_t* mask, const int32_t* depth2, const int32_t* ids,
                           const int32_t* bbox, int32_t n, const int32_t* edges2, int32_t S, int32_t* count, int32_t* deepest, double* sums, void* stream);
 
+/* ---- marker colocalisation per cell: sums, centred cross products, gated sums, counts above both gates (csrc/colocalization.hip, DESIGN.md
+ * section 27) -----------------------------------------------------------------------------------------------------------------------------------
+ * image (C, H, W) fp32, mask (H, W) int32, ids (n) int32 and bbox (n, 4) int32 on the device, exactly as for ribca_cell_intensities: the same
+ * clipping, the same pixel set S_i -- the pixels of the clipped box with mask == ids[i] -- in row-major order, the same empty cases.  chan (K)
+ * int32 and thr (K) fp32 are HOST arrays, read before the launch: chan holds K DISTINCT channel indices in [0, C), 2 <= K <= 32, in any order;
+ * thr holds one finite gate per selected channel, on the image's own scale.  With a = |S_i|, v_k[e] the value of channel chan[k] at the e-th
+ * pixel of S_i widened to fp64, g_k[e] the fp32 comparison value > thr[k] (STRICT; false for a NaN) and P = K (K + 1) / 2 the pairs (k, l),
+ * k <= l, in the order (0,0), (0,1) .. (0,K-1), (1,1) ..., all five outputs are OVERWRITTEN:
+ *     area  (n) int32        a
+ *     both  (n, P) int32     #{ e : g_k[e] and g_l[e] }; the diagonal counts the pixels above the channel's own gate
+ *     sums  (n, K) fp64      THE TREE over v_k: partial p_j, j = 0 .. 255, starts at 0.0 and adds v_k[j], v_k[j+256], ... in that order; then
+ *                            for s = 128, 64, ..., 1: p_j += p_{j+s} for j < s; the sum is p_0.  m_k = sums / a
+ *     cross (n, P) fp64      the same tree over (v_k[e] - m_k) * (v_l[e] - m_l); every operation is rounded on its own (no fused multiply-add)
+ *     gated (n, K, K) fp64   gated[k][l] is the same tree over v_k[e] restricted to the elements with g_l[e]: element e belongs to partial
+ *                            e mod 256 WHATEVER its gates, and an element whose gate is closed is skipped, not added as a zero -- the rule
+ *                            of ribca_cell_shell_sums
+ * Two consequences.  sums[i][k] and cross[i][(k, k)] equal the sum and the ssd ribca_cell_intensities gives channel chan[k], bit for bit.  A
+ * channel that is constant over the cell gives cross of exactly 0.0 in its row and column: the sum of a equal fp32 values is exact in fp64
+ * (a < 2^31, 24-bit significands), and so is its quotient by a, so every deviation is 0.0.
+ * a = 0 gives zeros everywhere.  For finite inputs the outputs are a pure function of the arguments, the same for every launch geometry and
+ * every run (no floating-point atomics; the counts are integer adds); for non-finite values only area and both are specified.
+ * 1 <= C <= 64, 2 <= K <= 32, 1 <= H, W <= 65535, H W < 2^31, 1 <= n <= 2^21; n == 0 returns 0 and touches nothing.  A NULL buffer, sizes out
+ * of range, a repeated or out-of-range chan and a non-finite thr are refused with a status that names the entry point (ribca_last_error)
+ * before any HIP call.  No workspace.  No loop of the kernel waits for another thread.  The entry point does not synchronise. */
+int ribca_cell_coloc(const float* image, int32_t C, int32_t H, int32_t W, const int32_t* mask, const int32_t* ids, const int32_t* bbox, int32_t n,
+                     const int32_t* chan, const float* thr, int32_t K, int32_t* area, int32_t* both, double* sums, double* cross, double* gated,
+                     void* stream);
+
 /* Neighbourhood compositions of spatial_methods.tissue_region_partition (spatial_methods.py:133-180): sizes (DEVICE array, n_sizes <= 8,
  * strictly increasing, max <= 255; the reference uses 10,20,30,50,75,100,150,200; n_types <= 254) -> counts (n_cells, n_sizes, n_types) uint16 =
  * number of cells of each type among the nearest sizes[l] OTHER cells (fp64 distances, ties towards the lower index).  The

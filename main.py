@@ -19,7 +19,10 @@ the share of the cell inside its classifier window -- with its per-type summary 
 summary, the standardised type medians and one map per marker and image (Annotator.cell_intensities); ``--localization B`` (B one of 1, 2, 3, 4, 6, 8)
 where every marker sits in every cell -- its mean over the pixels at most B pixels below the cell's edge and over the rest, their contrast, the
 inscribed radius -- with the per-type profile over seven depth shells, the summary and one contrast map per marker and image
-(Annotator.marker_localization); ``--expand-mask D`` (1 <= D <= 32) grows every label of the mask by D pixels on the GPU
+(Annotator.marker_localization); ``--colocalization`` whether two markers sit on the same pixels of a cell -- Pearson's r of every marker
+pair per cell, and for the pairs named with ``--coloc-pairs A:B,...`` the Manders overlap and fractions, the share of the cell above both gates
+(``--coloc-threshold T``) and an r map per image -- over the markers ``--coloc-markers A,B,...`` (default: all, at most 32), with the per-type
+summary and the matrices of the median r (Annotator.marker_colocalization); ``--expand-mask D`` (1 <= D <= 32) grows every label of the mask by D pixels on the GPU
 before anything reads it -- for masks that outline nuclei -- and writes the grown mask and a per-cell expansion table, and with ``--intensities``
 the intensity tables of the nucleus (core) and of the grown ring as well (Annotator(expand_mask=D)); ``--repair-mask A`` (A >= 1) repairs the mask on
 the GPU before the expansion and before anything reads it -- the pieces of a torn label become labels of their own, pieces of fewer than A pixels are
@@ -81,6 +84,16 @@ def parse_args(argv=None):
     ap.add_argument('--localization', type=int, default=0,
                     help="width in pixels (1, 2, 3, 4, 6 or 8) of the edge compartment of the marker localisation table: per cell and marker the mean "
                          "below the cell's edge and inside, their contrast and the inscribed radius, per-type depth profile and one map per marker and image (0 = off)")
+    ap.add_argument('--colocalization', action='store_true',
+                    help="per-cell marker colocalisation over the cell's own mask pixels: Pearson's r of every marker pair, per-type summary and "
+                         "the matrices of the median r; the other --coloc-* flags are read only with it")
+    ap.add_argument('--coloc-markers', type=str, default=None,
+                    help='comma-separated names of the 2 .. 32 markers to correlate (default: every marker of the list, at most 32)')
+    ap.add_argument('--coloc-pairs', type=str, default=None,
+                    help='comma-separated pairs A:B of those markers that also get the full statistics (r, Manders overlap, M1, M2, pixels above '
+                         'both gates, Jaccard) and an r map per image')
+    ap.add_argument('--coloc-threshold', type=float, default=0.15,
+                    help='the gate of the Manders fractions on the normalised intensity scale, 0 <= T < 1 (0.15 = 15 %%)')
     ap.add_argument('--outlines', action='store_true',
                     help='every cell as a polygon with properties, traced on the GPU from the mask after repair and expansion: one GeoJSON file '
                          '(QuPath detections: id, area, cell type, colour, confidence) and one per-cell ring table per image')
@@ -118,7 +131,32 @@ def parse_args(argv=None):
         ap.error("--localization takes 0 (off) or an edge band of 1, 2, 3, 4, 6 or 8 pixels")
     if not 0 <= args.repair_mask <= 2 ** 31 - 1:
         ap.error("--repair-mask takes 0 (off) or a smallest area of 1 pixel or more")
+    args.coloc = None      # the arguments of Annotator.marker_colocalization; None: nothing of it is read or written
+    if args.colocalization:
+        try:
+            args.coloc = _coloc_arguments(args.marker_list_path, args.coloc_markers, args.coloc_pairs, args.coloc_threshold)
+        except ValueError as e:
+            ap.error(str(e))
     return args
+
+
+def _coloc_arguments(marker_list_path, markers, pairs, threshold):
+    """the keyword arguments of Annotator.marker_colocalization from the --coloc-* flags; ValueError for a threshold outside 0 <= T < 1, a
+    marker the list does not hold (or holds twice, or named twice), fewer than 2 or more than 32 markers, a malformed or repeated pair"""
+    import numpy as np
+    from multiplexed_image_annotator_amd import colocalization
+    if not 0.0 <= threshold < 1.0:
+        raise ValueError("--coloc-threshold takes a gate T with 0 <= T < 1")
+    listed = [str(m) for m in np.atleast_1d(np.loadtxt(marker_list_path, delimiter=',', dtype=str))]
+    chosen = listed if markers is None else [m for m in markers.split(",")]
+    for m in chosen:
+        if listed.count(m) != 1 or chosen.count(m) != 1:
+            raise ValueError(f"--coloc-markers: {m!r} is not one marker of {marker_list_path}, named once")
+    if not 2 <= len(chosen) <= colocalization.MAX_MARKERS:
+        raise ValueError(f"--colocalization correlates 2 to {colocalization.MAX_MARKERS} markers, got {len(chosen)}: select some with --coloc-markers")
+    named = None if pairs is None else pairs.split(",")
+    colocalization.parse_pairs(named, chosen)
+    return dict(markers=None if markers is None else chosen, pairs=named, threshold=threshold)
 
 
 def _setup():
@@ -145,7 +183,7 @@ def _check_repair_mask(repair_mask):
 
 
 def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0, nearest_bands=0,
-              nearest_perms=0, match=None, outlines=False, localization=0, expand_mask=0, morphology=False, intensities=False,
+              nearest_perms=0, match=None, outlines=False, localization=0, coloc=None, expand_mask=0, morphology=False, intensities=False,
               contact_distance=0, contact_perms=0):
     """The call sequence of reference main.py:19-28 / 43-52: the CSV is exported ONCE, before the tissue-region analysis, so its
     "Tissue Region" column reads None exactly as the reference's does (RIBCA_EXPORT_REGIONS=1 opts in to a second export that
@@ -190,6 +228,8 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
             annotator.cell_intensities(integrate=True, maps=False, compartment="ring")
     if localization > 0:                            # and where in the cell they express it: rim or interior, per cell and marker (any number of cells)
         annotator.marker_localization(band=localization, integrate=True)
+    if coloc is not None:                           # and whether two markers share the pixels of a cell: double positive, doublet or spill (any number of cells)
+        annotator.marker_colocalization(integrate=True, **coloc)
     if match is not None:                           # and how a second mask of the same images -- nuclei, another tool's cells -- sits in the cells
         annotator.mask_matching(integrate=True, **match)
     if outlines:                                    # and the cells as objects a viewer can load: polygons with properties, per image
@@ -202,7 +242,7 @@ def _pipeline(annotator, bs, n_regions, enrichment_perms=0, cooccurrence_bands=0
 
 def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
         confidence, cell_size, cell_type_confidence, n_jobs, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0, local_autocorr_perms=0,
-        nearest_bands=0, nearest_perms=0, match=None, second_mask_path=None, outlines=False, localization=0, repair_mask=0, expand_mask=0,
+        nearest_bands=0, nearest_perms=0, match=None, second_mask_path=None, outlines=False, localization=0, coloc=None, repair_mask=0, expand_mask=0,
         morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:9-36: one image + mask -> images.csv -> annotate; returns (intensity_dict, names) as the reference does."""
     import numpy as np
@@ -225,7 +265,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
                           cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
-              outlines=outlines, match=match, localization=localization)
+              outlines=outlines, match=match, localization=localization, coloc=coloc)
     intensity_dict = {}
     full = annotator.preprocessor.intensity_full[0]
     for i in range(len(full)):
@@ -237,7 +277,7 @@ def run(marker_list_path, image_path, mask_path, device, main_dir, batch_id, bs,
 
 def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, strict, infer, min_cells, n_regions, normalize, blur, amax,
               confidence, cell_size, cell_type_confidence, n_jobs=0, enrichment_perms=0, cooccurrence_bands=0, autocorr_perms=0,
-              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, match=None, outlines=False, localization=0, repair_mask=0, expand_mask=0,
+              local_autocorr_perms=0, nearest_bands=0, nearest_perms=0, match=None, outlines=False, localization=0, coloc=None, repair_mask=0, expand_mask=0,
               morphology=False, intensities=False, contact_distance=0, contact_perms=0):
     """reference main.py:39-52: ``image_path`` is a CSV with columns image_path,mask_path (and second_mask_path for ``match``)."""
     _check_expand_mask(expand_mask)
@@ -248,7 +288,7 @@ def batch_run(marker_list_path, image_path, device, main_dir, batch_id, bs, stri
                           confidence, cell_size, cell_type_confidence, n_jobs=n_jobs, expand_mask=expand_mask, repair_mask=repair_mask)
     _pipeline(annotator, bs, n_regions, enrichment_perms, cooccurrence_bands, autocorr_perms, local_autocorr_perms, nearest_bands, nearest_perms,
               expand_mask=expand_mask, morphology=morphology, intensities=intensities, contact_distance=contact_distance, contact_perms=contact_perms,
-              outlines=outlines, match=match, localization=localization)
+              outlines=outlines, match=match, localization=localization, coloc=coloc)
 
 
 def main(argv=None):
@@ -260,7 +300,8 @@ def main(argv=None):
                   cooccurrence_bands=args.cooccurrence_bands, autocorr_perms=args.autocorr_perms,
                   local_autocorr_perms=args.local_autocorr_perms, nearest_bands=args.nearest_bands, nearest_perms=args.nearest_perms,
                   contact_distance=args.contact_distance, contact_perms=args.contact_perms, morphology=args.morphology, intensities=args.intensities,
-                  expand_mask=args.expand_mask, repair_mask=args.repair_mask, outlines=args.outlines, localization=args.localization)
+                  expand_mask=args.expand_mask, repair_mask=args.repair_mask, outlines=args.outlines, localization=args.localization,
+                  coloc=args.coloc)
     if args.match_masks:      # the arguments of Annotator.mask_matching; None: nothing of it is read or written
         common["match"] = dict(min_overlap=args.match_min_overlap, intensities=args.match_intensities, save_masks=args.match_save_masks)
     if args.batch_csv:

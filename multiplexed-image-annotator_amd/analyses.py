@@ -1086,6 +1086,128 @@ class Analyses(object):
                             "contrast; ops.mask_depth and ops.cell_shell_sums with their copies {:.1f}, tables and drawing {:.1f} ms.".format(
                                 files[0], cells, c_img, t, band, deeper, localization.DEPTH, undefined, kernel_ms, draw_ms))
 
+    # ---- marker colocalisation: do two markers sit on the same pixels of a cell (CellProfiler's MeasureColocalization) ----------------------------
+    def marker_colocalization(self, markers=None, pairs=None, threshold=0.15, integrate=True, maps=True):
+        """Whether two markers sit on the same pixels of a cell, from the segmentation mask the run works on -- after ``repair_mask`` and
+        ``expand_mask``: a real double positive (the two rise and fall together over the cell's pixels), a segmentation doublet (separate
+        lobes) or a neighbour's spill (one fills the cell, the other hugs the rim) read differently.  ops.cell_coloc
+        (csrc/colocalization.hip) adds, per cell and in a fixed fp64 order, the selected markers, their centred cross products and each marker
+        over the pixels where another is above its gate, and counts the pixels above both gates; colocalization.features, which states every
+        formula, finishes on the host: Pearson's ``r``, the Manders ``overlap`` coefficient, the Manders fractions ``m1`` and ``m2``,
+        ``both_fraction`` and ``jaccard`` per cell and marker pair.  ``markers``: the names of the channels to correlate, 2 to 32 of them, each
+        once (None: every image channel; more than 32 channels need a selection).  ``pairs``: names ``"A:B"`` of selected markers for which the
+        full statistics and the maps are written.  ``threshold``: the gate T, 0 <= T < 1, on the normalised scale of ``intensity_full`` -- 0.15
+        is CellProfiler's default of 15 %, a default for a setting, not a measured value; the kernel compares the image with
+        ``np.float32(2 T - 1)``, strictly.  Per image it writes ``{batch_id}_colocalization_{image number}.csv`` (colocalization.cells_csv,
+        one line per cell in id order: ``id``, ``cell type``, ``area``, then ``{A}~{B}_r`` per pair), with ``pairs``
+        ``{batch_id}_colocalization_pairs_{image number}.csv`` (colocalization.pairs_csv) and, with ``maps`` too, one
+        ``{batch_id}_colocalization_{A}_{B}_{image number}.png`` per named pair (intensities.file_slug), r painted through ops.colorize with
+        the diverging table on +- 1 (colocalization.colour_index; NaN cells at index 0, background 0).  Per group (the batch with
+        ``integrate``, else every image), with stem = ``{batch_id}_integrated_colocalization`` or ``{batch_id}_colocalization`` and the image
+        number at the end of each name: ``{stem}_summary.csv`` (colocalization.summary_csv, per cell type and pair), ``{stem}.csv`` / ``.png``,
+        the K x K matrix of the median r over all cells, and ``{stem}_{cell type}.csv`` / ``.png``, the same per cell type present (for a
+        single image ``{batch_id}_colocalization_medians...``, since ``{batch_id}_colocalization_{image number}.csv`` is its cell table).
+        Keeps the per-cell r as ``self.colocalization_r``, one (n, K (K - 1) / 2) array per local image, and records
+        ``colocalization_stats``, one record per group written by this rank; its ``kernel_ms`` is the host's clock around ops.cell_coloc with
+        the copy of the outputs back (tools/time_consumers.py --colocalization times the kernel alone).  Multi-rank runs as cell_intensities.
+        A wrong argument raises ValueError before anything is written or set."""
+        import time
+        from . import colocalization, intensities
+        self._check_annotated("No annotations")
+        n_local = len(self.annotations) if self._computes_here() else 0
+        c_img = int(self.preprocessor.images_dev[0].shape[0]) if n_local else len(self.channel_parser.markers)
+        all_markers = self._marker_names(c_img)
+        if markers is None:
+            if c_img > colocalization.MAX_MARKERS:
+                raise ValueError(f"marker_colocalization correlates at most {colocalization.MAX_MARKERS} markers and the images have {c_img} "
+                                 f"channels: select some with markers=[...]")
+            chan = list(range(c_img))
+        else:
+            chosen = [str(m) for m in markers]
+            for m in chosen:
+                if all_markers.count(m) != 1 or chosen.count(m) != 1:
+                    raise ValueError(f"marker_colocalization: {m!r} is not one marker of {all_markers}, named once")
+            chan = [all_markers.index(m) for m in chosen]
+        if not 2 <= len(chan) <= colocalization.MAX_MARKERS:
+            raise ValueError(f"marker_colocalization correlates 2 to {colocalization.MAX_MARKERS} markers, got {len(chan)}: select some with markers=[...]")
+        sel = [all_markers[c] for c in chan]
+        k = len(chan)
+        p, off = k * (k + 1) // 2, colocalization.off_pairs(k)
+        columns = colocalization.parse_pairs(pairs, sel)
+        thr = colocalization.gates(threshold, k)
+        t = len(self.cell_types)
+        names = [str(c) for c in self.cell_types]
+        self.colocalization_stats = []
+        kept = self.colocalization_r = []
+        if not self._computes_here():
+            return None
+        lut = colors.diverging_table()
+        width = 4 + p + k + p + k * k      # image number, cell id, cell type, area, then both, sums, cross, gated: a row of the exchange
+        for members in _groups(integrate, n_local):
+            rows, image_files, kernel_ms, draw_ms = [np.zeros((0, width))], [], 0.0, 0.0
+            for i in members:
+                ids = np.asarray(self.preprocessor.cell_ids[i], dtype=np.int64)
+                mask, image = self.preprocessor.masks_dev[i], self.preprocessor.images_dev[i]
+                n = len(ids)
+                if int(image.shape[0]) != c_img:
+                    raise ValueError(f"image {self._image_number(i)} has {int(image.shape[0])} channels, the batch {c_img}")
+                types = self._cell_type_ints(i) if n else np.zeros(0, dtype=np.int64)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                area, both, sums, cross, gated = ops.cell_coloc(image, mask, self.preprocessor.cell_ids_dev[i], self.preprocessor.cell_bbox_dev[i], chan, thr)
+                kernel_ms += (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                feat = colocalization.features(area, both, sums, cross, gated)
+                kept.append(feat["r"].copy())
+                number = self._image_number(i)
+                image_files.append(f"{self.batch_id}_colocalization_{number}.csv")
+                self._write_text(image_files[-1], colocalization.cells_csv(ids, types, names, sel, area, feat["r"]))
+                if columns:
+                    image_files.append(f"{self.batch_id}_colocalization_pairs_{number}.csv")
+                    self._write_text(image_files[-1], colocalization.pairs_csv(ids, types, names, sel, columns, area, feat))
+                    for col in columns if maps else ():
+                        a, b = off[col]
+                        image_files.append(f"{self.batch_id}_colocalization_{intensities.file_slug(sel[a])}_{intensities.file_slug(sel[b])}_{number}.png")
+                        idx = colocalization.colour_index(feat["r"][:, col])
+                        self._paint_map(i, lut[idx], idx, image_files[-1])
+                rows.append(np.concatenate([np.full((n, 1), float(number)), ids.reshape(n, 1).astype(np.float64), types.reshape(n, 1).astype(np.float64),
+                                            area.reshape(n, 1).astype(np.float64), both.reshape(n, p).astype(np.float64), sums.reshape(n, k),
+                                            cross.reshape(n, p), gated.reshape(n, k * k)], axis=1))
+                draw_ms += (time.perf_counter() - t0) * 1e3
+            table = np.concatenate(rows, axis=0)
+            if integrate and self.tile_mode:
+                table, _ = self._gather_rows(table)
+            if integrate and self.rank != 0:
+                continue
+            t0 = time.perf_counter()
+            cells = len(table)
+            types = table[:, 2].astype(np.int64)
+            area, both = table[:, 3].astype(np.int64), table[:, 4:4 + p].astype(np.int64)
+            sums, cross = table[:, 4 + p:4 + p + k], table[:, 4 + p + k:4 + 2 * p + k]
+            gated = table[:, 4 + 2 * p + k:].reshape(cells, k, k)
+            feat = colocalization.features(area, both, sums, cross, gated)
+            stem, tail = self._group_stem("colocalization", integrate, members)
+            mid = "" if integrate else "_medians"      # {batch_id}_colocalization_{image number}.csv is the image's cell table
+            files = [stem + "_summary" + tail + ".csv"]
+            self._write_text(files[0], colocalization.summary_csv(names, sel, colocalization.summary(types, t, feat)))
+            figures = []
+            groups = [("", None)] + [("_" + intensities.file_slug(names[a]), types == a) for a in range(t) if (types == a).any()]
+            for suffix, of_type in groups:
+                matrix = colocalization.median_matrix(feat["r"], k, of_type)
+                files.append(stem + mid + suffix + tail + ".csv")
+                self._write_text(files[-1], colocalization.matrix_csv(sel, matrix))
+                fig = self._write_table_figure(stem + mid + suffix + tail, matrix, -colocalization.LIMIT, colocalization.LIMIT, row_names=sel, col_names=sel)
+                files.append(fig["file"])
+                figures.append({"file": fig["file"], "limit": colocalization.LIMIT, "rect": fig["rect"]})
+            draw_ms += (time.perf_counter() - t0) * 1e3
+            valid = int((~np.isnan(feat["r"])).any(axis=1).sum()) if cells else 0
+            rec = {"file": files[0], "files": files, "image_files": image_files, "figure": figures[0], "figures": figures, "n": cells, "K": k, "T": t,
+                   "markers": sel, "pairs": [colocalization.pair_names(sel)[c] for c in columns], "threshold": float(threshold), "valid": valid,
+                   "kernel_ms": kernel_ms, "draw_ms": draw_ms}
+            self.colocalization_stats.append(rec)
+            self.logger.log("Marker colocalization {}: {} cells, {} markers, {} cell types, gate {:g}; {} cells with a valid r; ops.cell_coloc with "
+                            "its copies {:.1f}, tables and drawing {:.1f} ms.".format(files[0], cells, k, t, float(threshold), valid, kernel_ms, draw_ms))
+
     # ---- spatial autocorrelation: which markers are spatially structured, before any label is trusted (squidpy's spatial_autocorr) ----------------
     def spatial_autocorrelation(self, n_neighbors=25, n_perms=1000, integrate=True):
         """Moran's I and Geary's C of every image channel over the k-NN graph of the cell centroids (``n_neighbors`` counts the cell itself, as

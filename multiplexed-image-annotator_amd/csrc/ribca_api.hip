@@ -558,7 +558,7 @@ void run_last_block_cls_fold(const BlockW& L, const BlockWs& w, int cells, const
 
 extern "C" {
 
-int ribca_version(void) { return 113; }
+int ribca_version(void) { return 114; }
 const char* ribca_last_error(void) { return api_last_error(); }
 
 // the launcher table of libribca_hip_test.so (csrc/ribca_internal.h): the only way into the library besides the C entry points

@@ -946,6 +946,72 @@ def cell_shell_sums(image: torch.Tensor, mask: torch.Tensor, depth2: torch.Tenso
     return count.cpu().numpy(), deepest.cpu().numpy(), sums.cpu().numpy()
 
 
+COLOC_RESIDENT = 4096             # csrc/colocalization.hip CO_RESIDENT: a cell of more pixels takes the streaming form
+COLOC_MAX_MARKERS = 32            # csrc/colocalization.hip CO_K_MAX: a gate word is 32 bits
+COLOC_CHUNK_BYTES = 1 << 30       # the device outputs of one launch of cell_coloc stay within this; more cells go in consecutive chunks
+
+
+def cell_coloc(image: torch.Tensor, mask: torch.Tensor, ids, bbox, chan: Sequence[int], thr: Sequence[float],
+               out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """Per cell the second-order sums of K selected channels over the cell's own pixels: ``image`` (C, H, W) fp32 and ``mask`` (H, W) int32 on
+    the device, ``ids`` (n) and ``bbox`` (n, 4) as for ``cell_intensities`` (host arrays or device tensors), ``chan`` K distinct channel indices
+    (2 <= K <= COLOC_MAX_MARKERS, any order) and ``thr`` one finite gate per selected channel on the image's own scale (a pixel is above its
+    gate when ``value > thr``, strictly).  Returns host arrays ``area`` (n) int32, ``both`` (n, P) int32 -- the pixels above both gates of every
+    pair (k, l), k <= l, in the order (0,0), (0,1) .. (0,K-1), (1,1) .., P = K (K + 1) / 2 of them --, ``sums`` (n, K) fp64, ``cross`` (n, P) fp64 -- the centred cross products -- and
+    ``gated`` (n, K, K) fp64 -- ``gated[:, k, l]`` the sum of channel k over the pixels where channel l is above its gate (include/ribca_hip.h
+    states the summation order; colocalization.features turns them into the coefficients).  The cells go in consecutive chunks whose device
+    outputs stay within COLOC_CHUNK_BYTES; every cell is worked alone, so the result does not depend on the chunking.  ``out``: device tensors
+    to fill instead (returned as they are, no copy back, no synchronise)."""
+    assert image.is_cuda and image.dtype == torch.float32 and image.dim() == 3
+    assert mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2 and tuple(mask.shape) == tuple(image.shape[1:])
+    dev = image.device
+    ch = np.ascontiguousarray(np.asarray(chan, dtype=np.int32).reshape(-1))
+    gates = np.ascontiguousarray(np.asarray(thr, dtype=np.float32).reshape(-1))
+    k = len(ch)
+    if len(gates) != k:
+        raise ValueError(f"cell_coloc takes one gate per selected channel, got {len(gates)} for {k} channels")
+    p = k * (k + 1) // 2
+    c, h, w = (int(v) for v in image.shape)
+    ids_d = ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1)))
+    bbox_d = bbox if torch.is_tensor(bbox) else torch.from_numpy(np.ascontiguousarray(np.asarray(bbox, dtype=np.int32).reshape(-1, 4)))
+    ids_d = ids_d.to(device=dev, dtype=torch.int32).contiguous()
+    bbox_d = bbox_d.to(device=dev, dtype=torch.int32).contiguous()
+    n = ids_d.numel()
+    if tuple(bbox_d.shape) != (n, 4):
+        raise ValueError(f"cell_coloc takes one box rmin, rmax, cmin, cmax per cell, got {tuple(bbox_d.shape)} for {n} cells")
+    image, mask = image.contiguous(), mask.contiguous()
+    per_cell = 4 + 4 * p + 8 * k + 8 * p + 8 * k * k      # bytes of the five outputs
+    step = max(1, COLOC_CHUNK_BYTES // per_cell)
+
+    def launch(lo, hi, area, both, sums, cross, gated):
+        check(lib().ribca_cell_coloc(ptr(image), c, h, w, ptr(mask), ptr(ids_d[lo:hi]), ptr(bbox_d[lo:hi]), hi - lo,
+                                     ch.ctypes.data_as(ctypes.c_void_p), gates.ctypes.data_as(ctypes.c_void_p), k, ptr(area), ptr(both), ptr(sums),
+                                     ptr(cross), ptr(gated), stream_ptr()), "ribca_cell_coloc")
+
+    if out is not None:
+        area, both, sums, cross, gated = out
+        assert all(x.is_cuda and x.is_contiguous() for x in out)
+        assert area.dtype == torch.int32 and both.dtype == torch.int32 and all(x.dtype == torch.float64 for x in (sums, cross, gated))
+        assert area.numel() == n and both.numel() == n * p and sums.numel() == n * k and cross.numel() == n * p and gated.numel() == n * k * k
+        both2, sums2, cross2, gated2 = both.view(n, p), sums.view(n, k), cross.view(n, p), gated.view(n, k * k)
+        for lo in range(0, n, step):      # the caller's tensors hold every cell: a chunk is a slice of rows of each
+            hi = min(lo + step, n)
+            launch(lo, hi, area.view(n)[lo:hi], both2[lo:hi], sums2[lo:hi], cross2[lo:hi], gated2[lo:hi])
+        return out
+    host = (np.empty((n,), np.int32), np.empty((n, p), np.int32), np.empty((n, k), np.float64), np.empty((n, p), np.float64),
+            np.empty((n, k, k), np.float64))
+    for lo in range(0, n, step):
+        hi = min(lo + step, n)
+        m = hi - lo
+        dev_out = (torch.empty((m,), dtype=torch.int32, device=dev), torch.empty((m, p), dtype=torch.int32, device=dev),
+                   torch.empty((m, k), dtype=torch.float64, device=dev), torch.empty((m, p), dtype=torch.float64, device=dev),
+                   torch.empty((m, k, k), dtype=torch.float64, device=dev))
+        launch(lo, hi, *dev_out)
+        for dst, src in zip(host, dev_out):
+            dst[lo:hi] = src.cpu().numpy()
+    return host
+
+
 AUTOCORR_MAX_CHANNELS = 64      # csrc/autocorr.hip
 AUTOCORR_MAX_NEIGHBOURS = 31
 

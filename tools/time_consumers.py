@@ -33,7 +33,10 @@ dropped and merged, device events, beside ribca_contact_table at d = 1 in the sa
 matching.py on the host clock, and np.unique over the 64-bit pair keys of the same two masks on the host (``--matching``: this section alone); and the
 marker localisation (csrc/localization.hip): ribca_mask_depth at D = 8 and 32 and ribca_cell_shell_sums on the 15-channel image of the same tile,
 device events, the whole ops calls and the host features on the host clock, scipy's distance_transform_edt of the foreground on the host, and the
-restatement of tests/localization_numpy.py on a crop, scaled by the area (``--localization``: this section alone)."""
+restatement of tests/localization_numpy.py on a crop, scaled by the area (``--localization``: this section alone); and the marker colocalisation
+(csrc/colocalization.hip): ribca_cell_coloc on the 15-channel image of the same tile at K = 15 and K = 4, device events, beside
+ribca_cell_intensities in the same process, the whole ops.cell_coloc and the host features on the host clock, and the restatement of
+tests/coloc_numpy.py on a crop, scaled by the area (``--colocalization``: this section alone)."""
 import os
 import sys
 import time
@@ -703,6 +706,87 @@ def time_localization():
           f"{depth_ms * scale / 1e3:.1f} s and {sums_ms * scale / 1e3:.1f} s scaled by area to {h}x{w}; equal to the GPU outputs of the same crop, byte for byte: {same}")
 
 
+def time_colocalization():
+    """mask, image, ids, boxes and outputs on the device before the clock starts: ribca_cell_coloc between two device events, median of five
+    calls after a warm-up, at K = 15 (every channel) and at K = 4, and ribca_cell_intensities (median alone) in the same process as the
+    yardstick -- 30 trees per cell against the 15 + 120 + 225 of K = 15; then the whole ops.cell_coloc with its copies and the host features on
+    the host clock, and the numpy restatement on a crop, checked against the GPU on the same crop"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import coloc_numpy as CN
+    import intensities_numpy as IN
+    from multiplexed_image_annotator_amd import colocalization
+    h, w = mask.shape
+    c = 15
+
+    def events(call):
+        call()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            call()
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop))
+        return f"median {sorted(times)[2]:.3f} ms, min {min(times):.3f}, max {max(times):.3f} of 5 (device events)"
+
+    _, raw = synth.make_mask_and_image(h, w, 100000, c, synth.SEED_BASE + 3, device=dev)
+    image = (raw.to(torch.float32) / 32767.5 - 1.0).contiguous()      # the normalised range, with the background's ties
+    del raw
+    ids_d = torch.from_numpy(np.asarray(ids, dtype=np.int32)).to(dev)
+    bbox_d = torch.from_numpy(np.ascontiguousarray(tab[:, :4], dtype=np.int32)).to(dev)
+    hbm = f"one read of the {image.numel() * 4 / 1e9:.2f} GB image at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: {1e3 * image.numel() * 4 / HBM_BYTES_PER_S:.2f} ms"
+    for k in (c, 4):
+        chan, thr = list(range(k)), colocalization.gates(colocalization.THRESHOLD, k)
+        p = k * (k + 1) // 2
+        out = (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n, p), dtype=torch.int32, device=dev),
+               torch.empty((n, k), dtype=torch.float64, device=dev), torch.empty((n, p), dtype=torch.float64, device=dev),
+               torch.empty((n, k, k), dtype=torch.float64, device=dev))
+        took = events(lambda: ops.cell_coloc(image, mask, ids_d, bbox_d, chan, thr, out=out))
+        area = out[0].cpu().numpy()
+        print(f"cell coloc, K = {k}: {took} for {n} cells, {k + p + k * k} trees per cell, {h}x{w}; {hbm}; areas are the label table's: "
+              f"{np.array_equal(area, tab[:, 6])}; cells above {ops.COLOC_RESIDENT} px (streamed): {int((area > ops.COLOC_RESIDENT).sum())}")
+    q_num = np.array([1], dtype=np.int32)
+    out_i = (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n, c, 2), dtype=torch.float64, device=dev),
+             torch.empty((n, c, 1, 2), dtype=torch.float32, device=dev))
+    took = events(lambda: ops.cell_intensities(image, mask, ids_d, bbox_d, q_num, 2, out=out_i))
+    print(f"cell intensities, the median alone, same process (the yardstick: {2 * c} trees per cell): {took}")
+    chan, thr = list(range(c)), colocalization.gates(colocalization.THRESHOLD, c)
+    fn = lambda: ops.cell_coloc(image, mask, ids_d, bbox_d, chan, thr)      # noqa: E731
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        got = fn()
+        torch.cuda.synchronize()
+        times.append(1e3 * (time.perf_counter() - t0))
+    print(f"ops.cell_coloc, K = {c}, with the copy of its outputs to the host: median {sorted(times)[2]:.2f} ms, min {min(times):.2f}, max {max(times):.2f} "
+          f"of 5 (host clock)")
+    t0 = time.perf_counter()
+    feat = colocalization.features(*got)
+    print(f"colocalization.features on the host, {n} cells x {c * (c - 1) // 2} pairs: {1e3 * (time.perf_counter() - t0):.0f} ms; cells without any r: "
+          f"{int(np.isnan(feat['r']).all(axis=1).sum())}")
+    side = 1024
+    host = mask.cpu().numpy()
+    crop_mask = np.ascontiguousarray(host[:side, :side])
+    crop_image = np.ascontiguousarray(image[:, :side, :side].cpu().numpy())
+    crop_ids = np.unique(crop_mask[crop_mask > 0]).astype(np.int32)
+    crop_box = IN.boxes_of_all(crop_mask, crop_ids)
+    t0 = time.perf_counter()
+    want = CN.coloc(crop_image, crop_mask, crop_ids, crop_box, chan, thr)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    g = ops.cell_coloc(torch.from_numpy(crop_image).to(dev), torch.from_numpy(crop_mask).to(dev), crop_ids, crop_box, chan, thr)
+    same = all(a.tobytes() == b.tobytes() for a, b in zip(g, want))
+    scale = (h * w) / (side * side)
+    print(f"numpy restatement, K = {c}, top-left {side}x{side} crop, {len(crop_ids)} cells (host): {host_ms:.0f} ms -> {host_ms * scale / 1e3:.1f} s scaled "
+          f"by area to {h}x{w}; equal to the GPU outputs of the same crop, byte for byte: {same}")
+
+
+if "--colocalization" in sys.argv:      # this section alone
+    time_colocalization()
+    sys.exit(0)
 if "--localization" in sys.argv:      # this section alone
     time_localization()
     sys.exit(0)
