@@ -108,6 +108,13 @@ int64_t ribca_vit_blob_len(int32_t D, int32_t C, int32_t K, int32_t depth);
 int ribca_vit_create(const float* blob, int64_t blob_len, int32_t D, int32_t C, int32_t K, int32_t depth, void* stream,
                      ribca_vit_t** out);
 void ribca_vit_destroy(ribca_vit_t* m);
+/* The fast level of ribca_vit_forward for this handle.  2 (what create sets): every MX product the width allows, among them the QKV phase of
+ * the fused per-cell kernel (csrc/cell_attention_mx.hip; D = 384, RIBCA_CELL_ATTN_MX != 0); 1: that kernel at three fp16 passes
+ * (csrc/cell_attention.hip), every other product as at level 2.  A load-time probe that refuses level 2 for a model's weights can so keep the
+ * model's fc1 / fc2 MX products.  Returns the level in effect (1 where the handle has no per-cell MX kernel to switch off), -1 on a bad
+ * argument.  Arena and workspace sizes do not depend on the level; ribca_vit_forward_precise is untouched by it.  Not thread-safe against a
+ * forward of the same handle. */
+int32_t ribca_vit_set_fast_level(ribca_vit_t* m, int32_t level);
 
 /* Scratch bytes ribca_vit_forward needs to process `chunk_cells` cells at a time. */
 int64_t ribca_vit_workspace_bytes(const ribca_vit_t* m, int32_t chunk_cells);

@@ -102,6 +102,13 @@ int ribca_test_gemm_duo_gelu(const uint16_t* A, int32_t lda, const uint16_t* W, 
  * ribca_test_qkv_attention_fold, q / k / v never leave the CU.  Non-zero return: geometry not supported. */
 int ribca_test_cell_attention(const uint16_t* z_ps, int32_t lda, const uint16_t* W, int32_t ldw, int32_t cells, int32_t D,
                               const float* bias2, const float* csum, const float* rowstat, uint16_t* out, int32_t ldo, void* stream);
+/* ribca_test_cell_attention with the QKV phase as fp16 hi * hi + two block-scaled products (cell_attention_mx.hip; D = 384).  The weight is
+ * read from its stage image: img (ribca_test_cell_attention_mx_image_bytes(D) bytes, every byte written) = pack of the packed-split folded
+ * weight W [>= 3 D][ldw].  Non-zero return: D is not 384, a NULL buffer, or a row pitch below 2 D. */
+int64_t ribca_test_cell_attention_mx_image_bytes(int32_t D);
+int ribca_test_cell_attention_mx_pack(const uint16_t* W, int32_t ldw, int32_t D, uint8_t* img, void* stream);
+int ribca_test_cell_attention_mx(const uint16_t* z_ps, int32_t lda, const uint8_t* img, int32_t cells, int32_t D, const float* bias2,
+                                 const float* csum, const float* rowstat, uint16_t* out, int32_t ldo, void* stream);
 /* proj + residual, norm2, fc1, GELU, fc2 + residual of a 144-wide block in ONE kernel (cell_mlp.hip), token rows stationary in registers.
  * projw / fc1w (gamma o W, from fold_weight) / fc2w: packed-split weights [>= N][2 * Kp]; img_scratch (ribca_test_cell_mlp_image_bytes(D)
  * bytes): their stage image, written here when pack != 0 and only read otherwise.  z_ps rows 0 .. M - 1 are updated in place (columns

@@ -130,6 +130,7 @@ SIGNATURES = {
     "ribca_vit_blob_len": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ribca_vit_create": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, POINTER(c_void_p)]),
     "ribca_vit_destroy": (None, [c_void_p]),
+    "ribca_vit_set_fast_level": (c_int32, [c_void_p, c_int32]),
     "ribca_vit_workspace_bytes": (c_int64, [c_void_p, c_int32]),
     "ribca_vit_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "ribca_vit_forward_precise": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -192,6 +193,10 @@ TEST_SIGNATURES = {
                                            c_void_p, c_void_p, c_int32, c_void_p]),
     "ribca_test_cell_attention": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                             c_void_p]),
+    "ribca_test_cell_attention_mx_image_bytes": (c_int64, [c_int32]),
+    "ribca_test_cell_attention_mx_pack": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "ribca_test_cell_attention_mx": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                               c_void_p]),
     "ribca_test_cell_mlp_image_bytes": (c_int64, [c_int32]),
     "ribca_test_cell_mlp": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                       c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),

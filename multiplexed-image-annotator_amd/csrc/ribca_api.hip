@@ -119,16 +119,20 @@ struct BlockW {
   const uint16_t *qkvmxh = nullptr, *fc1mxh = nullptr; const unsigned char *qkvmxx = nullptr, *fc1mxx = nullptr;
   // proj, gamma o fc1 and fc2 as the stage image of the one-kernel second half (cell_mlp.hip; BlockPath::cell_mlp)
   const uint16_t* mlpimg = nullptr;
+  // gamma o qkv as the stage image of the per-cell kernel's MX form (cell_attention_mx.hip; BlockPath::cell_attn_mx)
+  const unsigned char* qkvcmx = nullptr;
 };
 
 // The process switches (A/B), read from the environment once per process.  RIBCA_MX=0: the fp16x3 kernels everywhere.  RIBCA_MXZ=0: qkv / fc1
 // stay on the fp16x3 kernels.  RIBCA_CELL_ATTN=0: the unfused qkv GEMM + attention pair in place of the per-cell kernel.  RIBCA_CELL_MLP=0: proj,
 // fc1 and fc2 of the 144-wide classifier as three GEMMs with their finalisers in place of the one-kernel second half.  RIBCA_CLS_ATTN=0: the
-// last block's attention as K / V GEMM + Q GEMM + attention kernel in place of the CLS-only form (cls_attention.hip).
+// last block's attention as K / V GEMM + Q GEMM + attention kernel in place of the CLS-only form (cls_attention.hip).  RIBCA_CELL_ATTN_MX=0: the
+// per-cell kernel's QKV phase at three fp16 passes (cell_attention.hip) at every width.
 bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
-struct Switches { bool mx, mxz, cell_attn, cell_mlp, cls_attn; };
+struct Switches { bool mx, mxz, cell_attn, cell_mlp, cls_attn, cell_attn_mx; };
 const Switches& switches() {
-  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN"), env_on("RIBCA_CELL_MLP"), env_on("RIBCA_CLS_ATTN")};
+  static const Switches sw = {env_on("RIBCA_MX"), env_on("RIBCA_MXZ"), env_on("RIBCA_CELL_ATTN"), env_on("RIBCA_CELL_MLP"), env_on("RIBCA_CLS_ATTN"),
+                              env_on("RIBCA_CELL_ATTN_MX")};
   return sw;
 }
 // The choice depends on the model's width alone, never on the chunk: a cell's bits must not depend on the size of the chunk it was computed in.
@@ -148,11 +152,14 @@ bool mx_z_on(int D) { return switches().mxz && mx_on(D) && D % 192 == 0; }
 //              registers (cell_mlp.hip; D = 144): no h buffer, no statistics partials, no finaliser on this path
 //   cls_attn   the attention of the CLS-only last block without the K / V product (cls_attention.hip; D = 144, 288, 384, 576; the imputer
 //              has no CLS-only block): three short fp32 launches in place of a [cells T x D] [D x 2 D] GEMM, a Q GEMM and the attention kernel
+//   cell_attn_mx  the QKV phase of the per-cell kernel as fp16 hi * hi + two block-scaled products (cell_attention_mx.hip; D = 384).  The one
+//              flag that is not fixed at create: ribca_vit_set_fast_level clears it (level 1) or sets it again (level 2) where the arena holds
+//              the stage image -- the layout keeps the image either way, so the arena and the workspace do not depend on the level
 struct BlockPath {
-  bool fold, mx_fc2, mx_z, cell_attn, cell_mlp, cls_attn;
+  bool fold, mx_fc2, mx_z, cell_attn, cell_mlp, cls_attn, cell_attn_mx;
   // ribca_vit_forward_precise: no MX product.  The fused per-cell kernels and the CLS-only attention are fp16x3 / fp32 and stay.  Layouts always
   // take the handle's own path, so that both entry points share one arena and one workspace size.
-  BlockPath precise() const { return {fold, false, false, cell_attn, cell_mlp, cls_attn}; }
+  BlockPath precise() const { return {fold, false, false, cell_attn, cell_mlp, cls_attn, false}; }
   // a whole block's qkv product reads the MX3 copy of the residual rows (so whatever wrote those rows must have left one)
   bool qkv_mx3() const { return mx_z && !cell_attn; }
   // q / k / vt exist: some launch of this path goes through the qkv GEMM + attention kernel pair
@@ -161,12 +168,14 @@ struct BlockPath {
 BlockPath block_path(const AttnGeom& a, bool fold) {
   const bool cell_attn = fold && switches().cell_attn && cell_attention_supported(a.D, a.H, a.T);
   return {fold, fold && mx_on(a.D), fold && mx_z_on(a.D), cell_attn, cell_attn && switches().cell_mlp && cell_mlp_supported(a.D),
-          fold && switches().cls_attn && cls_attention_supported(a.D, a.H, a.T)};
+          fold && switches().cls_attn && cls_attention_supported(a.D, a.H, a.T),
+          cell_attn && mx_on(a.D) && switches().cell_attn_mx && cell_attention_mx_supported(a.D, a.H, a.T)};
 }
 
 struct ribca_vit {
   int D, C, K, depth, Dp;
   BlockPath path;
+  bool cell_attn_mx_image = false;   // the arena holds the per-cell MX stage image (path.cell_attn_mx at create): what level 2 may switch on
   char* arena = nullptr;
   size_t arena_bytes = 0;
   const float *cls, *pos, *pe_b, *norm_w, *norm_b, *head_w, *head_b;
@@ -222,6 +231,7 @@ void layout_block(Carver& c, BlockW& L, int D, const BlockPath& p) {
     L.fc1mxh = c.take<uint16_t>(mx_wh_bytes(4 * D, Kz) / 2); L.fc1mxx = c.take<unsigned char>(mx_wx_bytes(4 * D, Kz));
   }
   if (p.cell_mlp) L.mlpimg = c.take<uint16_t>(cell_mlp_image_bytes(D) / 2);
+  if (p.cell_attn_mx) L.qkvcmx = c.take<unsigned char>(cell_attention_mx_image_bytes(D));
 }
 
 // lays the arena out; with base == nullptr only measures
@@ -302,6 +312,7 @@ struct BlobReader {
       launch_mx_pack_w(L.fc1w, 2 * Dp, 4 * D, Dp, Kz, const_cast<uint16_t*>(L.fc1mxh), const_cast<unsigned char*>(L.fc1mxx), s);
     }
     if (path.cell_mlp) launch_cell_mlp_pack(L.projw, L.fc1w, L.fc2w, D, const_cast<uint16_t*>(L.mlpimg), s);
+    if (path.cell_attn_mx) launch_cell_attention_mx_pack(L.qkvw, 2 * Dp, D, const_cast<unsigned char*>(L.qkvcmx), s);
   }
 };
 int64_t block_params(int64_t d) { return 2 * d + 3 * d * d + 3 * d + d * d + d + 2 * d + 4 * d * d + 4 * d + 4 * d * d + d; }
@@ -441,7 +452,8 @@ void run_block_fold(const BlockW& L, const BlockWs& w, int cells, const AttnGeom
   zmx.M = Mc;
   if (p.cell_attn) {
     ProfScope ps(P_CELL, s);
-    launch_cell_qkv_attention(w.zps, ld_x, L.qkvw, ld_x, L.qkvb2, L.qkvc, w.rs, w.xa, ld_x, cells, D, scale, s);
+    if (p.cell_attn_mx) launch_cell_qkv_attention_mx(w.zps, ld_x, L.qkvcmx, L.qkvb2, L.qkvc, w.rs, w.xa, ld_x, cells, D, scale, s);
+    else launch_cell_qkv_attention(w.zps, ld_x, L.qkvw, ld_x, L.qkvb2, L.qkvc, w.rs, w.xa, ld_x, cells, D, scale, s);
   } else {
     {
       ProfScope ps(P_QKV, s);
@@ -594,6 +606,7 @@ int ribca_vit_create(const float* blob, int64_t blob_len, int32_t D, int32_t C, 
   m->D = D; m->C = C; m->K = K; m->depth = depth;
   m->Dp = round_up(D, 32);
   m->path = block_path(make_attn_geom(D, kHeads, kTokens), true);
+  m->cell_attn_mx_image = m->path.cell_attn_mx;
   m->arena_bytes = layout(m, nullptr);
   hipError_t e = hipMalloc((void**)&m->arena, m->arena_bytes);
   if (e != hipSuccess) { delete m; return hip_fail(e, "hipMalloc(weights)"); }
@@ -611,6 +624,16 @@ int ribca_vit_create(const float* blob, int64_t blob_len, int32_t D, int32_t C, 
   if (api_finish() != 0) { ribca_vit_destroy(m); return 1; }
   *out = m;
   return 0;
+}
+
+// The fast level of ribca_vit_forward: 2 = every MX product the width allows, the per-cell kernel's QKV phase included (what create sets);
+// 1 = the per-cell kernel at three fp16 passes, every other product as at level 2.  Returns the level in effect -- 1 where the handle has no
+// per-cell MX kernel to switch -- or -1.  Neither the arena nor the workspace size depends on it.  Not to be called while a forward of the handle runs.
+int32_t ribca_vit_set_fast_level(ribca_vit_t* m, int32_t level) {
+  if (!m) { (void)fail("ribca_vit_set_fast_level: model is NULL"); return -1; }
+  if (level != 1 && level != 2) { (void)fail("ribca_vit_set_fast_level: level must be 1 or 2"); return -1; }
+  m->path.cell_attn_mx = level == 2 && m->cell_attn_mx_image;
+  return m->path.cell_attn_mx ? 2 : 1;
 }
 
 void ribca_vit_destroy(ribca_vit_t* m) {

@@ -12,7 +12,7 @@
 #include "ribca_kernels.h"
 #include "ribca_status.h"
 
-#define RIBCA_INTERNAL_VERSION 6005
+#define RIBCA_INTERNAL_VERSION 6006
 
 // every function of namespace ribca that csrc/ribca_test_api.hip calls (none of them overloaded)
 #define RIBCA_INTERNAL_FUNCS(X)                                                                                                              \
@@ -23,7 +23,8 @@
   X(launch_gemm_gelu_mx) X(launch_gemm_resid_ps) X(launch_gemm_mx_resid) X(launch_gemm_mx_qkv_ln) X(launch_gemm_mx_gelu) X(launch_attention) \
   X(launch_cell_qkv_attention) X(cell_mlp_supported) X(cell_mlp_image_bytes) X(launch_cell_mlp_pack) X(launch_cell_mlp)                     \
   X(cls_attention_supported) X(cls_attention_cell_tile) X(launch_cls_attn_qg) X(launch_cls_attn_ybar) X(launch_cls_attn_out)           \
-  X(attention_supported) X(attention_v_elems)
+  X(attention_supported) X(attention_v_elems)                                                                                               \
+  X(cell_attention_mx_supported) X(cell_attention_mx_image_bytes) X(launch_cell_attention_mx_pack) X(launch_cell_qkv_attention_mx)
 
 namespace ribca {
 struct InternalTable {

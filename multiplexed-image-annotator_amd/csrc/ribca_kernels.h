@@ -105,6 +105,14 @@ bool cell_attention_supported(int D, int H, int T);
 void launch_cell_qkv_attention(const uint16_t* z, int ldz, const uint16_t* W, int ldw, const float* bias2, const float* csum, const float2* rowstat,
                                uint16_t* out, int ldo, int cells, int D, float scale, hipStream_t s);
 
+// The same kernel with the QKV phase on the MX products (cell_attention_mx.hip; D = 384): the weight comes from its stage image
+// (launch_cell_attention_mx_pack from the packed-split gamma o W, cell_attention_mx_image_bytes bytes, once at create).
+bool cell_attention_mx_supported(int D, int H, int T);
+size_t cell_attention_mx_image_bytes(int D);
+void launch_cell_attention_mx_pack(const uint16_t* W, int ldw, int D, unsigned char* img, hipStream_t s);
+void launch_cell_qkv_attention_mx(const uint16_t* z, int ldz, const unsigned char* img, const float* bias2, const float* csum, const float2* rowstat,
+                                  uint16_t* out, int ldo, int cells, int D, float scale, hipStream_t s);
+
 // ----- second half of a 144-wide block in one kernel (cell_mlp.hip): proj + residual, norm2, fc1, GELU, fc2 + residual, token rows
 // stationary in registers.  img: the block's proj / (gamma o fc1) / fc2 weights as ONE stage image in consumption order
 // (launch_cell_mlp_pack from the packed-split weights, cell_mlp_image_bytes bytes, once at create).  xa: attention output rows (read only),

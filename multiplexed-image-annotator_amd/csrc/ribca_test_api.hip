@@ -299,6 +299,26 @@ int ribca_test_cell_attention(const uint16_t* z_ps, int32_t lda, const uint16_t*
   RIBCA_FINISH();
   return 0;
 }
+int64_t ribca_test_cell_attention_mx_image_bytes(int32_t D) { if (table() == nullptr) return 0; return (int64_t)cell_attention_mx_image_bytes(D); }
+int ribca_test_cell_attention_mx_pack(const uint16_t* W, int32_t ldw, int32_t D, uint8_t* img, void* stream) {
+  RIBCA_NEED_TABLE();
+  if (!cell_attention_mx_supported(D, kHeads, kTokens)) return fail("ribca_test_cell_attention_mx_pack: D must be 384");
+  if (!W || !img || ldw < 2 * D) return fail("ribca_test_cell_attention_mx_pack: NULL buffer or ldw < 2 D");
+  launch_cell_attention_mx_pack(W, ldw, D, img, (hipStream_t)stream);
+  RIBCA_FINISH();
+  return 0;
+}
+int ribca_test_cell_attention_mx(const uint16_t* z_ps, int32_t lda, const uint8_t* img, int32_t cells, int32_t D, const float* bias2,
+                                 const float* csum, const float* rowstat, uint16_t* out, int32_t ldo, void* stream) {
+  RIBCA_NEED_TABLE();
+  if (!cell_attention_mx_supported(D, kHeads, kTokens)) return fail("ribca_test_cell_attention_mx: D must be 384");
+  if (!z_ps || !img || !bias2 || !csum || !rowstat || !out || cells < 0 || lda < 2 * D || ldo < 2 * D)
+    return fail("ribca_test_cell_attention_mx: NULL buffer, cells < 0 or a row pitch below 2 D");
+  launch_cell_qkv_attention_mx(z_ps, lda, img, bias2, csum, reinterpret_cast<const float2*>(rowstat), out, ldo, cells, D,
+                               1.0f / sqrtf((float)(D / kHeads)), (hipStream_t)stream);
+  RIBCA_FINISH();
+  return 0;
+}
 int64_t ribca_test_cell_mlp_image_bytes(int32_t D) { if (table() == nullptr) return 0; return (int64_t)cell_mlp_image_bytes(D); }
 int ribca_test_cell_mlp(const uint16_t* xa, int32_t ldx, const uint16_t* projw, const uint16_t* fc1w, const uint16_t* fc2w, const float* projb,
                         const float* fc1c, const float* fc1b2, const float* fc2b, uint16_t* img_scratch, int32_t pack, uint16_t* z_ps,

@@ -1652,6 +1652,10 @@ class VitModel:
         self.probe_logit_delta = 0.0
         self.probe_predicted_dp = 0.0
         self.fast_ok = True
+        #: fast level of the handle (ribca_vit_set_fast_level): 2 = with the per-cell kernel's MX products, 1 = every other MX product only;
+        #: 0 once the probe has refused both (``fast_ok`` False).  predicted worst |dp| per level the probe tried: ``probe_level_dp``
+        self.fast_level = self._set_fast_level(2)
+        self.probe_level_dp: Dict[int, float] = {}
         if lib().ribca_mx_enabled(self.D) and os.environ.get("RIBCA_MARGIN_PROBE", "1") != "0":
             self._calibrate_margin()
 
@@ -1662,6 +1666,17 @@ class VitModel:
     PROBE_FACTOR = 3.0
     #: the fast (MX) forward is used only where the predicted worst |fast - full precision| stays below RECHECK_MARGIN / PROBE_DIVISOR
     PROBE_DIVISOR = 2.5
+
+    def _set_fast_level(self, level: int) -> int:
+        """select the handle's fast level; returns the level in effect (1 where the model has no per-cell MX kernel)"""
+        try:
+            fn = lib().ribca_vit_set_fast_level
+        except AttributeError:      # an A/B library older than the entry point (RIBCA_LIB): one fast level
+            return 1
+        got = int(fn(self._h, int(level)))
+        if got < 0:
+            check(1, "ribca_vit_set_fast_level")
+        return got
 
     def _calibrate_margin(self) -> None:
         """What the margin-gated re-evaluation rests on is |fast - full precision| staying well inside RECHECK_MARGIN for every cell (a cell
@@ -1678,22 +1693,34 @@ class VitModel:
         was 0.18 ... 2.75 x delta / 4 (tools/probe_vs_real.py, profiles/r6/probe_vs_real.txt), so the predicted worst case is
         PROBE_FACTOR x delta / 4 and a model is accepted while that stays below RECHECK_MARGIN / 2.5 = 4e-4 (delta <= 5.3e-4): every
         accepted case measured <= 2.5e-4.  A model beyond the bar runs EVERY product at three fp16 passes (``fast_ok`` False: the
-        precise forward for all cells, slower, nothing to re-evaluate).  Costs two 64-cell forwards per model."""
+        precise forward for all cells, slower, nothing to re-evaluate).  Costs two 64-cell forwards per model.
+
+        Levels: a model whose handle has the per-cell kernel's MX products (fast level 2) is probed with them first; if that misses the bar
+        the probe is repeated at level 1 (the per-cell kernel at three fp16 passes, fc1 / fc2 still MX) before the model is given up to the
+        precise forward -- one more 64-cell forward, only for a model that fails level 2."""
         g = torch.Generator().manual_seed(0x5249424341)
         u = torch.rand((self.PROBE_CELLS, self.C, PATCH, PATCH), generator=g, dtype=torch.float32) * 2.0 - 1.0
         x = torch.where(u > 0.1, u, torch.full_like(u, -1.0)).to(self.device)
         with torch.cuda.device(self.device):
             src = list(range(self.C))
-            fast = self._forward(x, src, chunk_cells=self.PROBE_CELLS, precise=False).double()
             full = self._forward(x, src, chunk_cells=self.PROBE_CELLS, precise=True).double()
-            self.probe_fast_minus_full = float((fast - full).abs().max().item())       # (informational: the probability form)
-            ok = (fast > 1e-30) & (full > 1e-30)
-            lf, lp = torch.log(fast.clamp_min(1e-300)), torch.log(full.clamp_min(1e-300))
+            lp = torch.log(full.clamp_min(1e-300))
             top = full.argmax(1, keepdim=True)
-            d = ((lf - lf.gather(1, top)) - (lp - lp.gather(1, top))).abs()
-            self.probe_logit_delta = float(d[ok].max().item()) if bool(ok.any()) else 0.0
-        self.probe_predicted_dp = self.PROBE_FACTOR * 0.25 * self.probe_logit_delta
-        self.fast_ok = self.probe_predicted_dp <= float(type(self).RECHECK_MARGIN) / self.PROBE_DIVISOR
+            for level in ((2, 1) if self.fast_level == 2 else (1,)):
+                self.fast_level = self._set_fast_level(level)
+                fast = self._forward(x, src, chunk_cells=self.PROBE_CELLS, precise=False, force_fast=True).double()
+                self.probe_fast_minus_full = float((fast - full).abs().max().item())       # (informational: the probability form)
+                ok = (fast > 1e-30) & (full > 1e-30)
+                lf = torch.log(fast.clamp_min(1e-300))
+                d = ((lf - lf.gather(1, top)) - (lp - lp.gather(1, top))).abs()
+                self.probe_logit_delta = float(d[ok].max().item()) if bool(ok.any()) else 0.0
+                self.probe_predicted_dp = self.PROBE_FACTOR * 0.25 * self.probe_logit_delta
+                self.probe_level_dp[level] = self.probe_predicted_dp
+                self.fast_ok = self.probe_predicted_dp <= float(type(self).RECHECK_MARGIN) / self.PROBE_DIVISOR
+                if self.fast_ok:
+                    break
+        if not self.fast_ok:
+            self.fast_level = 0
 
     @property
     def recheck_margin(self) -> float:

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Times the per-cell fused qkv + attention kernel (cell_attention.hip) on 1024 cells against the unfused pair, per D."""
+"""Times the per-cell fused qkv + attention kernel (cell_attention.hip; its MX form, cell_attention_mx.hip, where the width has one) on 1024
+cells against the unfused pair, per D."""
 import os
 import sys
 
@@ -36,8 +37,17 @@ for d in (384, 288, 144):
         check(lib().ribca_test_qkv_attention_fold(ptr(z), 2 * dp, ptr(w), 2 * dp, cells, d, dp, ptr(bias), ptr(csum), ptr(rs), ptr(q), ptr(k), ptr(vt), ptr(out),
                                                   2 * dp, stream_ptr()), "unfused")
 
+    forms = [("fused", fused), ("unfused qkv + attention", unfused)]
+    if lib().ribca_test_cell_attention_mx_image_bytes(d) > 0:      # the MX form of the fused kernel (cell_attention_mx.hip)
+        img = torch.zeros(lib().ribca_test_cell_attention_mx_image_bytes(d), dtype=torch.uint8, device=dev)
+        check(lib().ribca_test_cell_attention_mx_pack(ptr(w), 2 * dp, d, ptr(img), stream_ptr()), "pack")
+
+        def fused_mx():
+            check(lib().ribca_test_cell_attention_mx(ptr(z), 2 * dp, ptr(img), cells, d, ptr(bias), ptr(csum), ptr(rs), ptr(out), 2 * dp, stream_ptr()), "fused mx")
+
+        forms.insert(1, ("fused mx", fused_mx))
     res = {}
-    for name, fn in (("fused", fused), ("unfused qkv + attention", unfused)):
+    for name, fn in forms:
         fn()
         best = 1e9
         for _ in range(3):
