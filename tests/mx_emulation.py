@@ -68,6 +68,21 @@ def fp6_image(x16):
     return (q * scale[:, :, None]).reshape(r, k)
 
 
+def cell_gemm(a_hi16, a_lo, w_hi16, w_lo16):
+    """the three products of cell_attention_mx.hip in float64 (a_lo: x - hi, NOT yet quantised; K a multiple of 128).  That kernel's scale
+    blocks are the 32 values k = 128 S + 32 s + 8 g + j of one (row, S, g); hi_pos(128 S + 32 s + 8 g + j) = 128 S + 32 g + 8 s + j, so
+    under the column permutation hi_pos they are 32 consecutive columns and the product is `gemm` on operands permuted that way (a sum
+    over k does not care in which order the columns stand).  Rules as everywhere here: A lo e4m3 under sl = max(ef, 1) + 93 of the
+    block's largest |A hi|; A hi, W hi, W lo e2m3, each under its own max(ef, 1) + 110."""
+    k = a_hi16.shape[1]
+    assert k % 128 == 0 and w_hi16.shape[1] == k
+    src = np.empty(k, dtype=np.int64)
+    src[hi_pos(np.arange(k))] = np.arange(k)                 # the column that stands at position p
+    ah, wh, wl = a_hi16[:, src], w_hi16[:, src], w_lo16[:, src]
+    _, a_lo_q, _, _ = pack_act(ah, np.asarray(a_lo, dtype=np.float64)[:, src])
+    return gemm(ah, a_lo_q, wh, wl)
+
+
 def gemm(a_hi16, a_lo_q, w_hi16, w_lo16):
     """the three products of gemm_mx.hip in float64: Ah Wh^T + Al' Wh'^T + Ah' Wl'^T  (a_lo_q: the dequantised e4m3 lo of pack_act)"""
     ah, wh = a_hi16.astype(np.float64), w_hi16.astype(np.float64)

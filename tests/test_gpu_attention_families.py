@@ -1,6 +1,7 @@
 """The kernels that compute EVERY query row of the attention -- attention_kernel<64, 1> (the imputer's one-tile geometry, V transposed and
 key-permuted), attention_lds_kernel<HD, 7, 4> (101 tokens) behind the plain, the folded and the MX qkv product, and the fused per-cell
-kernel -- at every token count the imputer can ask for and under input families whose softmax is not flat.
+kernel in both forms (fp16x3 and, at D = 384, the MX products in its QKV phase) -- at every token count the imputer can ask for and under input
+families whose softmax is not flat.
 
 Families (tests/attention_families.py; each condition is asserted on the fp64 reference before a kernel result is looked at):
     gaussian      w ~ N(0, 1 / D): scores of order 1, the baseline of the token sweep
@@ -12,18 +13,23 @@ Families (tests/attention_families.py; each condition is asserted on the fp64 re
 Accuracy: the reference is fp64 torch on the decoded packed-split inputs.  No bound is fitted: for the unfused hooks it is derived per output
 element from the q / k / v operand buffers the hook hands back (attention_families.error_bound states every term), E_s < 0.5 is asserted,
 and so is that the bound stays below 5 % of the range of v.  The fused per-cell kernel keeps q and k on chip: its largest error may be at
-most twice that of ribca_test_qkv_attention_fold on the same inputs.  Every measured pair is appended to
+most twice that of ribca_test_qkv_attention_fold on the same inputs -- for its MX form (cell_attention_mx.hip, whose attention phase is a
+copy of that kernel's and whose pad keys 101 .. 111 are copies of the last token) twice that of the unfused MX pair,
+ribca_test_qkv_attention_mx, over all five families.  Every measured pair is appended to
 profiles/attention_families/gpu_tests_measured.log.
 
 Contract, same cases: every operand sits between guard bands (0x00 and 0x7C: bands intact, same bits), a second launch gives the same bits,
 columns D .. Dp - 1 of the written rows are zero, rows behind the cells * T written ones keep their prefill, the V^T pad keys stay zero, and
 (token sweep) 0x7E00 halves in the pad rows T .. 15 of the q and k buffers change no output bit.
 
-Largest error / bound per kernel over all its cases, MI355X (profiles/attention_families/gpu_tests_measured.log, 704 pairs):
+Largest error / bound per kernel over all its cases, MI355X (profiles/attention_families/gpu_tests_measured.log, 714 pairs):
     attention_kernel<64, 1>, T = 2 .. 16     0.87 (W_k = 0 at T = 2, where the bound is little more than the error of v as given);
                                              per family: gaussian 0.71, sharp 0.74, far_negative 0.64, far_positive 0.74, wk0 0.87
     attention_lds_kernel, plain qkv          0.07     folded qkv 0.06     MX qkv 0.22 (E_s <= 4.0e-3, bound <= 0.5 % of the range of v)
     fused per-cell kernel                    0.61 of twice the unfused error (its error 0.76 .. 1.22 times the unfused one)
+    fused per-cell kernel, MX form (D = 384) 0.56 of twice the unfused MX pair's error (its error 0.93 .. 1.11 times the pair's: gaussian
+                                             3.4e-5 / 3.3e-5, sharp 1.44e-3 / 1.29e-3, far_negative 3.6e-4 / 3.9e-4, far_positive 3.6e-4 /
+                                             3.6e-4, wk0 1.9e-5 / 2.0e-5 at 3 cells)
 E_s stays below 3e-4 on the fp16x3 producers, so every bound is below 0.04 % of the range of v there.  No defect was found; one term
 was missing from the bound as first derived (the 2^-25 absolute floor of the packed-split store, see error_bound)."""
 import math
@@ -106,7 +112,8 @@ def _reference(f, cells, t):
 
 # ---------------------------------------------------------------------------------------------------------------- launches
 def _launch(kind, f, cells, t, dev, band, nan_pads=False, relaunch=False):
-    """one hook call with every operand inside an arena of `band` bytes: (arena, {q, k, vt, out}); kind: tokens / plain / fold / mx / cell"""
+    """one hook call with every operand inside an arena of `band` bytes: (arena, {q, k, vt, out}); kind: tokens / plain / fold / mx / cell / cellmx
+    (cellmx: the per-cell MX kernel, whose stage image is packed from f["w"] inside the arena first and returned as "img")"""
     check, lib, ptr, stream_ptr = _api()
     d, dp, heads = f["d"], f["dp"], f["heads"]
     hd = d // heads
@@ -116,7 +123,7 @@ def _launch(kind, f, cells, t, dev, band, nan_pads=False, relaunch=False):
     csum = ar.put(f["csum"]) if f["fold"] else None
     rs = ar.put(f["rs"][:m]) if f["fold"] else None
     res = {}
-    if kind != "cell":
+    if kind not in ("cell", "cellmx"):
         res["q"], res["k"] = ar.zeros((cells, heads, tp, 2 * hdq), torch.int16), ar.zeros((cells, heads, tp, 2 * hdq), torch.int16)
         v_elems = lib.ribca_test_attention_v_elems(d, heads, t, cells)
         assert v_elems > 0
@@ -133,6 +140,10 @@ def _launch(kind, f, cells, t, dev, band, nan_pads=False, relaunch=False):
         a_hi, a_l8, a_sc = ar.zeros((m, kz), torch.int16), ar.zeros((m, kz), torch.uint8), ar.zeros((m, kz // 32), torch.uint8)
         wh = ar.zeros((lib.ribca_test_mx_weight_bytes(3 * d, kz, 0),), torch.uint8)
         wx = ar.zeros((lib.ribca_test_mx_weight_bytes(3 * d, kz, 1),), torch.uint8)
+    if kind == "cellmx":
+        nimg = lib.ribca_test_cell_attention_mx_image_bytes(d)
+        assert nimg > 0
+        res["img"] = ar.empty((nimg,), torch.uint8)      # holds the band's fill: the pack kernel writes every byte
 
     def call():
         if kind == "tokens":
@@ -148,6 +159,10 @@ def _launch(kind, f, cells, t, dev, band, nan_pads=False, relaunch=False):
         elif kind == "mx":
             st = lib.ribca_test_qkv_attention_mx(ptr(rows), 2 * dp, ptr(w), 2 * dp, cells, d, dp, ptr(bias), ptr(csum), ptr(rs), ptr(a_hi), ptr(a_l8),
                                                  ptr(a_sc), ptr(wh), ptr(wx), ptr(res["q"]), ptr(res["k"]), ptr(res["vt"]), ptr(out), 2 * dp, stream_ptr())
+        elif kind == "cellmx":
+            check(lib.ribca_test_cell_attention_mx_pack(ptr(w), 2 * dp, d, ptr(res["img"]), stream_ptr()), "cellmx pack")
+            st = lib.ribca_test_cell_attention_mx(ptr(rows), 2 * dp, ptr(res["img"]), cells, d, ptr(bias), ptr(csum), ptr(rs), ptr(out), 2 * dp,
+                                                  stream_ptr())
         else:
             st = lib.ribca_test_cell_attention(ptr(rows), 2 * dp, ptr(w), 2 * dp, cells, d, ptr(bias), ptr(csum), ptr(rs), ptr(out), 2 * dp, stream_ptr())
         check(st, kind)
@@ -317,5 +332,24 @@ def test_cell_attention_families(dev, d, family):
         assert torch.isfinite(got).all()
         e_new, e_old = (got - o).abs().max().item(), (old - o).abs().max().item()
         _log(f"cell D={d} {family} T={WIDE_T} cells={cells}: error {e_new:.3e} unfused {e_old:.3e} "
+             f"(error / (2 x unfused) {e_new / (2.0 * e_old) if e_old > 0 else float('nan'):.3f})")
+        assert e_new <= 2.0 * e_old, (cells, e_new, e_old)
+
+
+@pytest.mark.parametrize("family", af.FAMILIES)
+def test_cell_attention_mx_families(dev, family):
+    """the fused per-cell kernel with the MX products in its QKV phase (D = 384; its pad keys 101 .. 111 are copies of the last token, not
+    zeros): the contract, and at most twice the error of the unfused MX pair on the same inputs against the same fp64 reference"""
+    d = 384
+    f = _case(d, WIDE_HEADS, 1, family, max(WIDE_CELLS) * WIDE_T, dev)
+    for cells in WIDE_CELLS:
+        m = cells * WIDE_T
+        o = af.merge_heads(_reference(f, cells, WIDE_T)[3])
+        res = _run_contract("cellmx", f, cells, WIDE_T, dev, sweep=False)
+        _, unfused = _launch("mx", f, cells, WIDE_T, dev, 0x00)
+        got, old = ps_decode(res["out"][:m], d), ps_decode(unfused["out"][:m], d)
+        assert torch.isfinite(got).all()
+        e_new, e_old = (got - o).abs().max().item(), (old - o).abs().max().item()
+        _log(f"cellmx D={d} {family} T={WIDE_T} cells={cells}: error {e_new:.3e} unfused MX pair {e_old:.3e} "
              f"(error / (2 x unfused) {e_new / (2.0 * e_old) if e_old > 0 else float('nan'):.3f})")
         assert e_new <= 2.0 * e_old, (cells, e_new, e_old)

@@ -5,7 +5,13 @@ one child process per setting -- the switch is what this test is about).  On 8 c
   RECHECK_MARGIN / PROBE_DIVISOR (ops.VitModel._calibrate_margin): what the margin-gated re-evaluation of Annotator.predict rests on;
 * the precise forward (ribca_vit_forward_precise) is bit-identical in both: precise() clears the flag, the fp16x3 kernel is untouched, and
   RIBCA_CELL_ATTN_MX=0 is the path of the tree before this kernel existed;
-* classifiers without a per-cell MX kernel (every width but 384) have bit-identical fast forwards as well, and report fast level 1."""
+* classifiers without a per-cell MX kernel (every width but 384) have bit-identical fast forwards as well, and report fast level 1;
+* the level switch is stateless (ribca_vit_set_fast_level on the RIBCA_CELL_ATTN_MX=1 handles, after their forwards): at level 1 the fast
+  forward of the 384-wide handle has the bits of the RIBCA_CELL_ATTN_MX=0 process -- the forward of the tree before the per-cell MX kernel --
+  back at level 2 it has the bits of the first level-2 forward, and the precise forward has the same bits at either level.
+
+Measured on MI355X: the 384-wide model ends at level 2 (predicted worst |dp| 3.1e-4; 2.5e-4 at level 1 in the other process), its fast
+forwards under the two switches differ by 6.0e-6 on the 8 cells, every other width by 0."""
 import json
 import os
 import subprocess
@@ -34,6 +40,14 @@ for name, (d, c, k) in synth.VIT_CONFIGS.items():
     out[name] = {"D": d, "fast": fast.double().tolist(), "fast_sha": hashlib.sha256(fast.numpy().tobytes()).hexdigest(),
                  "precise_sha": hashlib.sha256(full.numpy().tobytes()).hexdigest(), "fast_level": model.fast_level, "uses_mx": model.uses_mx,
                  "probe_level_dp": model.probe_level_dp, "bar": float(ops.VitModel.RECHECK_MARGIN) / ops.VitModel.PROBE_DIVISOR}
+    if model.fast_level == 2:      # the switch, after the forwards: down to level 1, up again
+        sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+        out[name]["down"] = model._set_fast_level(1)
+        out[name]["fast_sha_level1"] = sha(model._forward(x, list(range(c)), chunk_cells=8, precise=False))
+        out[name]["precise_sha_level1"] = sha(model._forward(x, list(range(c)), chunk_cells=8, precise=True))
+        out[name]["up"] = model._set_fast_level(2)
+        out[name]["fast_sha_level2_again"] = sha(model._forward(x, list(range(c)), chunk_cells=8, precise=False))
+        out[name]["precise_sha_level2_again"] = sha(model._forward(x, list(range(c)), chunk_cells=8, precise=True))
 print("RESULT " + json.dumps(out))
 """ % ROOT
 
@@ -62,3 +76,8 @@ def test_forward_with_and_without_the_per_cell_mx_products():
             assert b["fast_level"] <= 1 and a["fast_sha"] == b["fast_sha"], name
         else:
             assert b["uses_mx"] and b["fast_level"] == 2, (name, b["fast_level"], b["probe_level_dp"])
+            assert (b["down"], b["up"]) == (1, 2), name
+            assert b["fast_sha"] != a["fast_sha"], name                       # (the two levels differ on these cells: the next lines say something)
+            assert b["fast_sha_level1"] == a["fast_sha"], name                # level 1 on a level-2 handle: the pre-MX forward, bit for bit
+            assert b["fast_sha_level2_again"] == b["fast_sha"], name          # and back: no state left behind
+            assert b["precise_sha_level1"] == b["precise_sha"] == b["precise_sha_level2_again"], name

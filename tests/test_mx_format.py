@@ -4,6 +4,7 @@ invariants, and the scheme's error against the exact product -- the bound the GP
 import numpy as np
 import pytest
 
+import cell_mx_families as cf
 import mx_emulation as mx
 
 
@@ -110,3 +111,76 @@ def test_scheme_error_against_exact_product(m, n, k):
     # hi * hi alone is 2^-11 class per term (a random walk over k): the corrections buy more than a decimal digit
     rel_hh = (np.abs(a_hi.astype(np.float64) @ w_hi.astype(np.float64).T - exact) / scale).max()
     assert rel_hh > 8 * rel
+
+
+def _cell_gemm_literal(a_hi16, a_lo, w_hi16, w_lo16):
+    """the per-cell kernel's three products stated block by block: for every (row, 128-k step S, lane group g) the 32 values
+    k = 128 S + 32 s + 8 g + j (s = 0 .. 3, j = 0 .. 7) share one scale -- no permutation, no reshape"""
+    def ef_of(v16):
+        return max(int(mx.f16_exp_field(np.abs(v16)).max()), 1)
+
+    m, kk = a_hi16.shape
+    n = w_hi16.shape[0]
+    a_lo_q, a_hi_q = np.zeros((m, kk)), np.zeros((m, kk))
+    w_hi_q, w_lo_q = np.zeros((n, kk)), np.zeros((n, kk))
+    for S in range(kk // 128):
+        for g in range(4):
+            k = np.array([128 * S + 32 * s + 8 * g + j for s in range(4) for j in range(8)])
+            for r in range(m):
+                ef = ef_of(a_hi16[r, k])
+                sl, sh = 2.0 ** (ef + 93 - 127), 2.0 ** (ef + 110 - 127)
+                a_lo_q[r, k] = mx.e4m3_round(a_lo[r, k] / sl) * sl
+                a_hi_q[r, k] = mx.e2m3_round(a_hi16[r, k].astype(np.float64) / sh) * sh
+            for c in range(n):
+                sh, sl = 2.0 ** (ef_of(w_hi16[c, k]) + 110 - 127), 2.0 ** (ef_of(w_lo16[c, k]) + 110 - 127)
+                w_hi_q[c, k] = mx.e2m3_round(w_hi16[c, k].astype(np.float64) / sh) * sh
+                w_lo_q[c, k] = mx.e2m3_round(w_lo16[c, k].astype(np.float64) / sl) * sl
+    return a_hi16.astype(np.float64) @ w_hi16.astype(np.float64).T + a_lo_q @ w_hi_q.T + a_hi_q @ w_lo_q.T
+
+
+def test_cell_gemm_is_the_literal_block_statement():
+    """mx.cell_gemm (gemm under the column permutation hi_pos) against loops over (row, S, g) that gather k = 128 S + 32 s + 8 g + j: 7 rows
+    x 48 columns of W x K = 384, rows with an outlier per 8 k, an all-zero 128-k step and fp16-subnormal hi among them.  Both sides are the
+    same float64 sums of the same terms in another order: 1e-12 of sum |a w| is 10^4 roundings' worth."""
+    rng = np.random.default_rng(23)
+    a = (rng.standard_normal((7, 384)) * np.exp(rng.standard_normal((7, 1)))).astype(np.float32)
+    a[1, 5::8] *= 4096.0
+    a[2, 128:256] = 0.0
+    a[3] *= 1e-6
+    a[4, [5, 13, 21, 29]] *= 4096.0
+    w = (rng.standard_normal((48, 384)) / np.sqrt(384) * np.exp(rng.standard_normal((1, 384)))).astype(np.float32)
+    a_hi, a_lo16 = cf.split_host(a)
+    w_hi, w_lo16 = cf.split_host(w)
+    a_lo = a_lo16.astype(np.float64)
+    got, want = mx.cell_gemm(a_hi, a_lo, w_hi, w_lo16), _cell_gemm_literal(a_hi, a_lo, w_hi, w_lo16)
+    scale = np.abs(a.astype(np.float64)) @ np.abs(w.astype(np.float64)).T
+    assert np.all(np.abs(got - want) <= 1e-12 * scale), (np.abs(got - want) / scale).max()
+    # the grouping matters: with 32 consecutive k per block (gemm_mx.hip) the same operands give another product
+    _, lo_q, _, _ = mx.pack_act(a_hi, a_lo)
+    other = mx.gemm(a_hi, lo_q, w_hi, w_lo16)
+    assert (np.abs(other - want) / scale).max() > 1e-9
+
+
+@pytest.mark.parametrize("family", cf.ROW_FAMILIES)
+def test_cell_families_never_saturate_e4m3(family):
+    """the token rows of tests/test_gpu_cell_attention_mx.py: under the scale blocks of either kernel |A lo / scale| <= 256 (the hardware
+    conversion never reaches e4m3's 448), and edge_rows has what it is there for"""
+    m = 3 * cf.T
+    hi, lo = cf.split_host(cf.rows_f32(family, m).numpy())
+    for cell_blocks in (True, False):
+        q, ef = cf.lo_codes(hi, lo, cell_blocks)
+        assert np.abs(q).max() <= 256.0, (family, cell_blocks, np.abs(q).max())
+    if family == "edge_rows":
+        q, ef = cf.lo_codes(hi, lo, True)                       # ef: [m][12], block 4 S + g
+        assert np.all(ef[1::16, 4:8] == 0) and np.all(hi[1::16, 128:256] == 0)      # the clamp max(ef, 1) is taken in every block of S = 1
+        sub = (np.abs(hi[2::16]) < 2.0 ** -14) & (hi[2::16] != 0)
+        assert sub.all(axis=1).any() and (sub.any(axis=1) & ~sub.all(axis=1)).any()   # rows subnormal throughout, and rows that mix
+        assert (np.abs(hi) == 65504).any()                      # saturated outliers: lo = 0 there
+        assert np.all(lo[np.abs(hi) == 65504] == 0)
+        # the 16 tokens of a wave (rows 16 w .. 16 w + 15 of a cell) do not share a scale byte: at least 4 distinct ones in every wave's block 0
+        for c in range(3):
+            for wv in range(6):
+                assert len(set(ef[c * cf.T + 16 * wv:c * cf.T + 16 * wv + 16, 0].tolist())) >= 4, (c, wv)
+        # rows 0 and T - 1 of cell 0 are the rows of `uniform`
+        u_hi, u_lo = cf.split_host(cf.rows_f32("uniform", m).numpy())
+        assert np.array_equal(hi[[0, cf.T - 1]], u_hi[[0, cf.T - 1]]) and np.array_equal(lo[[0, cf.T - 1]], u_lo[[0, cf.T - 1]])
