@@ -19,7 +19,7 @@ LIB_TEST = os.path.join(HERE, "libribca_hip_test.so")
 TEST_SOURCES = ["ribca_test_api.hip"]
 EXPORTS = os.path.join(CSRC, "exports.map")
 SOURCES = ["gemm_split16.hip", "gemm_duo.hip", "gemm_mx.hip", "attention.hip", "cell_attention.hip", "cell_attention_mx.hip", "cell_mlp.hip", "cls_attention.hip", "vit_misc.hip", "preprocess.hip", "preprocess_scaled.hip", "vote.hip", "colorize.hip", "knn.hip", "umap.hip", "hdbscan.hip", "regions.hip", "spectral.hip", "scatter.hip", "celltype_stats.hip", "perm.hip", "enrichment.hip", "autocorr.hip", "local_autocorr.hip", "cooccurrence.hip", "nearest.hip", "contact.hip", "morphology.hip", "intensities.hip", "expand.hip", "components.hip", "outlines.hip", "overlap.hip", "localization.hip", "colocalization.hip", "normalize.hip", "ribca_api.hip"]
-HEADERS = ["ribca_common.h", "ribca_kernels.h", "ribca_scratch.h", "ribca_perm.h", "ribca_rowtable.h", "ribca_cellbox.h", "ribca_status.h", "ribca_internal.h", "gemm_epi.h", os.path.join("..", "..", "include", "ribca_hip.h"),
+HEADERS = ["ribca_common.h", "ribca_kernels.h", "ribca_scratch.h", "ribca_perm.h", "ribca_rowtable.h", "ribca_cellbox.h", "ribca_status.h", "ribca_internal.h", "gemm_epi.h", "attn_core.h", os.path.join("..", "..", "include", "ribca_hip.h"),
            os.path.join("..", "..", "include", "ribca_hip_test.h")]
 # -fvisibility=hidden: the dynamic symbol table of either library is what its header declares between `#pragma GCC visibility push(default)` and
 # `pop` -- no C++ launcher, kernel stub or template instantiation is exported (tests/test_abi.py compares the full `nm -D` list with the header)

@@ -17,6 +17,7 @@
 // All three products use the fp16x3 split (ribca_common.h).  Q is pre-scaled by hd^-0.5 by the producer.
 #include <cstdlib>
 
+#include "attn_core.h"
 #include "ribca_common.h"
 #include "ribca_kernels.h"
 
@@ -82,48 +83,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const uint16_t* __restri
         s[kt] = mfma_f16(khi[kt][ks], qhi[ks], s[kt]);
       }
     }
-    // keys >= T (only possible in the last tile) are padding
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (16 * (NT - 1) + 4 * g + r >= T) s[NT - 1][r] = -INFINITY;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kt][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // exp(s - mx) = exp2(s log2e - mx log2e): one packed fma per two scores in front of v_exp_f32 (cell_attention.hip does the same)
-    const f32x2v l2 = {1.44269504089f, 1.44269504089f}, moff = {-mx * 1.44269504089f, -mx * 1.44269504089f};
-    f32x2v sum2 = {0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-      const f32x2v a0 = fma2(f32x2v{s[kt][0], s[kt][1]}, l2, moff);
-      const f32x2v a1 = fma2(f32x2v{s[kt][2], s[kt][3]}, l2, moff);
-      const f32x2v e0 = {__builtin_amdgcn_exp2f(a0.x), __builtin_amdgcn_exp2f(a0.y)}, e1 = {__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)};
-      s[kt] = f32x4{e0.x, e0.y, e1.x, e1.y};
-      sum2 += e0;
-      sum2 += e1;
-    }
-    float sum = sum2.x + sum2.y;
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.0f / sum;
-    if (NT & 1) s[NT] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // P fragments: k-step t covers key tiles 2t (elements 0..3) and 2t+1 (elements 4..7)
+    // keys >= T (only possible in the last tile) are padding; P fragments: k-step t covers key tiles 2t (elements 0..3) and 2t+1 (elements 4..7)
     f16x8 phi[KST], plo[KST];
-#pragma unroll
-    for (int t = 0; t < KST; ++t) {
-      const f32x2v inv2 = {inv, inv};
-      const f32x2v pa0 = f32x2v{s[2 * t][0], s[2 * t][1]} * inv2, pa1 = f32x2v{s[2 * t][2], s[2 * t][3]} * inv2;
-      const f32x2v pb0 = f32x2v{s[2 * t + 1][0], s[2 * t + 1][1]} * inv2, pb1 = f32x2v{s[2 * t + 1][2], s[2 * t + 1][3]} * inv2;
-      const float pa[4] = {pa0.x, pa0.y, pa1.x, pa1.y}, pb[4] = {pb0.x, pb0.y, pb1.x, pb1.y};
-      uint2 ha, la, hb, lb;
-      split4_unit(pa, ha, la);      // probabilities: inside the fp16 range by construction
-      split4_unit(pb, hb, lb);
-      phi[t] = __builtin_bit_cast(f16x8, uint4{ha.x, ha.y, hb.x, hb.y});
-      plo[t] = __builtin_bit_cast(f16x8, uint4{la.x, la.y, lb.x, lb.y});
-    }
+    softmax_keys_split<NT>(s, T, g, phi, plo);
     const int qtok = qt * 16 + r16;
     uint16_t* orow = out + ((size_t)cell * T + qtok) * ldo;
 #pragma unroll
@@ -164,11 +126,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const uint16_t* __restri
 // 16-column block of 16-bit elements column-major (lane 4q + p supplies the address of row q, columns 4p .. 4p + 3; lane i receives
 // column i of the four rows): one read per key quartet, hi and lo halves separately = 4 reads per (dt, t) where the V^T form had two
 // 16-byte ones.  Rows 101 .. 111 lie beyond the staging descriptor's range and arrive as zeros (never fetched), rows 112 .. 127 are zeroed in LDS: their P is exactly 0.
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
-__device__ __forceinline__ f16x4 lds_read_tr16(const char* p) {
-  return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p)));
-}
 template <int HD, int NT, int WPP>
 __global__ __launch_bounds__(64 * WPP) void attention_lds_kernel(const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K,
                                                                  const uint16_t* __restrict__ V, uint16_t* __restrict__ out, int ldo,
@@ -258,46 +215,8 @@ __global__ __launch_bounds__(64 * WPP) void attention_lds_kernel(const uint16_t*
         s[kt] = mfma_f16(kh, qhi[ks], s[kt]);
       }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (16 * (NT - 1) + 4 * g + r >= T) s[NT - 1][r] = -INFINITY;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kt][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // exp(s - mx) = exp2(s log2e - mx log2e): one packed fma per two scores in front of v_exp_f32 (cell_attention.hip does the same)
-    const f32x2v l2 = {1.44269504089f, 1.44269504089f}, moff = {-mx * 1.44269504089f, -mx * 1.44269504089f};
-    f32x2v sum2 = {0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-      const f32x2v a0 = fma2(f32x2v{s[kt][0], s[kt][1]}, l2, moff);
-      const f32x2v a1 = fma2(f32x2v{s[kt][2], s[kt][3]}, l2, moff);
-      const f32x2v e0 = {__builtin_amdgcn_exp2f(a0.x), __builtin_amdgcn_exp2f(a0.y)}, e1 = {__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)};
-      s[kt] = f32x4{e0.x, e0.y, e1.x, e1.y};
-      sum2 += e0;
-      sum2 += e1;
-    }
-    float sum = sum2.x + sum2.y;
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.0f / sum;
-    if (NT & 1) s[NT] = f32x4{0.f, 0.f, 0.f, 0.f};
     f16x8 phi[KST], plo[KST];
-#pragma unroll
-    for (int t = 0; t < KST; ++t) {
-      const f32x2v inv2 = {inv, inv};
-      const f32x2v pa0 = f32x2v{s[2 * t][0], s[2 * t][1]} * inv2, pa1 = f32x2v{s[2 * t][2], s[2 * t][3]} * inv2;
-      const f32x2v pb0 = f32x2v{s[2 * t + 1][0], s[2 * t + 1][1]} * inv2, pb1 = f32x2v{s[2 * t + 1][2], s[2 * t + 1][3]} * inv2;
-      const float pa[4] = {pa0.x, pa0.y, pa1.x, pa1.y}, pb[4] = {pb0.x, pb0.y, pb1.x, pb1.y};
-      uint2 ha, la, hb, lb;
-      split4_unit(pa, ha, la);      // probabilities: inside the fp16 range by construction
-      split4_unit(pb, hb, lb);
-      phi[t] = __builtin_bit_cast(f16x8, uint4{ha.x, ha.y, hb.x, hb.y});
-      plo[t] = __builtin_bit_cast(f16x8, uint4{la.x, la.y, lb.x, lb.y});
-    }
+    softmax_keys_split<NT>(s, T, g, phi, plo);
     const int qtok = qt * 16 + r16;
     uint16_t* orow = out + ((size_t)cell * T + qtok) * ldo;
 #pragma unroll

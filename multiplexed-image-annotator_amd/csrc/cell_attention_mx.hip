@@ -7,8 +7,10 @@
 //   90 bytes per lane, tile and 128 k read back from the ring instead of 128 (4 hi fragments, 24 bytes of fp6 lo', 2 scale bytes), 23 KB
 //   per 128-deep stage of four tiles through the LDS-DMA instead of 32 KB.
 //
-// What differs from cell_attention.hip (everything else -- the grid, the folded LayerNorm, the k / v publication and the attention phase --
-// is that file's code, duplicated here so that the precise kernel's instruction stream stays what it was):
+// Shared with cell_attention.hip through attn_core.h: the softmax (softmax_keys_split), the transposed V read and the LDS map behind the
+// ring.  The grid, the once-per-cell staging, the loader wave's loop, the folded LayerNorm, the k / v publication and the loops of the
+// attention phase are that file's code, repeated here: moved into shared function templates they compiled to a slower fp16x3 kernel at
+// D = 288 (docs/history.md, "One softmax, one LDS map"), and a tail that only one of the two kernels calls would be no gain.  What differs:
 // * The token rows stay in registers for the whole cell, so their images are built ONCE per cell: per 128 k the lane (token, g) holds
 //   k = 32 s + 8 g + j (s = sub-step 0..3, j = 0..7) -- 32 values that form ONE scale block (a permutation of k inside 128 that the pack
 //   kernel applies to W as well: the block of lane g IS the 32 "consecutive" k' = 32 g + 8 s + j the fp6 operand wants in one lane).
@@ -26,6 +28,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "attn_core.h"
 #include "gemm_epi.h"
 #include "ribca_common.h"
 #include "ribca_kernels.h"
@@ -34,15 +37,10 @@ namespace ribca {
 
 namespace {
 
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4c;
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4c;
 typedef int i32x8m __attribute__((ext_vector_type(8)));
 typedef unsigned u32x6m __attribute__((ext_vector_type(6)));
 typedef _Float16 h32m __attribute__((ext_vector_type(32)));
 typedef short s16x2m __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f16x4c lds_read_tr16c(const char* p) {
-  return __builtin_bit_cast(f16x4c, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4c __attribute__((address_space(3)))*)(p)));
-}
 
 template <int... Is, class F>
 __device__ __forceinline__ void sfor_impl(std::integer_sequence<int, Is...>, F&& f) {
@@ -52,8 +50,6 @@ template <int N, class F>
 __device__ __forceinline__ void sfor(F&& f) {
   sfor_impl(std::make_integer_sequence<int, N>{}, f);
 }
-
-constexpr int kTP = 112, kVRows = 128;
 
 template <int D, int HD> struct CellMxGeom {
   static constexpr int NK = D / 32;            // 32-deep sub-steps: the token rows' fragments
@@ -67,18 +63,11 @@ template <int D, int HD> struct CellMxGeom {
   static constexpr int WSTAGE = OFF_SC + 1024;              // 23 KB
   static constexpr int GPL = WSTAGE / 1024;                 // DMA instructions (1 KB each) per stage
   static constexpr int GROUPS = D / GD;
-  static constexpr int HPG = GD / HD;          // heads per group
-  static constexpr int KIMG = kTP * ROWB;      // one head's K image: 112 tokens x 128 B (fragment order, swizzled like a GEMM tile)
-  static constexpr int VROWB = 4 * GD;         // 256 B: the group's dims packed-split
-  static constexpr int VIMG = kVRows * VROWB + 64;
-  static constexpr int CB = 2 * 3 * D * 4;     // column sums and folded bias of the whole qkv product
   static constexpr int RING = 3;               // stage s + 1 is written while stage s is read; the slot of s - 1 is free by then
-  static constexpr int OFF_K = RING * WSTAGE;
-  static constexpr int OFF_V = OFF_K + HPG * KIMG;
-  static constexpr int OFF_CB = OFF_V + (VIMG + 15) / 16 * 16;
-  static constexpr int LDS = OFF_CB + CB;
+  using Map = CellLdsMap<D, HD, GD, RING * WSTAGE>;      // K images, V image, column sums and bias behind the ring (attn_core.h)
+  static constexpr int LDS = Map::LDS;
   static constexpr size_t IMAGE = (size_t)GROUPS * SPG * WSTAGE;
-  static_assert(D % 128 == 0 && HD == 32 && D % GD == 0 && HPG % 2 == 0, "geometry: whole 128-deep steps, two heads of 32 per group");
+  static_assert(D % 128 == 0 && HD == 32 && D % GD == 0 && Map::HPG % 2 == 0, "geometry: whole 128-deep steps, two heads of 32 per group");
   static_assert(WSTAGE % 1024 == 0 && 2 * GPL <= 63, "whole DMA pieces; two stages in flight within the 6-bit vmcnt");
   static_assert(LDS <= 160 * 1024, "LDS of a CU");
 };
@@ -134,7 +123,8 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
                                                                     const float2* __restrict__ rowstat, uint16_t* __restrict__ out, int ldo, int T,
                                                                     float scale) {
   using G = CellMxGeom<D, HD>;
-  constexpr int NK = G::NK, NS = G::NS, SPG = G::SPG, GROUPS = G::GROUPS, HPG = G::HPG, kRing = G::RING, kGroupDims = G::GD, NTP = G::NTP,
+  using M = typename G::Map;
+  constexpr int NK = G::NK, NS = G::NS, SPG = G::SPG, GROUPS = G::GROUPS, HPG = M::HPG, kRing = G::RING, kGroupDims = G::GD, NTP = G::NTP,
                 kWStage = G::WSTAGE;
   constexpr int NTILES = 3 * NTP;              // accumulator tiles per wave and group: q | k | v
   constexpr int TOTAL = GROUPS * SPG;          // ring steps of the whole cell
@@ -147,10 +137,10 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
 
   // ---- once per cell: column sums / folded bias of all 3 D outputs, zero rows behind V
   for (int i = tid; i < 3 * D / 4; i += 512) {
-    reinterpret_cast<float4*>(smem + G::OFF_CB)[i] = reinterpret_cast<const float4*>(csum)[i];
-    reinterpret_cast<float4*>(smem + G::OFF_CB + 3 * D * 4)[i] = reinterpret_cast<const float4*>(bias2)[i];
+    reinterpret_cast<float4*>(smem + M::OFF_CB)[i] = reinterpret_cast<const float4*>(csum)[i];
+    reinterpret_cast<float4*>(smem + M::OFF_CB + 3 * D * 4)[i] = reinterpret_cast<const float4*>(bias2)[i];
   }
-  for (int o = kTP * G::VROWB + tid * 16; o < G::VIMG; o += 512 * 16) *reinterpret_cast<uint4*>(smem + G::OFF_V + o) = uint4{0u, 0u, 0u, 0u};
+  for (int o = kTP * M::VROWB + tid * 16; o < M::VIMG; o += 512 * 16) *reinterpret_cast<uint4*>(smem + M::OFF_V + o) = uint4{0u, 0u, 0u, 0u};
   __syncthreads();
 
   if (wave == 7) {
@@ -235,7 +225,7 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
   }
   const float2 rs = rowstat[(size_t)cell * T + trow];
   const float rstd = rs.x, nm = -rs.y * rs.x;
-  const char* cb = smem + G::OFF_CB;
+  const char* cb = smem + M::OFF_CB;
   uint16_t* orow = out + ((size_t)cell * T + tok) * ldo;
   const int k_wr = lds_off(tok, 2 * g);                        // this lane's 32 bytes (hi | lo) of a K image row
   constexpr int KST = 4, NT = 7;
@@ -331,12 +321,12 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
       qlo[h] = __builtin_bit_cast(f16x8, uint4{l0.x, l0.y, l1.x, l1.y});
       split4(ka, h0, l0);
       split4(kb, h1, l1);
-      char* kimg = smem + G::OFF_K + h * G::KIMG;
+      char* kimg = smem + M::OFF_K + h * M::KIMG;
       *reinterpret_cast<uint4*>(kimg + k_wr) = uint4{h0.x, h0.y, h1.x, h1.y};
       *reinterpret_cast<uint4*>(kimg + (k_wr ^ 16)) = uint4{l0.x, l0.y, l1.x, l1.y};
     }
     {
-      uint16_t* vrow = reinterpret_cast<uint16_t*>(smem + G::OFF_V + tok * G::VROWB);
+      uint16_t* vrow = reinterpret_cast<uint16_t*>(smem + M::OFF_V + tok * M::VROWB);
 #pragma unroll
       for (int j = 0; j < NTP; ++j) {
         const float v4[4] = {acc[2 * NTP + j][0], acc[2 * NTP + j][1], acc[2 * NTP + j][2], acc[2 * NTP + j][3]};
@@ -354,7 +344,7 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
     // VALU of the other, and the two P V products interleave (a wave is in-order: without a second independent chain every
     // exp / split waits behind the MFMAs that feed it)
     constexpr int DT = (HD + 15) / 16;
-    const char* vimg = smem + G::OFF_V;
+    const char* vimg = smem + M::OFF_V;
 #pragma unroll
     for (int hp = 0; hp < HPG; hp += 2) {
       f32x4 s[2][2 * KST];
@@ -363,7 +353,7 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
         const int ko = lds_off(16 * kt + r16, 2 * g);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const char* kimg = smem + G::OFF_K + (hp + e) * G::KIMG;
+          const char* kimg = smem + M::OFF_K + (hp + e) * M::KIMG;
           const f16x8 kh = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(kimg + ko));
           const f16x8 kl = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(kimg + (ko ^ 16)));
           s[e][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -374,48 +364,7 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
       }
       f16x8 phi[2][KST], plo[2][KST];
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (16 * (NT - 1) + 4 * g + r >= T) s[e][NT - 1][r] = -INFINITY;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[e][kt][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // exp(s - mx) = exp2(s log2e - mx log2e): ONE packed fma per two scores in front of v_exp_f32 (a subtract and a multiply per
-        // score before); probabilities are normalised two at a time and split without the fp16 range clamp (they lie in [0, 1])
-        const f32x2v l2 = {1.44269504089f, 1.44269504089f}, moff = {-mx * 1.44269504089f, -mx * 1.44269504089f};
-        f32x2v sum2 = {0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt) {
-          const f32x2v a0 = fma2(f32x2v{s[e][kt][0], s[e][kt][1]}, l2, moff);
-          const f32x2v a1 = fma2(f32x2v{s[e][kt][2], s[e][kt][3]}, l2, moff);
-          const f32x2v e0 = {__builtin_amdgcn_exp2f(a0.x), __builtin_amdgcn_exp2f(a0.y)}, e1 = {__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)};
-          s[e][kt] = f32x4{e0.x, e0.y, e1.x, e1.y};
-          sum2 += e0;
-          sum2 += e1;
-        }
-        float sum = sum2.x + sum2.y;
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
-        const f32x2v inv2 = {inv, inv};
-        s[e][NT] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < KST; ++t) {
-          const f32x2v pa0 = f32x2v{s[e][2 * t][0], s[e][2 * t][1]} * inv2, pa1 = f32x2v{s[e][2 * t][2], s[e][2 * t][3]} * inv2;
-          const f32x2v pb0 = f32x2v{s[e][2 * t + 1][0], s[e][2 * t + 1][1]} * inv2, pb1 = f32x2v{s[e][2 * t + 1][2], s[e][2 * t + 1][3]} * inv2;
-          const float pa[4] = {pa0.x, pa0.y, pa1.x, pa1.y}, pb[4] = {pb0.x, pb0.y, pb1.x, pb1.y};
-          uint2 ha, la, hb, lb;
-          split4_unit(pa, ha, la);
-          split4_unit(pb, hb, lb);
-          phi[e][t] = __builtin_bit_cast(f16x8, uint4{ha.x, ha.y, hb.x, hb.y});
-          plo[e][t] = __builtin_bit_cast(f16x8, uint4{la.x, la.y, lb.x, lb.y});
-        }
-      }
+      for (int e = 0; e < 2; ++e) softmax_keys_split<NT>(s[e], T, g, phi[e], plo[e]);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -426,9 +375,9 @@ __global__ __launch_bounds__(512) void cell_qkv_attention_mx_kernel(const uint16
             const int dcol0 = (hp + e) * HD + 16 * dt + 4 * (r16 & 3);    // first of the 4 dims this lane addresses for the transposed read
             const int dcol = kGroupDims == 64 ? ((((dcol0 >> 4) ^ (r16 >> 2)) << 4) | (dcol0 & 15)) : dcol0;      // (row & 3 == r16 >> 2)
             const int voff = (dcol >> 3) * 32 + (dcol & 7) * 2;           // byte offset of their hi halves inside a V row; + 16: lo halves
-            const char* va = vimg + (32 * t + 4 * g + (r16 >> 2)) * G::VROWB + voff;
-            const f16x4c h0 = lds_read_tr16c(va), l0 = lds_read_tr16c(va + 16);
-            const f16x4c h1 = lds_read_tr16c(va + 16 * G::VROWB), l1 = lds_read_tr16c(va + 16 * G::VROWB + 16);
+            const char* va = vimg + (32 * t + 4 * g + (r16 >> 2)) * M::VROWB + voff;
+            const f16x4 h0 = lds_read_tr16(va), l0 = lds_read_tr16(va + 16);
+            const f16x4 h1 = lds_read_tr16(va + 16 * M::VROWB), l1 = lds_read_tr16(va + 16 * M::VROWB + 16);
             const f16x8 vhi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
             const f16x8 vlo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
             o[e] = mfma_f16(vlo, phi[e][t], o[e]);

@@ -1,8 +1,8 @@
 """cell_attention_mx.hip refills a three-slot LDS ring behind its step barriers and holds a cell's token rows, their fp8 / fp6 images and twelve
-accumulator tiles in registers for the whole kernel.  Compile-only (no GPU needed), the checks tests/test_kernel_resources.py makes of the
-fp16x3 kernel, restated for this file -- no spill, no scratch, no ds_read in flight across a barrier behind which a slot is refilled -- and
-the kernel's own budget: at most 256 vector registers (two waves per SIMD at 512 threads) and at most 160 KB of LDS, static plus the dynamic
-size its launcher asks for."""
+accumulator tiles in registers for the whole kernel.  Compile-only (no GPU needed): the kernel's own budget, at most 256 vector registers
+(two waves per SIMD at 512 threads) and at most 160 KB of LDS, static plus the dynamic size its launcher asks for.  No spill, no scratch and
+no ds_read in flight across a barrier behind which a slot is refilled: tests/test_kernel_resources.py, which lists this file beside the
+fp16x3 kernel's."""
 import os
 import re
 import subprocess
@@ -36,12 +36,6 @@ def usage(tmp_path_factory):
     return seen
 
 
-def test_no_spills_no_scratch(usage):
-    bad = [(k, f, v) for k, res in usage.items() for f, v in res.items() if f in ("VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]") and v != 0]
-    assert all("ScratchSize [bytes/lane]" in res and "VGPRs Spill" in res for res in usage.values()), usage
-    assert not bad, bad
-
-
 def _dynamic_lds():
     """the LDS map of CellMxGeom<384, 32>, restated from the constants of the source: ring of 3 stages, two K images, the V image, column sums and bias"""
     d, gd, ntp, tp, vrows = 384, 64, 4, 112, 128
@@ -59,31 +53,3 @@ def test_registers_and_lds(usage):
     assert res["VGPRs"] + res.get("AGPRs", 0) <= 256, res
     assert "static_assert(LDS <= 160 * 1024" in open(SRC).read()      # the source checks its own map; this restatement gives the figure
     assert res["LDS Size [bytes/block]"] + dyn <= LDS_CU, (res, dyn)
-
-
-def test_no_lds_read_in_flight_across_a_ring_barrier(tmp_path):
-    """Behind a step barrier the loader refills the slot of the previous stage: every ds_read of it must have RETURNED (s_waitcnt lgkmcnt(0))
-    before the wave reaches the barrier.  Walking back from every s_barrier in the ISA, the wait must come before any ds_read."""
-    asm = tmp_path / "k.s"
-    cmd = [B._hipcc()] + [f for f in B.FLAGS if f != "-fPIC"] + ["--cuda-device-only", "-S", SRC, "-o", str(asm)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = [l.strip() for l in open(asm) if l.strip() and not l.strip().startswith(";")]
-    bad, barriers, kernel = [], 0, None
-    for i, l in enumerate(lines):
-        m = re.match(r"(_ZN5ribca\w+):", l)
-        if m:
-            kernel = m.group(1)
-        if not l.startswith("s_barrier"):
-            continue
-        barriers += 1
-        for j in range(i - 1, max(i - 400, -1), -1):
-            if lines[j].startswith("s_waitcnt") and "lgkmcnt(0)" in lines[j]:
-                break
-            if lines[j].startswith("s_barrier") or lines[j].endswith(":") and lines[j].startswith("_ZN"):
-                break
-            if lines[j].startswith("ds_read"):
-                bad.append((kernel, i, lines[j]))
-                break
-    assert barriers >= 10, barriers
-    assert not bad, bad[:5]
